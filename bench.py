@@ -13,14 +13,19 @@ all-reduce over RCCL.
                    default for --scaling strong, where a 4-image shard (0.6 ms of kernels) is as
                    much host-bound as kernel-bound when every launch is enqueued from Python
 
-    python bench.py --gpus N --steps K --warmup W [--scaling strong] [--graph]
+    python bench.py --gpus N --steps K --warmup W [--scaling strong] [--graph] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 
-`--gpus N` with N > 1 and no RANK in the environment re-executes itself under
+`--gpus N` with N > 1 and no RANK in the environment runs itself as a child under
 torch.distributed.run with N ranks (one per GPU); it exits non-zero when fewer than N GPUs are
-visible.  Rank 0 prints ONE JSON line (see README / DESIGN.md for the field meanings); besides the
-headline it carries `other_configs`: the per-GPU shards of BASELINE.json configs[2..4] timed in
-the same process (N = 1 only).
+visible.  Rank 0 prints ONE JSON line (see README / DESIGN.md for the field meanings).  A plain run
+sets up, warms up, times the K steps and reports the headline (`value`, `ms_per_step`, the HBM
+roofline of the step).  `--full` adds what takes instrumentation or runs of its own: per-kernel
+HIP-event times and the MFMA roofline of the dominant kernel, counter traffic, the gather-path rate,
+the sustained figure, `other_configs` (the per-GPU shards of BASELINE.json configs[2..4] timed in
+the same process, N = 1 only) and `cpu_baseline`.
+`--dump-outputs DIR` writes what the last timed step computed (output and gradients; a fixed,
+seeded sample of the two large ones) as DIR/<name>.npy, so that two builds can be compared.
 """
 import argparse
 import json
@@ -91,6 +96,7 @@ class Workload:
         d = cfg["dil"]
         self.geo = (3,) * nd + (1,) * nd + (d,) * nd + (d,) * nd + (G, DG, 64, cfg["bias"])
         self.M = M
+        self.keep, self.last_out, self.last_grads = False, None, None
         if not (nd == 2 and cfg["modulated"]):
             # caller-allocated entry points (reference deformable_conv3d.cu:160-167, 434-442 ...)
             self.out = torch.empty_like(self.go)
@@ -112,12 +118,16 @@ class Workload:
     def forward(self):
         M, c = self.M, self.cfg
         if c["nd"] == 2 and c["modulated"]:
-            return M.modulated_deform_conv2d_forward_cuda(self.x, self.w, self.b, self.off, self.m, *self.geo)
-        if c["modulated"]:
+            out = M.modulated_deform_conv2d_forward_cuda(self.x, self.w, self.b, self.off, self.m, *self.geo)
+        elif c["modulated"]:
             M.modulated_deform_conv3d_forward_cuda(self.x, self.w, self.b, self.off, self.m, self.out, *self.geo)
+            out = self.out
         else:
             M.deform_conv3d_forward_cuda(self.x, self.w, self.b, self.off, self.out, *self.geo)
-        return self.out
+            out = self.out
+        if self.keep:
+            self.last_out = out
+        return out
 
     def backward(self):
         """-> (grad_weight, grad_bias)"""
@@ -125,6 +135,8 @@ class Workload:
         M, c = self.M, self.cfg
         if c["nd"] == 2 and c["modulated"]:
             r = M.modulated_deform_conv2d_backward_cuda(self.x, self.w, self.b, self.off, self.m, self.go, *self.geo)
+            if self.keep:
+                self.last_grads = r
             return r[3], r[4]
         with _capi.overwrite_grads():
             if c["modulated"]:
@@ -133,7 +145,14 @@ class Workload:
             else:
                 M.deform_conv3d_backward_cuda(self.x, self.w, self.b, self.off, self.gi, self.gw, self.gb,
                                               self.goff, self.go, *self.geo)
+        if self.keep:
+            self.last_grads = (self.gi, self.goff, self.gm, self.gw, self.gb)
         return self.gw, self.gb
+
+    def outputs(self):
+        """What the caller received from the last forward + backward made with `keep` set: the output and the five
+        gradients (not kept by default, so that a step frees its results as the caller's would)."""
+        return _named_outputs(self.last_out, self.last_grads)
 
 
 class _HipClock:
@@ -194,6 +213,13 @@ class _StubWorkload:
         time.sleep(2e-4 * self.B)
         return self.gw.clone(), self.gb.clone()
 
+    def outputs(self):
+        """Fixed stand-ins for the step's results (the stub computes nothing)."""
+        import torch
+        g = torch.Generator(device="cpu").manual_seed(self.B)
+        return _named_outputs(torch.randn(self.B, 4, 4, generator=g),
+                              (torch.randn(self.B, 8, 4, 4, generator=g), None, None, self.gw, self.gb))
+
 
 class _StubClock:
     stub = True
@@ -216,8 +242,47 @@ class _StubClock:
         return _StubWorkload(name, device)
 
 
+OUTPUT_NAMES = ("output", "grad_input", "grad_offset", "grad_mask", "grad_weight", "grad_bias")
+DUMP_SAMPLE = 1 << 22          # elements kept of an output larger than this: a fixed, seeded sample
+DUMP_LIMIT_BYTES = 64 << 20    # all files of --dump-outputs together
+
+
+def _named_outputs(out, grads):
+    """{name: tensor} of one step's results; the gradients a configuration does not have (grad_mask of an
+    unmodulated op, grad_bias without bias) are left out."""
+    named = dict(zip(OUTPUT_NAMES, (out,) + tuple(grads)))
+    return {k: v for k, v in named.items() if v is not None and v.numel() > 0}
+
+
+def outputs_to_host(outputs, sample=DUMP_SAMPLE):
+    """{file name: float32 / float64 numpy array} of `outputs`.  A tensor of more than `sample` elements is
+    represented by `sample` of them at indices drawn with a fixed seed (sorted, with repetition) and saved
+    as `<name>_sample`, so that two runs with the same arguments pick the same elements."""
+    import torch
+    host = {}
+    for name, t in outputs.items():
+        flat = t.detach().reshape(-1)
+        if flat.numel() > sample:
+            g = torch.Generator(device="cpu").manual_seed(20261016)
+            idx = torch.randint(0, flat.numel(), (sample,), generator=g).sort().values
+            flat, name = flat[idx.to(flat.device)], name + "_sample"
+        dt = torch.float64 if flat.dtype == torch.float64 else torch.float32
+        host[name] = flat.to(dtype=dt).cpu().numpy()
+    total = sum(a.nbytes for a in host.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit("bench.py: --dump-outputs would write %d bytes (limit %d)" % (total, DUMP_LIMIT_BYTES))
+    return host
+
+
+def write_outputs(host, out_dir):
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in host.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def resolve_world(gpus, env, visible_gpus):
-    """How this invocation runs.  -> ("spawn", N): re-execute under torch.distributed.run with N ranks;
+    """How this invocation runs.  -> ("spawn", N): run again under torch.distributed.run with N ranks;
     ("run", world, rank, local_rank): run as that rank.  Raises SystemExit (non-zero) when the
     request cannot be met -- it never silently runs fewer ranks than `--gpus` asked for."""
     if gpus < 1:
@@ -394,16 +459,24 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-other-configs", action="store_true")
-    ap.add_argument("--sustain-s", type=float, default=2.0,
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: per-kernel times and the roofline, counter traffic, the gather path, "
+                         "the sustained figure, the other BASELINE configurations and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last step computed as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-other-configs", action="store_true", help="with --full: skip the other configurations")
+    ap.add_argument("--sustain-s", type=float, default=None,
                     help="after the K timed steps, keep stepping for about this long and report sustained_ms_per_step "
-                         "(0 = skip); not part of `value`")
+                         "(0 = skip; default 2 with --full, else 0); not part of `value`")
     ap.add_argument("--scaling", choices=("weak", "strong"), default="weak")
     ap.add_argument("--graph", dest="graph", action="store_true", default=None,
                     help="replay the step from a HIP graph (default for --scaling strong)")
     ap.add_argument("--no-graph", dest="graph", action="store_false")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("bench.py: --steps must be >= 1")
+    sustain_s = args.sustain_s if args.sustain_s is not None else (2.0 if args.full else 0.0)
 
     import torch
     be = _StubClock() if os.environ.get("MDCONV_BENCH_STUB") == "1" else _HipClock()
@@ -417,7 +490,9 @@ def main():
         s.close()
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(plan[1]),
                "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
-        os.execv(sys.executable, cmd)
+        # a child process, not exec: this process may have initialised the GPU runtime already
+        import subprocess
+        sys.exit(subprocess.run(cmd).returncode)
     _, world, rank, local_rank = plan
     if not be.stub and not torch.cuda.is_available():
         raise SystemExit("bench.py needs a GPU (the product has no CPU path)")
@@ -493,6 +568,7 @@ def main():
                 (compute_and_exchange if reducer is not None else compute)()
         torch.cuda.current_stream().wait_stream(side)
         torch.cuda.synchronize()
+        wl.keep = bool(args.dump_outputs)   # the captured step's results are what every replay rewrites
         if reducer is not None and os.environ.get("MDCONV_BENCH_EXCHANGE") != "after":
             try:
                 graph = torch.cuda.CUDAGraph()
@@ -502,7 +578,7 @@ def main():
             except Exception as e:   # noqa: BLE001 -- any capture failure: fall back, say so
                 sys.stderr.write("bench.py: the collective could not be captured (%s); exchange after the replay\n" % (e,))
                 torch.cuda.synchronize()
-                graph = None
+                graph, wl.last_out, wl.last_grads = None, None, None
         if graph is None:
             graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(graph, capture_error_mode="thread_local"):
@@ -525,7 +601,9 @@ def main():
         step()
     be.sync()
     paths = "stub" if be.stub else _capi.last_path()
-    if graph is None and not be.stub:
+    # per-kernel events inside the timed region: --full only
+    profiled = args.full and graph is None and not be.stub
+    if profiled:
         _capi.profile_enable(True)
         _capi.profile_reset()
     if distributed:
@@ -534,6 +612,8 @@ def main():
     t0 = time.perf_counter()
     marks = [be.stamp()]
     for i in range(args.steps):
+        if i == args.steps - 1 and graph is None:
+            wl.keep = bool(args.dump_outputs)   # the results of the last step stay referenced for --dump-outputs
         step()
         marks.append(be.stamp())
     t_enq = time.perf_counter()
@@ -541,9 +621,13 @@ def main():
     if distributed:
         dist.barrier()
     elapsed = time.perf_counter() - t0
-    if be.stub:
+    # what the last timed step computed, copied out before anything else runs
+    dumped = outputs_to_host(wl.outputs()) if args.dump_outputs and rank == 0 else None
+    if not args.full:
+        prof = None
+    elif be.stub:
         prof, prof_src = {"stub_kernel": (args.steps, 1.0)}, "stub"
-    elif graph is None:
+    elif profiled:
         _capi.profile_enable(False)
         prof, prof_src = _capi.profile_read(), "HIP events around each kernel inside the timed region"
     else:
@@ -566,8 +650,8 @@ def main():
     # and cache state to show; the same step for >= --sustain-s seconds, HIP-event timed, makes those visible (and
     # gives a GPU-utilisation sampler something to see).  Reported next to the headline, never instead of it.
     sustained = None
-    if args.sustain_s > 0:
-        n_sus = max(args.steps, int(args.sustain_s / max(elapsed / args.steps, 1e-6)))
+    if sustain_s > 0:
+        n_sus = max(args.steps, int(sustain_s / max(elapsed / args.steps, 1e-6)))
         s0 = be.stamp()
         for _ in range(n_sus):
             step()
@@ -584,11 +668,6 @@ def main():
     step_ms = sorted(be.elapsed_ms(marks[i], marks[i + 1]) for i in range(args.steps))
     global_b = nominal_b * world if args.scaling == "weak" else nominal_b
     value = global_b * (wl.n_samples // wl.B) / (elapsed / args.steps) / 1e9
-    # dominant kernel = the profiled kernel with the largest measured average duration
-    gemms = {k: v for k, v in prof.items() if "col2im" not in k}
-    dom, (dom_n, dom_ms) = max(gemms.items(), key=lambda kv: kv[1][1])
-    achieved = wl.gemm_flop / (dom_ms * 1e-3) / 1e12 if dom_ms > 0 else 0.0
-    traffic, traffic_src = (None, "stub") if be.stub else measured_traffic(dom)
     comp = wl.bytes
     result = {
         "metric": "fwd+bwd GSamples/s, MDCN2d 3x3 C=256 56x56 B=32; %HBM roofline",
@@ -596,8 +675,6 @@ def main():
         "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4), "higher_is_better": True,
         "ms_per_step_median": round(step_ms[len(step_ms) // 2], 4),
         "host_enqueue_ms_per_step": round((t_enq - t0) / args.steps * 1e3, 4),
-        "sustained_ms_per_step": None if sustained is None else round(sustained[0], 4),
-        "sustained_steps": None if sustained is None else sustained[1],
         "launch_mode": "hip graph replay" if graph is not None else "eager (one Python call per entry point)",
         "scaling": args.scaling, "exchange": exchange,
         "exchange_mode": None if reducer is None else reducer.last_mode, "vs_baseline": None, "dtype": "f32",
@@ -605,26 +682,39 @@ def main():
         "config": {"workload": "%s, B=%d per GPU, forward+backward (BASELINE.json configs[1])" % (wl.cfg["what"], wl.B),
                    "global_batch": global_b, "parallelism": "dp%d batch-sharded" % world,
                    "kernel_path": paths},
-        "roofline": {"bound": "mfma", "kernel": dom, "achieved": round(achieved, 2),
-                     "peak": PEAK_F32_MFMA_TFLOPS, "unit": "TFLOP/s",
-                     "frac": round(achieved / PEAK_F32_MFMA_TFLOPS, 4), "traffic": traffic,
-                     "traffic_source": traffic_src,
-                     "flop_per_launch": wl.gemm_flop, "avg_ms": round(dom_ms, 4), "launches": dom_n},
-        "kernels_ms": {k: round(v[1], 4) for k, v in prof.items()}, "kernels_ms_source": prof_src,
         "hbm_roofline": {"compulsory_bytes": int(comp),
                          "achieved_GBs": round(comp / (ms_per_step * 1e-3) / 1e9, 1),
                          "peak_GBs": HBM_PEAK_GBS,
                          "frac": round(comp / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)},
-        "traffic": ({"hbm_bytes_per_step": None, "source": "stub" if be.stub else "counters are collected on the B = 32 shard only"}
-                    if be.stub or wl.B != nominal_b else step_traffic("cfg2", comp)),
-        "gather_path": None if be.stub else gather_path(wl, prof),
     }
-    if world == 1 and not distributed and not args.no_other_configs and not be.stub:
-        del wl
-        torch.cuda.empty_cache()
-        result["other_configs"] = {n: time_other_config(n, device) for n in ("cfg3", "cfg4", "cfg5")}
-    if world == 1 and not args.no_cpu_baseline and not be.stub:
-        result["cpu_baseline"] = cpu_baseline()
+    if args.full or sustained is not None:
+        result["sustained_ms_per_step"] = None if sustained is None else round(sustained[0], 4)
+        result["sustained_steps"] = None if sustained is None else sustained[1]
+    if args.full:
+        # dominant kernel = the profiled kernel with the largest measured average duration
+        gemms = {k: v for k, v in prof.items() if "col2im" not in k}
+        dom, (dom_n, dom_ms) = max(gemms.items(), key=lambda kv: kv[1][1])
+        achieved = wl.gemm_flop / (dom_ms * 1e-3) / 1e12 if dom_ms > 0 else 0.0
+        traffic, traffic_src = (None, "stub") if be.stub else measured_traffic(dom)
+        result.update({
+            "roofline": {"bound": "mfma", "kernel": dom, "achieved": round(achieved, 2),
+                         "peak": PEAK_F32_MFMA_TFLOPS, "unit": "TFLOP/s",
+                         "frac": round(achieved / PEAK_F32_MFMA_TFLOPS, 4), "traffic": traffic,
+                         "traffic_source": traffic_src,
+                         "flop_per_launch": wl.gemm_flop, "avg_ms": round(dom_ms, 4), "launches": dom_n},
+            "kernels_ms": {k: round(v[1], 4) for k, v in prof.items()}, "kernels_ms_source": prof_src,
+            "traffic": ({"hbm_bytes_per_step": None, "source": "stub" if be.stub else "counters are collected on the B = 32 shard only"}
+                        if be.stub or wl.B != nominal_b else step_traffic("cfg2", comp)),
+            "gather_path": None if be.stub else gather_path(wl, prof),
+        })
+        if world == 1 and not distributed and not args.no_other_configs and not be.stub:
+            del wl
+            torch.cuda.empty_cache()
+            result["other_configs"] = {n: time_other_config(n, device) for n in ("cfg3", "cfg4", "cfg5")}
+        if world == 1 and not args.no_cpu_baseline and not be.stub:
+            result["cpu_baseline"] = cpu_baseline()
+    if dumped is not None:
+        write_outputs(dumped, args.dump_outputs)
     print(json.dumps(result))
     if distributed:
         dist.destroy_process_group()

@@ -144,18 +144,26 @@ def test_extension_module_surface_matches_reference():
     }
     for name, nargs in expect.items():
         assert len(inspect.signature(getattr(M, name)).parameters) == nargs, name
-    # Where the reference tree is present (the build container; never on the GPU box) the table above is not trusted:
-    # the eight call sites of /root/reference/modulated_deform_conv.py (:28, 57, 112, 142, 194, 225, 281, 313) are
-    # read with `ast` and compared argument by argument -- count AND order -- with our binding
-    # (tools/check_reference_call_sites.py; nothing of the reference is copied).
-    if os.path.isdir("/root/reference"):
-        import importlib.util
-        root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-        spec = importlib.util.spec_from_file_location("check_reference_call_sites",
-                                                      os.path.join(root, "tools", "check_reference_call_sites.py"))
-        mod = importlib.util.module_from_spec(spec)
-        spec.loader.exec_module(mod)
-        assert mod.check("/root/reference") == expect
+    # ... and the ORDER, argument by argument (the tensors, then kernel / stride / pad / dilation
+    # per axis h, w[, l], then group, deformable_group, in_step, with_bias); tools/check_reference_call_sites.py compares
+    # the same order with the call sites of the reference's wrapper where that tree is at hand
+    tensors = {
+        "deform_conv2d_forward_cuda": "input weight bias offset output",
+        "deform_conv2d_backward_cuda": "input weight bias offset grad_input grad_weight grad_bias grad_offset grad_output",
+        "modulated_deform_conv2d_forward_cuda": "input weight bias offset mask",
+        "modulated_deform_conv2d_backward_cuda": "input weight bias offset mask grad_output",
+        "deform_conv3d_forward_cuda": "input weight bias offset output",
+        "deform_conv3d_backward_cuda": "input weight bias offset grad_input grad_weight grad_bias grad_offset grad_output",
+        "modulated_deform_conv3d_forward_cuda": "input weight bias offset mask output",
+        "modulated_deform_conv3d_backward_cuda":
+            "input weight bias offset mask grad_input grad_weight grad_bias grad_offset grad_mask grad_output",
+    }
+    for name, t in tensors.items():
+        axes = "hwl"[:3 if "3d" in name else 2]
+        want = t.split() + ["%s_%s" % (p, a) for p in ("kernel", "stride", "pad", "dilation") for a in axes]
+        want += ["group", "deformable_group", "in_step", "with_bias"]
+        assert list(inspect.signature(getattr(M, name)).parameters) == want, name
+        assert len(want) == expect[name], name
 
 
 def test_python_surface_and_cpu_behaviour():

@@ -61,15 +61,15 @@ def test_workload_table_matches_survey_8d():
         assert abs(3 * gemm - flop) / flop < 2e-3
 
 
-def _stub_bench(*flags):
+def _stub_bench(*flags, full=True, steps=4):
     """bench.py end to end with the host-only stub workload (MDCONV_BENCH_STUB=1: sleeps instead of kernels, gloo
     instead of RCCL): the launcher, rank / shard arithmetic, barrier + MAX-over-ranks timing and the JSON line."""
     import json
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
     env["MDCONV_BENCH_STUB"] = "1"
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "4", "--warmup", "1",
-                        "--sustain-s", "0.05", "--no-cpu-baseline"] + list(flags),
-                       capture_output=True, text=True, env=env, timeout=600)
+    extra = ["--full", "--sustain-s", "0.05", "--no-cpu-baseline"] if full else []
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", str(steps), "--warmup", "1"]
+                       + extra + list(flags), capture_output=True, text=True, env=env, timeout=600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout            # ONE JSON line, from rank 0 only
@@ -78,7 +78,7 @@ def _stub_bench(*flags):
 
 @pytest.mark.parametrize("scaling", ["weak", "strong"])
 def test_two_rank_launch_shards_and_reports_whole_job_throughput(scaling):
-    """`--gpus 2` without a launcher re-executes under torch.distributed.run with two ranks (here on CPU, gloo);
+    """`--gpus 2` without a launcher runs itself as a child under torch.distributed.run with two ranks (here on CPU, gloo);
     weak: B = 32 per rank, global batch 64; strong: global batch 32 in shards of 16; `value`
     is the whole job's samples over the MAX-over-ranks time."""
     d = _stub_bench("--gpus", "2", "--scaling", scaling)
@@ -101,3 +101,40 @@ def test_single_rank_stub_line_has_the_contract_fields():
         assert k in d, k
     assert d["n_gpus"] == 1 and d["config"]["global_batch"] == 32 and d["vs_baseline"] is None
     assert d["data"].startswith("STUB") and d["config"]["kernel_path"] == "stub"   # can never pass for a measurement
+
+
+def test_plain_stub_line_is_the_headline_only():
+    """Without --full the run times its steps and reports the headline; nothing that takes instrumentation or runs
+    of its own (per-kernel times, sustained figure, other configurations, CPU baseline)."""
+    d = _stub_bench(full=False, steps=7)
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup", "hbm_roofline"):
+        assert k in d, k
+    assert d["steps"] == 7 and d["ms_per_step"] > 0 and d["higher_is_better"] is True and d["dtype"] == "f32"
+    for k in ("roofline", "kernels_ms", "sustained_ms_per_step", "traffic", "gather_path", "other_configs", "cpu_baseline"):
+        assert k not in d, k
+
+
+def test_dump_outputs_writes_the_last_step(tmp_path):
+    """--dump-outputs DIR: one float32 / float64 .npy per array the step returns, identical from run to run."""
+    import numpy as np
+    dumps = []
+    for i in range(2):
+        out = tmp_path / ("run%d" % i)
+        d = _stub_bench("--dump-outputs", str(out), full=False)
+        assert d["steps"] == 4
+        files = sorted(p.name for p in out.iterdir())
+        assert files == ["grad_bias.npy", "grad_input.npy", "grad_weight.npy", "output.npy"], files
+        dumps.append({f: np.load(out / f) for f in files})
+    for f, a in dumps[0].items():
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, dumps[1][f]), f
+
+
+def test_dump_outputs_samples_large_arrays_with_a_fixed_seed():
+    import torch
+    big = torch.arange(5000, dtype=torch.float32)
+    outs = {"output": big, "grad_weight": torch.ones(3, 3, dtype=torch.float64)}
+    a, b = bench.outputs_to_host(outs, sample=1000), bench.outputs_to_host(outs, sample=1000)
+    assert sorted(a) == ["grad_weight", "output_sample"]
+    assert a["output_sample"].shape == (1000,) and a["output_sample"].dtype.name == "float32"
+    assert a["grad_weight"].dtype.name == "float64" and a["grad_weight"].shape == (9,)
+    assert (a["output_sample"] == b["output_sample"]).all() and len(set(a["output_sample"].tolist())) > 500

@@ -13,8 +13,8 @@ and through the parameter names of our binding mapped the same way (kernel_h -> 
 Also checks how many values the call site unpacks (the 5-tuple of the MDCN2d backward, one tensor of its forward).
 
     python tools/check_reference_call_sites.py [/root/reference]        exit 0 = all eight agree
-`tests/test_abi_cpu.py::test_extension_module_surface_matches_reference` runs it when /root/reference exists
-(this container) and falls back to the committed arity table elsewhere (the GPU box has no reference tree)."""
+`tests/test_abi_cpu.py::test_extension_module_surface_matches_reference` checks the same order against a table of
+its own, so that the suite needs no reference tree."""
 import ast
 import inspect
 import os
