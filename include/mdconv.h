@@ -50,6 +50,13 @@ extern "C" {
 
 /* AT_DISPATCH_FLOATING_TYPES_AND_HALF (mdeformable_conv.cu:101) + bfloat16 */
 enum { MDCONV_F32 = 0, MDCONV_F16 = 1, MDCONV_F64 = 2, MDCONV_BF16 = 3 };
+/* "fp32 sampling": flag ORed into mdconv_desc.dtype -- MDCONV_F16 | MDCONV_SAMPLING_F32 or
+ * MDCONV_BF16 | MDCONV_SAMPLING_F32.  offset, mask, grad_offset and grad_mask are then fp32 while
+ * input, weight, bias, output, grad_output, grad_input, grad_weight and grad_bias keep the 16-bit
+ * type: sampling positions are not rounded to 16 bits (a bf16 offset of 32-64 px is a multiple of
+ * 0.25 px).  Every shape and call mode of the 16-bit type runs with it, on the same kernel family.
+ * With MDCONV_F32 / MDCONV_F64 the flag is MDCONV_EINVAL. */
+#define MDCONV_SAMPLING_F32 0x10
 
 enum {
   MDCONV_OK = 0,
@@ -67,7 +74,8 @@ enum { MDCONV_PATH_AUTO = 0, MDCONV_PATH_DIRECT = 1, MDCONV_PATH_MFMA = 2 };
 typedef struct mdconv_desc {
   int ndim;       /* 2 or 3, | MDCONV_DESC_V2 when the v2 fields below are filled in */
   int modulated;  /* 0 = DeformConv (DCNv1), 1 = ModulatedDeformConv (DCNv2) */
-  int dtype;      /* MDCONV_F32 / F16 / F64 / BF16 -- element type of every tensor */
+  int dtype;      /* MDCONV_F32 / F16 / F64 / BF16 -- element type of every tensor (offset / mask and their
+                     gradients: fp32 when MDCONV_SAMPLING_F32 is ORed in, see above) */
   int batch;      /* B */
   int c_in;       /* C_in  */
   int c_out;      /* C_out */

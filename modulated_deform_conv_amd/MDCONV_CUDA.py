@@ -103,6 +103,27 @@ def _check_side(d, nd, K, offset, mask, other, other_name, osz):
                                                                 (d.batch, d.c_out) + osz))
 
 
+def _sampling_f32(input, offset, mask=None):
+    """fp16 / bf16 tensors with fp32 `offset` and `mask` ("fp32 sampling", include/mdconv.h: MDCONV_SAMPLING_F32):
+    sampling positions are not rounded to 16 bits.  Any other mix of dtypes is refused by `_same`."""
+    return (input.dtype in (torch.float16, torch.bfloat16) and offset.dtype == torch.float32
+            and (mask is None or mask.numel() == 0 or mask.dtype == torch.float32))
+
+
+def _check_dtypes(d, input, offset, mask, **tensors):
+    """`offset` / `mask` (and, in `tensors`, grad_offset / grad_mask) share the input's dtype, or are all fp32 with
+    fp16 / bf16 tensors, which sets MDCONV_SAMPLING_F32 in the descriptor; every other tensor has the input's dtype."""
+    side = {k: tensors.pop(k) for k in ("grad_offset", "grad_mask") if k in tensors}
+    if not _sampling_f32(input, offset, mask):
+        _same(input, offset=offset, mask=mask, **side, **tensors)
+        return
+    _same(input, **tensors)
+    if offset.device != input.device:
+        raise RuntimeError("offset must be on the device of input (%s), got %s" % (input.device, offset.device))
+    _same(offset, mask=mask, **side)
+    d.dtype |= _capi.SAMPLING_F32
+
+
 def _same(ref, **tensors):
     for name, t in tensors.items():
         if t is None or t.numel() == 0:
@@ -146,8 +167,8 @@ def _forward(nd, modulated, fn_name, input, weight, bias, offset, mask, output, 
     input = _layout(d, input, False)
     osz = _out_shape(d, nd)
     _check_side(d, nd, _prod(ksz), offset, mask if modulated else None, output, "output", osz)
-    _same(input, weight=weight, offset=offset, mask=mask if modulated else None,
-          bias=bias if with_bias else None, output=output)
+    _check_dtypes(d, input, offset, mask if modulated else None, weight=weight,
+                  bias=bias if with_bias else None, output=output)
     if with_bias and bias.numel() != d.c_out:
         raise RuntimeError("bias has %d elements, expected %d" % (bias.numel(), d.c_out))
     if output is None:
@@ -194,9 +215,9 @@ def deform_conv2d_backward_cuda(input, weight, bias, offset, grad_input, grad_we
 
 def _backward_checks(input, weight, offset, mask, grad_input, grad_weight, grad_bias, grad_offset,
                      grad_mask, grad_output, d, with_bias):
-    _same(input, weight=weight, offset=offset, mask=mask, grad_input=grad_input,
-          grad_weight=grad_weight, grad_offset=grad_offset, grad_mask=grad_mask,
-          grad_output=grad_output, grad_bias=grad_bias if with_bias else None)
+    _check_dtypes(d, input, offset, mask, weight=weight, grad_input=grad_input,
+                  grad_weight=grad_weight, grad_offset=grad_offset, grad_mask=grad_mask,
+                  grad_output=grad_output, grad_bias=grad_bias if with_bias else None)
     for name, g, ref in (("grad_input", grad_input, input), ("grad_weight", grad_weight, weight),
                          ("grad_offset", grad_offset, offset), ("grad_mask", grad_mask, mask)):
         if ref is not None and g.numel() != ref.numel():

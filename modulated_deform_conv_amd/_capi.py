@@ -11,6 +11,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MDCONV_LIB") or os.path.join(HERE, "libmdconv_hip.so")
 
 F32, F16, F64, BF16 = 0, 1, 2, 3
+SAMPLING_F32 = 0x10   # MDCONV_SAMPLING_F32: ORed into F16 / BF16, offset / mask and their gradients are fp32
 PATH_AUTO, PATH_DIRECT, PATH_MFMA = 0, 1, 2
 ABI_VERSION = 2
 DESC_V2 = 0x100   # MDCONV_DESC_V2: the descriptor carries accumulate / input_layout / path

@@ -29,13 +29,13 @@ namespace mdconv {
 namespace {
 
 
-template <int ND, bool MOD, typename T, int WAVES, int NKS>
+template <int ND, bool MOD, typename T, int WAVES, int NKS, typename SE = typename T::Raw>
 __global__ __launch_bounds__(64 * WAVES, (WAVES >= 8 || NKS >= 16 || ND == 3) ? 1 : 2) void hp_bwd_kernel(
     Geom g, HpDims hd, const typename T::Raw *__restrict__ xt, const U4 *__restrict__ wpb,
     const int4 *__restrict__ btab, const typename T::Raw *__restrict__ gout,
-    const typename T::Raw *__restrict__ offset, const typename T::Raw *__restrict__ mask,
-    typename T::Raw *__restrict__ gcol, typename T::Raw *__restrict__ grad_offset,
-    typename T::Raw *__restrict__ grad_mask, float *__restrict__ part, int *__restrict__ cnt) {
+    const SE *__restrict__ offset, const SE *__restrict__ mask,
+    typename T::Raw *__restrict__ gcol, SE *__restrict__ grad_offset,
+    SE *__restrict__ grad_mask, float *__restrict__ part, int *__restrict__ cnt) {
   using Raw = typename T::Raw;
   constexpr int NC = 1 << ND, NP = NC / 2;
   constexpr int MB2 = NKS / 2;
@@ -125,15 +125,15 @@ __global__ __launch_bounds__(64 * WAVES, (WAVES >= 8 || NKS >= 16 || ND == 3) ? 
         for (int w = w0; w < w1; ++w) sum += red[(w * (ND + 1) + a) * 32 + p];
         const int bb = nn / g.S_o, pp = nn - bb * g.S_o;
         const int64_t seg = (int64_t)bb * g.DG + dgi;
-        Raw *dst = a < ND ? grad_offset + (seg * (ND * g.K) + ND * tap + a) * g.S_o + pp
-                          : grad_mask + (seg * g.K + tap) * g.S_o + pp;
-        T::stf(dst, g.acc_data ? T::ldf(dst) + sum : sum);
+        SE *dst = a < ND ? grad_offset + (seg * (ND * g.K) + ND * tap + a) * g.S_o + pp
+                        : grad_mask + (seg * g.K + tap) * g.S_o + pp;
+        samp_st(dst, g.acc_data ? samp_ld(dst) + sum : sum);
       }
     }
   };
 
   // offsets / mask of the lane's pixel, one tile ahead
-  Raw dlr[ND], mlr;   // raw 16-bit values until they are needed (a conversion here is a use of the load where it is issued)
+  SE dlr[ND], mlr;   // raw 16-bit values until they are needed (a conversion here is a use of the load where it is issued)
   auto fetch = [&](int tile) {
     const int nn = min(tile * 32 + pl, g.N - 1);
     const int bb = nn / g.S_o, pp = nn - bb * g.S_o;
@@ -163,9 +163,9 @@ __global__ __launch_bounds__(64 * WAVES, (WAVES >= 8 || NKS >= 16 || ND == 3) ? 
     TapCoef<ND, float> tc;
     float dl[ND];
 #pragma unroll
-    for (int a = 0; a < ND; ++a) dl[a] = T::ldf(&dlr[a]);
+    for (int a = 0; a < ND; ++a) dl[a] = samp_ld(&dlr[a]);
     make_tap<ND, float>(g, oc, tcd, dl, true, tc);
-    const float m_n = MOD ? T::ldf(&mlr) : 1.f;
+    const float m_n = MOD ? samp_ld(&mlr) : 1.f;
     if (tile + 1 < t_hi) fetch(tile + 1);
     HpCorners<ND> hc;
     hp_corners<ND>(tc, hc);
@@ -287,34 +287,34 @@ __global__ __launch_bounds__(64 * WAVES, (WAVES >= 8 || NKS >= 16 || ND == 3) ? 
 
 }  // namespace
 
-size_t hp_bwd_lds_bytes(const Geom &g, const HpDims &hd) {
+static size_t hp_bwd_lds_bytes(const Geom &g, const HpDims &hd) {
   return (size_t)hd.OpL * kPP * 2 + (size_t)32 * (hd.OpL + 8) * 2 + (size_t)hd.waves * 32 * kPP * 2 +
          (size_t)hd.waves * (g.nd + 1) * 32 * 4;
 }
 
-template <int ND, bool MOD, typename T, int WAVES, int NKS>
+template <int ND, bool MOD, typename T, int WAVES, int NKS, typename SE>
 static int launch_bwd_hp(const Geom &g, const HpDims &hd, const Tensors &t, const void *xt,
                          const void *wpb, const int4 *btab, void *gcol, float *part, int *cnt,
                          hipStream_t stream) {
   using Raw = typename T::Raw;
   const size_t lds = hp_bwd_lds_bytes(g, hd);
   if (lds > 64 * 1024) {
-    hipError_t ea = hipFuncSetAttribute((const void *)hp_bwd_kernel<ND, MOD, T, WAVES, NKS>,
+    hipError_t ea = hipFuncSetAttribute((const void *)hp_bwd_kernel<ND, MOD, T, WAVES, NKS, SE>,
                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (ea != hipSuccess) { set_error("hipFuncSetAttribute: %s", hipGetErrorString(ea)); return MDCONV_ELAUNCH; }
   }
-  hipLaunchKernelGGL((hp_bwd_kernel<ND, MOD, T, WAVES, NKS>), dim3(hd.ranges, g.K), dim3(64 * WAVES), lds,
+  hipLaunchKernelGGL((hp_bwd_kernel<ND, MOD, T, WAVES, NKS, SE>), dim3(hd.ranges, g.K), dim3(64 * WAVES), lds,
                      stream, g, hd, (const Raw *)xt, (const U4 *)wpb, btab, (const Raw *)t.grad_output,
-                     (const Raw *)t.offset, (const Raw *)t.mask, (Raw *)gcol, (Raw *)t.grad_offset,
-                     (Raw *)t.grad_mask, part, cnt);
+                     (const SE *)t.offset, (const SE *)t.mask, (Raw *)gcol, (SE *)t.grad_offset,
+                     (SE *)t.grad_mask, part, cnt);
   return check_launch("hp_bwd");
 }
 
-template <int ND, bool MOD, typename T>
+template <int ND, bool MOD, typename T, typename SE>
 static int dispatch_bwd_hp(const Geom &g, const HpDims &hd, const Tensors &t, const void *xt,
                            const void *wpb, const int4 *btab, void *gcol, float *part, int *cnt,
                            hipStream_t stream) {
-#define HP_BWD(W, N) return launch_bwd_hp<ND, MOD, T, W, N>(g, hd, t, xt, wpb, btab, gcol, part, cnt, stream)
+#define HP_BWD(W, N) return launch_bwd_hp<ND, MOD, T, W, N, SE>(g, hd, t, xt, wpb, btab, gcol, part, cnt, stream)
 #define HP_BWD_W(W)                                                                            \
   switch (hd.nks) {                                                                            \
     case 2: HP_BWD(W, 2);                                                                      \
@@ -332,20 +332,31 @@ static int dispatch_bwd_hp(const Geom &g, const HpDims &hd, const Tensors &t, co
 #undef HP_BWD
 }
 
+#define HP_DISPATCH(T, SE)                                                                         \
+  do {                                                                                            \
+    if (g.nd == 2)                                                                                \
+      return g.modulated ? dispatch_bwd_hp<2, true, T, SE>(g, hd, t, xt, wpb, btab, gcol, part, cnt, stream)  \
+                         : dispatch_bwd_hp<2, false, T, SE>(g, hd, t, xt, wpb, btab, gcol, part, cnt, stream); \
+    return g.modulated ? dispatch_bwd_hp<3, true, T, SE>(g, hd, t, xt, wpb, btab, gcol, part, cnt, stream)    \
+                       : dispatch_bwd_hp<3, false, T, SE>(g, hd, t, xt, wpb, btab, gcol, part, cnt, stream);   \
+  } while (0)
+#ifndef HP_SAMPLING_F32_UNIT
 int hp_backward_launch(const Geom &g, const HpDims &hd, int dtype, const Tensors &t, const void *xt,
                        const void *wpb, const int4 *btab, void *gcol, float *part, int *cnt,
                        hipStream_t stream) {
-#define HP_DISPATCH(T)                                                                            \
-  do {                                                                                            \
-    if (g.nd == 2)                                                                                \
-      return g.modulated ? dispatch_bwd_hp<2, true, T>(g, hd, t, xt, wpb, btab, gcol, part, cnt, stream)  \
-                         : dispatch_bwd_hp<2, false, T>(g, hd, t, xt, wpb, btab, gcol, part, cnt, stream); \
-    return g.modulated ? dispatch_bwd_hp<3, true, T>(g, hd, t, xt, wpb, btab, gcol, part, cnt, stream)    \
-                       : dispatch_bwd_hp<3, false, T>(g, hd, t, xt, wpb, btab, gcol, part, cnt, stream);   \
-  } while (0)
-  if (dtype == MDCONV_F16) HP_DISPATCH(F16);
-  HP_DISPATCH(BF16);
-#undef HP_DISPATCH
+  if (t.samp32) return hp_backward_launch_s32(g, hd, dtype, t, xt, wpb, btab, gcol, part, cnt, stream);
+  if (dtype == MDCONV_F16) HP_DISPATCH(F16, F16::Raw);
+  HP_DISPATCH(BF16, BF16::Raw);
 }
+#else
+// fp32 offsets / masks (MDCONV_SAMPLING_F32): the same kernels with SE = float, compiled in their own unit (hp_bwd_s32.hip)
+int hp_backward_launch_s32(const Geom &g, const HpDims &hd, int dtype, const Tensors &t, const void *xt,
+                           const void *wpb, const int4 *btab, void *gcol, float *part, int *cnt,
+                           hipStream_t stream) {
+  if (dtype == MDCONV_F16) HP_DISPATCH(F16, float);
+  HP_DISPATCH(BF16, float);
+}
+#endif
+#undef HP_DISPATCH
 
 }  // namespace mdconv

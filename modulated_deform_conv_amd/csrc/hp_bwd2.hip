@@ -45,13 +45,13 @@ template <int ND> __device__ __forceinline__ void advance_pixel(const Geom &g, i
 // (pixel, deformable group) states per tile: the state pipeline is the critical path there) that run the per-(tap, pixel) scalar
 // pipeline -- offsets / mask, sampling state, CSR counting, the final grad_offset / grad_mask
 // arithmetic -- beside them (it was 47 % of the tile time when wave 0 did it on top of its share).
-template <int ND, bool MOD, typename T, int WAVES, int NKS, int NS>
+template <int ND, bool MOD, typename T, int WAVES, int NKS, int NS, typename SE = typename T::Raw>
 __global__ __launch_bounds__(64 * (WAVES + NS), WAVES >= 8 ? 1 : 2) void hp_bwd2_kernel(
     Geom g, HpDims hd, const typename T::Raw *__restrict__ xt, const U4 *__restrict__ wpb,
     const int4 *__restrict__ btab, const typename T::Raw *__restrict__ gout,
-    const typename T::Raw *__restrict__ offset, const typename T::Raw *__restrict__ mask,
-    typename T::Raw *__restrict__ gcol, typename T::Raw *__restrict__ grad_offset,
-    typename T::Raw *__restrict__ grad_mask, float *__restrict__ part, int *__restrict__ cnt) {
+    const SE *__restrict__ offset, const SE *__restrict__ mask,
+    typename T::Raw *__restrict__ gcol, SE *__restrict__ grad_offset,
+    SE *__restrict__ grad_mask, float *__restrict__ part, int *__restrict__ cnt) {
   using Raw = typename T::Raw;
   constexpr int NC = 1 << ND, NP = NC / 2;
   constexpr int MB2 = NKS / 2;
@@ -108,7 +108,7 @@ __global__ __launch_bounds__(64 * (WAVES + NS), WAVES >= 8 ? 1 : 2) void hp_bwd2
       out_coords<ND>(g, p_first, noc[ps]);
       advance_pixel<ND>(g, pl, nb[ps], noc[ps]);
     }
-    Raw dlr[SP][ND], mlr[SP];   // raw 16-bit values until build() (a conversion in fetch() is a use of the load where it is issued)
+    SE dlr[SP][ND], mlr[SP];   // raw 16-bit values until build() (a conversion in fetch() is a use of the load where it is issued)
     auto fetch = [&]() {   // offsets / mask of the pixel at (nb, noc)
 #pragma unroll
       for (int ps = 0; ps < SP; ++ps) {
@@ -141,8 +141,8 @@ __global__ __launch_bounds__(64 * (WAVES + NS), WAVES >= 8 ? 1 : 2) void hp_bwd2
           for (int a = 1; a < ND; ++a) pix = pix * g.out_sz[a] + noc[ps][a];
           float dlf[ND], mlf = 1.f;
 #pragma unroll
-          for (int a = 0; a < ND; ++a) dlf[a] = T::ldf(&dlr[ps][a]);
-          if (MOD) mlf = T::ldf(&mlr[ps]);
+          for (int a = 0; a < ND; ++a) dlf[a] = samp_ld(&dlr[ps][a]);
+          if (MOD) mlf = samp_ld(&mlr[ps]);
           TapCoef<ND, float> tc;
           make_tap<ND, float>(g, noc[ps], tcd, dlf, true, tc);
           HpCorners<ND> hc;
@@ -171,8 +171,8 @@ __global__ __launch_bounds__(64 * (WAVES + NS), WAVES >= 8 ? 1 : 2) void hp_bwd2
           for (int a = 0; a <= ND; ++a) f.old[a] = 0.f;
           if (f.live && g.acc_data) {   // accumulate mode: previous values, needed a tile later
 #pragma unroll
-            for (int a = 0; a < ND; ++a) f.old[a] = T::ldf(grad_offset + f.off_idx + (int64_t)a * g.S_o);
-            if (MOD) f.old[ND] = T::ldf(grad_mask + f.msk_idx);
+            for (int a = 0; a < ND; ++a) f.old[a] = samp_ld(grad_offset + f.off_idx + (int64_t)a * g.S_o);
+            if (MOD) f.old[ND] = samp_ld(grad_mask + f.msk_idx);
           }
           if (f.live) {
             // scatter anchor of this sample (first pass of the CSR build, hp_col2im.hip): one
@@ -218,8 +218,8 @@ __global__ __launch_bounds__(64 * (WAVES + NS), WAVES >= 8 ? 1 : 2) void hp_bwd2
             }
           }
 #pragma unroll
-          for (int a = 0; a < ND; ++a) T::stf(grad_offset + f.off_idx + (int64_t)a * g.S_o, goff[a] * f.mg + f.old[a]);
-          if (MOD) T::stf(grad_mask + f.msk_idx, gm + f.old[ND]);
+          for (int a = 0; a < ND; ++a) samp_st(grad_offset + f.off_idx + (int64_t)a * g.S_o, goff[a] * f.mg + f.old[a]);
+          if (MOD) samp_st(grad_mask + f.msk_idx, gm + f.old[ND]);
         }
       }
     };
@@ -462,6 +462,7 @@ __global__ __launch_bounds__(64 * (WAVES + NS), WAVES >= 8 ? 1 : 2) void hp_bwd2
 }  // namespace
 
 
+#ifndef HP_SAMPLING_F32_UNIT
 size_t hp_bwd2_lds_bytes(const Geom &g, const HpDims &hd) {
   const int nc = 1 << g.nd;
   const int lpp = hd.Cp / 8, lpd = g.DG == 1 ? lpp : g.Cdg / 8;
@@ -471,34 +472,35 @@ size_t hp_bwd2_lds_bytes(const Geom &g, const HpDims &hd) {
   return (size_t)2 * hd.OpL * kPP * 2 + (size_t)2 * 32 * (hd.Cp + 8) * 2 +
          (size_t)2 * 32 * g.DG * (2 * nc + 4) * 4 + (size_t)32 * g.DG * msub * nc * 4;
 }
+#endif
 
-template <int ND, bool MOD, typename T, int WAVES, int NKS, int NS>
+template <int ND, bool MOD, typename T, int WAVES, int NKS, int NS, typename SE>
 static int launch_bwd2_hp(const Geom &g, const HpDims &hd, const Tensors &t, const void *xt,
                           const void *wpb, const int4 *btab, void *gcol, float *part, int *cnt,
                           hipStream_t stream) {
   using Raw = typename T::Raw;
   const size_t lds = hp_bwd2_lds_bytes(g, hd);
   if (lds > 64 * 1024) {
-    hipError_t ea = hipFuncSetAttribute((const void *)hp_bwd2_kernel<ND, MOD, T, WAVES, NKS, NS>,
+    hipError_t ea = hipFuncSetAttribute((const void *)hp_bwd2_kernel<ND, MOD, T, WAVES, NKS, NS, SE>,
                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (ea != hipSuccess) { set_error("hipFuncSetAttribute: %s", hipGetErrorString(ea)); return MDCONV_ELAUNCH; }
   }
-  hp_debug_plan("hp_bwd2", hp_bwd2_kernel<ND, MOD, T, WAVES, NKS, NS>, 64 * (WAVES + NS), lds, (long)hd.ranges * g.K);
-  hipLaunchKernelGGL((hp_bwd2_kernel<ND, MOD, T, WAVES, NKS, NS>), dim3(hd.ranges, g.K), dim3(64 * (WAVES + NS)), lds,
+  hp_debug_plan("hp_bwd2", hp_bwd2_kernel<ND, MOD, T, WAVES, NKS, NS, SE>, 64 * (WAVES + NS), lds, (long)hd.ranges * g.K);
+  hipLaunchKernelGGL((hp_bwd2_kernel<ND, MOD, T, WAVES, NKS, NS, SE>), dim3(hd.ranges, g.K), dim3(64 * (WAVES + NS)), lds,
                      stream, g, hd, (const Raw *)xt, (const U4 *)wpb, btab, (const Raw *)t.grad_output,
-                     (const Raw *)t.offset, (const Raw *)t.mask, (Raw *)gcol, (Raw *)t.grad_offset,
-                     (Raw *)t.grad_mask, part, cnt);
+                     (const SE *)t.offset, (const SE *)t.mask, (Raw *)gcol, (SE *)t.grad_offset,
+                     (SE *)t.grad_mask, part, cnt);
   return check_launch("hp_bwd2");
 }
 
-template <int ND, bool MOD, typename T>
+template <int ND, bool MOD, typename T, typename SE>
 static int dispatch_bwd2_hp(const Geom &g, const HpDims &hd, const Tensors &t, const void *xt,
                             const void *wpb, const int4 *btab, void *gcol, float *part, int *cnt,
                             hipStream_t stream) {
 #define HP_BWD(W, N)                                                                           \
   do {                                                                                         \
-    if (g.DG > 2) return launch_bwd2_hp<ND, MOD, T, W, N, 2>(g, hd, t, xt, wpb, btab, gcol, part, cnt, stream); \
-    return launch_bwd2_hp<ND, MOD, T, W, N, 1>(g, hd, t, xt, wpb, btab, gcol, part, cnt, stream);              \
+    if (g.DG > 2) return launch_bwd2_hp<ND, MOD, T, W, N, 2, SE>(g, hd, t, xt, wpb, btab, gcol, part, cnt, stream); \
+    return launch_bwd2_hp<ND, MOD, T, W, N, 1, SE>(g, hd, t, xt, wpb, btab, gcol, part, cnt, stream);              \
   } while (0)
 #define HP_BWD_W(W)                                                                            \
   switch (hd.nks) {                                                                            \
@@ -517,20 +519,31 @@ static int dispatch_bwd2_hp(const Geom &g, const HpDims &hd, const Tensors &t, c
 #undef HP_BWD
 }
 
+#define HP_DISPATCH(T, SE)                                                                         \
+  do {                                                                                            \
+    if (g.nd == 2)                                                                                \
+      return g.modulated ? dispatch_bwd2_hp<2, true, T, SE>(g, hd, t, xt, wpb, btab, gcol, part, cnt, stream)  \
+                         : dispatch_bwd2_hp<2, false, T, SE>(g, hd, t, xt, wpb, btab, gcol, part, cnt, stream); \
+    return g.modulated ? dispatch_bwd2_hp<3, true, T, SE>(g, hd, t, xt, wpb, btab, gcol, part, cnt, stream)    \
+                       : dispatch_bwd2_hp<3, false, T, SE>(g, hd, t, xt, wpb, btab, gcol, part, cnt, stream);   \
+  } while (0)
+#ifndef HP_SAMPLING_F32_UNIT
 int hp_backward2_launch(const Geom &g, const HpDims &hd, int dtype, const Tensors &t, const void *xt,
                         const void *wpb, const int4 *btab, void *gcol, float *part, int *cnt,
                         hipStream_t stream) {
-#define HP_DISPATCH(T)                                                                            \
-  do {                                                                                            \
-    if (g.nd == 2)                                                                                \
-      return g.modulated ? dispatch_bwd2_hp<2, true, T>(g, hd, t, xt, wpb, btab, gcol, part, cnt, stream)  \
-                         : dispatch_bwd2_hp<2, false, T>(g, hd, t, xt, wpb, btab, gcol, part, cnt, stream); \
-    return g.modulated ? dispatch_bwd2_hp<3, true, T>(g, hd, t, xt, wpb, btab, gcol, part, cnt, stream)    \
-                       : dispatch_bwd2_hp<3, false, T>(g, hd, t, xt, wpb, btab, gcol, part, cnt, stream);   \
-  } while (0)
-  if (dtype == MDCONV_F16) HP_DISPATCH(F16);
-  HP_DISPATCH(BF16);
-#undef HP_DISPATCH
+  if (t.samp32) return hp_backward2_launch_s32(g, hd, dtype, t, xt, wpb, btab, gcol, part, cnt, stream);
+  if (dtype == MDCONV_F16) HP_DISPATCH(F16, F16::Raw);
+  HP_DISPATCH(BF16, BF16::Raw);
 }
+#else
+// fp32 offsets / masks (MDCONV_SAMPLING_F32): the same kernels with SE = float, compiled in their own unit (hp_bwd2_s32.hip)
+int hp_backward2_launch_s32(const Geom &g, const HpDims &hd, int dtype, const Tensors &t, const void *xt,
+                            const void *wpb, const int4 *btab, void *gcol, float *part, int *cnt,
+                            hipStream_t stream) {
+  if (dtype == MDCONV_F16) HP_DISPATCH(F16, float);
+  HP_DISPATCH(BF16, float);
+}
+#endif
+#undef HP_DISPATCH
 
 }  // namespace mdconv

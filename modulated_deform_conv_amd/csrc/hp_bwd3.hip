@@ -10,6 +10,9 @@ int hp_bwd3_f16_2d(const Geom &, const HpDims &, const Tensors &, const void *, 
 int hp_bwd3_f16_3d(const Geom &, const HpDims &, const Tensors &, const void *, const void *, void *, void *, int *, hipStream_t);
 int hp_bwd3_bf16_2d(const Geom &, const HpDims &, const Tensors &, const void *, const void *, void *, void *, int *, hipStream_t);
 int hp_bwd3_bf16_3d(const Geom &, const HpDims &, const Tensors &, const void *, const void *, void *, void *, int *, hipStream_t);
+// fp32 offsets / masks (MDCONV_SAMPLING_F32): hp_bwd3_s32_{f16,bf16}.hip, both ranks
+int hp_bwd3_s32_f16(const Geom &, const HpDims &, const Tensors &, const void *, const void *, void *, void *, int *, hipStream_t);
+int hp_bwd3_s32_bf16(const Geom &, const HpDims &, const Tensors &, const void *, const void *, void *, void *, int *, hipStream_t);
 
 size_t hp_bwd3_lds_bytes(const Geom &g, const HpDims &hd) {
   const size_t region = (size_t)32 * (hd.Cp + 8) * 2 > (size_t)kB3ChunkRows * kPP * 2 ? (size_t)32 * (hd.Cp + 8) * 2
@@ -34,6 +37,9 @@ bool hp_bwd3_supported(const Geom &g, const HpDims &hd) {
 
 int hp_backward3_launch(const Geom &g, const HpDims &hd, int dtype, const Tensors &t, const void *xt,
                         const void *wpb, void *gcol, void *colbuf, int *cnt, hipStream_t stream) {
+  if (t.samp32)
+    return dtype == MDCONV_F16 ? hp_bwd3_s32_f16(g, hd, t, xt, wpb, gcol, colbuf, cnt, stream)
+                               : hp_bwd3_s32_bf16(g, hd, t, xt, wpb, gcol, colbuf, cnt, stream);
   if (dtype == MDCONV_F16)
     return g.nd == 2 ? hp_bwd3_f16_2d(g, hd, t, xt, wpb, gcol, colbuf, cnt, stream)
                      : hp_bwd3_f16_3d(g, hd, t, xt, wpb, gcol, colbuf, cnt, stream);

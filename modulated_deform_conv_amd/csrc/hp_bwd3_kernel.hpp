@@ -60,13 +60,14 @@ constexpr int kB3SlabMaxKB = 48;   // largest W^T slab of one tap that is staged
 constexpr int kB3WRing2 = 8, kB3WRing3 = 4;   // kWG instances: A fragments in flight per wave (2-D, 3-D)
 
 // LPP: lanes per pixel of a deformable group (C_dg / 8); CBT: 32-channel blocks of ALL channels (Cp / 32)
-template <int ND, bool MOD, typename T, int LPP, int NKS, int CBT>
+// SE: element type of offset / mask / grad_offset / grad_mask (T::Raw, or float for MDCONV_SAMPLING_F32)
+template <int ND, bool MOD, typename T, int LPP, int NKS, int CBT, typename SE = typename T::Raw>
 __global__ __launch_bounds__(256, 2) void hp_bwd3_kernel(
     Geom g, HpDims hd, const typename T::Raw *__restrict__ xt, const U4 *__restrict__ wpb,
-    const typename T::Raw *__restrict__ gout, const typename T::Raw *__restrict__ offset,
-    const typename T::Raw *__restrict__ mask, typename T::Raw *__restrict__ gcol,
-    typename T::Raw *__restrict__ colbuf, typename T::Raw *__restrict__ grad_offset,
-    typename T::Raw *__restrict__ grad_mask, int *__restrict__ cnt) {
+    const typename T::Raw *__restrict__ gout, const SE *__restrict__ offset,
+    const SE *__restrict__ mask, typename T::Raw *__restrict__ gcol,
+    typename T::Raw *__restrict__ colbuf, SE *__restrict__ grad_offset,
+    SE *__restrict__ grad_mask, int *__restrict__ cnt) {
   using Raw = typename T::Raw;
   constexpr int NC = 1 << ND;
   constexpr int SW = 2 * NC + 4;        // state dwords per (group, pixel): voff[NC] (later S[NC]), w*mask[NC], grad_col row, image, pad
@@ -164,9 +165,9 @@ __global__ __launch_bounds__(256, 2) void hp_bwd3_kernel(
   // (raw 16-bit values until build(): a conversion inside fetch() would be a use of the load where it is issued, hp_fwd2.hip)
   // One group: lanes 0-31 / 32-63 handle taps t / t + 1 of their pixel (round r = 0 only).  Several groups: both
   // half-waves handle the SAME tap, groups 2r / 2r + 1 in round r.
-  Raw dlr[NR][ND], mlr[NR];
-  const Raw *off_px = offset + (int64_t)b * NDG * (ND * g.K) * g.S_o + pix;
-  const Raw *msk_px = MOD ? mask + (int64_t)b * NDG * g.K * g.S_o + pix : nullptr;
+  SE dlr[NR][ND], mlr[NR];
+  const SE *off_px = offset + (int64_t)b * NDG * (ND * g.K) * g.S_o + pix;
+  const SE *msk_px = MOD ? mask + (int64_t)b * NDG * g.K * g.S_o + pix : nullptr;
   // the tap THIS lane builds next, its coordinates kept incrementally (one group: lanes 32-63 one tap ahead)
   int b_tap = NDG == 1 ? kh : 0, b_tcd[ND];
   {
@@ -214,8 +215,8 @@ __global__ __launch_bounds__(256, 2) void hp_bwd3_kernel(
   auto build_state = [&](int r, int tap, int dg, const int *tcd, bool mine, bool hold) {
     float dl[ND], ml = 1.f;
 #pragma unroll
-    for (int a = 0; a < ND; ++a) dl[a] = T::ldf(&dlr[r][a]);
-    if (MOD) ml = T::ldf(&mlr[r]);
+    for (int a = 0; a < ND; ++a) dl[a] = samp_ld(&dlr[r][a]);
+    if (MOD) ml = samp_ld(&mlr[r]);
     TapCoef<ND, float> tc;
     make_tap<ND, float>(g, oc, tcd, dl, true, tc);
     HpCorners<ND> hc;
@@ -278,15 +279,15 @@ __global__ __launch_bounds__(256, 2) void hp_bwd3_kernel(
       }
     }
     const int64_t ch = (int64_t)dg * g.K + tap;
-    Raw *go = grad_offset + (int64_t)b * NDG * (ND * g.K) * g.S_o + pix + ch * ND * g.S_o;
+    SE *go = grad_offset + (int64_t)b * NDG * (ND * g.K) * g.S_o + pix + ch * ND * g.S_o;
 #pragma unroll
     for (int a = 0; a < ND; ++a) {
-      Raw *d = go + (int64_t)a * g.S_o;
-      T::stf(d, goff[a] * fac[r].mg + (g.acc_data ? T::ldf(d) : 0.f));
+      SE *d = go + (int64_t)a * g.S_o;
+      samp_st(d, goff[a] * fac[r].mg + (g.acc_data ? samp_ld(d) : 0.f));
     }
     if (MOD) {
-      Raw *d = grad_mask + (int64_t)b * NDG * g.K * g.S_o + pix + ch * g.S_o;
-      T::stf(d, gm + (g.acc_data ? T::ldf(d) : 0.f));
+      SE *d = grad_mask + (int64_t)b * NDG * g.K * g.S_o + pix + ch * g.S_o;
+      samp_st(d, gm + (g.acc_data ? samp_ld(d) : 0.f));
     }
   };
   auto finish = [&](int tap) {
@@ -466,28 +467,28 @@ __global__ __launch_bounds__(256, 2) void hp_bwd3_kernel(
 
 size_t hp_bwd3_lds_bytes(const Geom &g, const HpDims &hd);   // hp_bwd3.hip
 
-template <int ND, bool MOD, typename T, int LPP, int NKS, int CBT>
+template <int ND, bool MOD, typename T, int LPP, int NKS, int CBT, typename SE>
 int launch_bwd3(const Geom &g, const HpDims &hd, const Tensors &t, const void *xt, const void *wpb,
                 void *gcol, void *colbuf, int *cnt, hipStream_t stream) {
   using Raw = typename T::Raw;
   const size_t lds = hp_bwd3_lds_bytes(g, hd);
   if (lds > 64 * 1024) {
-    hipError_t ea = hipFuncSetAttribute((const void *)hp_bwd3_kernel<ND, MOD, T, LPP, NKS, CBT>,
+    hipError_t ea = hipFuncSetAttribute((const void *)hp_bwd3_kernel<ND, MOD, T, LPP, NKS, CBT, SE>,
                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (ea != hipSuccess) { set_error("hipFuncSetAttribute: %s", hipGetErrorString(ea)); return MDCONV_ELAUNCH; }
   }
-  hp_debug_plan("hp_bwd3", hp_bwd3_kernel<ND, MOD, T, LPP, NKS, CBT>, 256, lds, (g.N + 127) / 128);
-  hipLaunchKernelGGL((hp_bwd3_kernel<ND, MOD, T, LPP, NKS, CBT>), dim3((g.N + 127) / 128), dim3(256), lds, stream, g, hd,
-                     (const Raw *)xt, (const U4 *)wpb, (const Raw *)t.grad_output, (const Raw *)t.offset,
-                     (const Raw *)t.mask, (Raw *)gcol, (Raw *)colbuf, (Raw *)t.grad_offset, (Raw *)t.grad_mask, cnt);
+  hp_debug_plan("hp_bwd3", hp_bwd3_kernel<ND, MOD, T, LPP, NKS, CBT, SE>, 256, lds, (g.N + 127) / 128);
+  hipLaunchKernelGGL((hp_bwd3_kernel<ND, MOD, T, LPP, NKS, CBT, SE>), dim3((g.N + 127) / 128), dim3(256), lds, stream, g, hd,
+                     (const Raw *)xt, (const U4 *)wpb, (const Raw *)t.grad_output, (const SE *)t.offset,
+                     (const SE *)t.mask, (Raw *)gcol, (Raw *)colbuf, (SE *)t.grad_offset, (SE *)t.grad_mask, cnt);
   return check_launch("hp_bwd3");
 }
 
 // (Cp, deformable groups) -> (LPP, CBT): LPP = C_dg / 8 lanes per pixel of a group, CBT = Cp / 32
-template <int ND, bool MOD, typename T>
+template <int ND, bool MOD, typename T, typename SE = typename T::Raw>
 int dispatch_bwd3(const Geom &g, const HpDims &hd, const Tensors &t, const void *xt, const void *wpb,
                   void *gcol, void *colbuf, int *cnt, hipStream_t stream) {
-#define HP_B3(L, N, C) return launch_bwd3<ND, MOD, T, L, N, C>(g, hd, t, xt, wpb, gcol, colbuf, cnt, stream)
+#define HP_B3(L, N, C) return launch_bwd3<ND, MOD, T, L, N, C, SE>(g, hd, t, xt, wpb, gcol, colbuf, cnt, stream)
 #define HP_B3_L(L, C)                                                              \
   switch (hd.nks) {                                                                \
     case 2: HP_B3(L, 2, C);                                                        \

@@ -46,10 +46,13 @@ __global__ __launch_bounds__(256) void hp_csr_scan_kernel(int S, const int *__re
 // that `test_bf16_two_pass_gather_rounds_once_like_the_one_pass_gather` (and its 2-D sibling) forbid.
 template <int ND, typename T> struct ShortEntry { static constexpr bool value = false; };
 template <> struct ShortEntry<2, F16> { static constexpr bool value = true; };
-template <int ND, bool MOD, typename T>
+// SE: element type of offset / mask (T::Raw, or float for MDCONV_SAMPLING_F32 -- the short 2-D fp16 entries still carry the
+// weight x mask products as fp16 pairs: the sample's position is exact, its scatter weights have the precision of the
+// fp16 grad_col rows they multiply, as in an all-fp16 call)
+template <int ND, bool MOD, typename T, typename SE = typename T::Raw>
 __global__ __launch_bounds__(256) void hp_csr_fill_kernel(Geom g, int S_e,
-                                                          const typename T::Raw *__restrict__ offset,
-                                                          const typename T::Raw *__restrict__ mask,
+                                                          const SE *__restrict__ offset,
+                                                          const SE *__restrict__ mask,
                                                           int *__restrict__ cursor,
                                                           const int *__restrict__ rowptr,
                                                           int4 *__restrict__ entries) {
@@ -64,10 +67,10 @@ __global__ __launch_bounds__(256) void hp_csr_fill_kernel(Geom g, int S_e,
     float delta[ND];
     const int64_t ob = ((int64_t)seg * (ND * g.K) + ND * tap) * g.S_o + pix;
 #pragma unroll
-    for (int a = 0; a < ND; ++a) delta[a] = T::ldf(offset + ob + (int64_t)a * g.S_o);
+    for (int a = 0; a < ND; ++a) delta[a] = samp_ld(offset + ob + (int64_t)a * g.S_o);
     TapCoef<ND, float> tc;
     make_tap<ND, float>(g, oc, tcd, delta, true, tc);
-    const float m = MOD ? T::ldf(mask + ((int64_t)seg * g.K + tap) * g.S_o + pix) : 1.f;
+    const float m = MOD ? samp_ld(mask + ((int64_t)seg * g.K + tap) * g.S_o + pix) : 1.f;
     SampleAnchor<ND> sa;
     sample_anchor<ND>(g, tc, m, sa);
     if (sa.on) {
@@ -664,16 +667,19 @@ int hp_csr_build(const Geom &g, int dtype, const Tensors &t, int *cnt, int *rowp
   hipLaunchKernelGGL(hp_csr_scan_kernel, dim3((S_e + kScanChunk - 1) / kScanChunk, g.B * g.DG), dim3(256), 0, stream,
                      S_e, cnt, rowptr);
   if ((rc = check_launch("hp_csr_scan"))) return rc;
-#define HP_CSR(ND, MOD, T)                                                                        \
-  hipLaunchKernelGGL((hp_csr_fill_kernel<ND, MOD, T>), dim3(grid_for(samples)), dim3(256), 0, stream, g, S_e, \
-                     (const typename T::Raw *)t.offset, (const typename T::Raw *)t.mask, cnt, rowptr,    \
-                     (int4 *)entries)
-#define HP_CSR_T(T)                                                                               \
+#define HP_CSR(ND, MOD, T, SE)                                                                     \
+  hipLaunchKernelGGL((hp_csr_fill_kernel<ND, MOD, T, SE>), dim3(grid_for(samples)), dim3(256), 0, stream, g, S_e, \
+                     (const SE *)t.offset, (const SE *)t.mask, cnt, rowptr, (int4 *)entries)
+#define HP_CSR_T(T, SE)                                                                            \
   do {                                                                                            \
-    if (g.nd == 2) { if (g.modulated) HP_CSR(2, true, T); else HP_CSR(2, false, T); }             \
-    else { if (g.modulated) HP_CSR(3, true, T); else HP_CSR(3, false, T); }                       \
+    if (g.nd == 2) { if (g.modulated) HP_CSR(2, true, T, SE); else HP_CSR(2, false, T, SE); }       \
+    else { if (g.modulated) HP_CSR(3, true, T, SE); else HP_CSR(3, false, T, SE); }                 \
   } while (0)
-  if (dtype == MDCONV_F16) HP_CSR_T(F16); else HP_CSR_T(BF16);
+  if (t.samp32) {
+    if (dtype == MDCONV_F16) HP_CSR_T(F16, float); else HP_CSR_T(BF16, float);
+  } else {
+    if (dtype == MDCONV_F16) HP_CSR_T(F16, F16::Raw); else HP_CSR_T(BF16, BF16::Raw);
+  }
 #undef HP_CSR_T
 #undef HP_CSR
   return check_launch("hp_csr_fill");

@@ -109,6 +109,15 @@ struct BF16 {
   }
 };
 
+// Sampling elements -- offset, mask, grad_offset, grad_mask: the tensors' own 16-bit type (the kernels' default
+// template argument SE = T::Raw) or fp32 (MDCONV_SAMPLING_F32: loaded as dwords straight into the fp32 sampling state)
+__device__ __forceinline__ float samp_ld(const _Float16 *p) { return (float)*p; }
+__device__ __forceinline__ float samp_ld(const __bf16 *p) { return (float)*p; }
+__device__ __forceinline__ float samp_ld(const float *p) { return *p; }
+__device__ __forceinline__ void samp_st(_Float16 *p, float v) { *p = (_Float16)v; }
+__device__ __forceinline__ void samp_st(__bf16 *p, float v) { *p = (__bf16)v; }
+__device__ __forceinline__ void samp_st(float *p, float v) { *p = v; }
+
 __device__ __forceinline__ U4 buf_load4u(rsrc_t r, int voff, int soff) {
   return __builtin_bit_cast(U4, __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, 0));
 }

@@ -25,11 +25,11 @@ namespace {
 
 constexpr int kStage = 4;   // 16-channel chunks per LDS stage of the weights
 
-template <int ND, bool MOD, typename T, int MB>
+template <int ND, bool MOD, typename T, int MB, typename SE = typename T::Raw>
 __global__ __launch_bounds__(256, 2) void hp_fwd_kernel(
     Geom g, HpDims hd, const typename T::Raw *__restrict__ xt, const U4 *__restrict__ wpf,
-    const typename T::Raw *__restrict__ bias, const typename T::Raw *__restrict__ offset,
-    const typename T::Raw *__restrict__ mask, typename T::Raw *__restrict__ output,
+    const typename T::Raw *__restrict__ bias, const SE *__restrict__ offset,
+    const SE *__restrict__ mask, typename T::Raw *__restrict__ output,
     const int2 *__restrict__ ctab) {
   constexpr int NC = 1 << ND;
   __shared__ U4 As[2][kStage][MB][64];
@@ -68,7 +68,7 @@ __global__ __launch_bounds__(256, 2) void hp_fwd_kernel(
   int voff[NC];
   float wgt[NC];
   int st_tap = -1, st_dg = -1;
-  typename T::Raw dlr[ND], mlr;   // prefetched offsets / mask of (pf_tap, pf_dg), raw until used
+  SE dlr[ND], mlr;   // prefetched offsets / mask of (pf_tap, pf_dg), raw until used
   int pf_tap = -1, pf_dg = -1;
   auto fetch = [&](int tap, int dg) {
     const int64_t seg = (int64_t)b * g.DG + dg;
@@ -85,8 +85,8 @@ __global__ __launch_bounds__(256, 2) void hp_fwd_kernel(
     tap_coords<ND>(g, tap, tcd);
     float dl[ND];
 #pragma unroll
-    for (int a = 0; a < ND; ++a) dl[a] = T::ldf(&dlr[a]);
-    const float ml = MOD ? T::ldf(&mlr) : 1.f;
+    for (int a = 0; a < ND; ++a) dl[a] = samp_ld(&dlr[a]);
+    const float ml = MOD ? samp_ld(&mlr) : 1.f;
     TapCoef<ND, float> tc;
     make_tap<ND, float>(g, oc, tcd, dl, false, tc);
     HpCorners<ND> hc;
@@ -225,15 +225,15 @@ __global__ __launch_bounds__(256, 2) void hp_fwd_kernel(
 
 }  // namespace
 
-template <int ND, bool MOD, typename T>
+template <int ND, bool MOD, typename T, typename SE>
 static int launch_fwd_hp(const Geom &g, const HpDims &hd, const Tensors &t, const void *xt,
                          const void *wpf, const int2 *ctab, hipStream_t stream) {
   using Raw = typename T::Raw;
   const dim3 grid((g.N + 127) / 128, hd.oranges);
 #define HP_FWD(MBV)                                                                              \
-  hipLaunchKernelGGL((hp_fwd_kernel<ND, MOD, T, MBV>), grid, dim3(256), 0, stream, g, hd,          \
-                     (const Raw *)xt, (const U4 *)wpf, (const Raw *)t.bias, (const Raw *)t.offset, \
-                     (const Raw *)t.mask, (Raw *)t.output, ctab)
+  hipLaunchKernelGGL((hp_fwd_kernel<ND, MOD, T, MBV, SE>), grid, dim3(256), 0, stream, g, hd,       \
+                     (const Raw *)xt, (const U4 *)wpf, (const Raw *)t.bias, (const SE *)t.offset,   \
+                     (const SE *)t.mask, (Raw *)t.output, ctab)
   switch (hd.MB) {
     case 1: HP_FWD(1); break;
     case 2: HP_FWD(2); break;
@@ -245,16 +245,20 @@ static int launch_fwd_hp(const Geom &g, const HpDims &hd, const Tensors &t, cons
 
 int hp_forward_launch(const Geom &g, const HpDims &hd, int dtype, const Tensors &t, const void *xt,
                       const void *wpf, const int2 *ctab, hipStream_t stream) {
-#define HP_DISPATCH(T)                                                                       \
+#define HP_DISPATCH(T, SE)                                                                    \
   do {                                                                                       \
     if (g.nd == 2)                                                                           \
-      return g.modulated ? launch_fwd_hp<2, true, T>(g, hd, t, xt, wpf, ctab, stream)         \
-                         : launch_fwd_hp<2, false, T>(g, hd, t, xt, wpf, ctab, stream);       \
-    return g.modulated ? launch_fwd_hp<3, true, T>(g, hd, t, xt, wpf, ctab, stream)           \
-                       : launch_fwd_hp<3, false, T>(g, hd, t, xt, wpf, ctab, stream);         \
+      return g.modulated ? launch_fwd_hp<2, true, T, SE>(g, hd, t, xt, wpf, ctab, stream)      \
+                         : launch_fwd_hp<2, false, T, SE>(g, hd, t, xt, wpf, ctab, stream);    \
+    return g.modulated ? launch_fwd_hp<3, true, T, SE>(g, hd, t, xt, wpf, ctab, stream)        \
+                       : launch_fwd_hp<3, false, T, SE>(g, hd, t, xt, wpf, ctab, stream);      \
   } while (0)
-  if (dtype == MDCONV_F16) HP_DISPATCH(F16);
-  HP_DISPATCH(BF16);
+  if (t.samp32) {
+    if (dtype == MDCONV_F16) HP_DISPATCH(F16, float);
+    HP_DISPATCH(BF16, float);
+  }
+  if (dtype == MDCONV_F16) HP_DISPATCH(F16, F16::Raw);
+  HP_DISPATCH(BF16, BF16::Raw);
 #undef HP_DISPATCH
 }
 

@@ -30,11 +30,11 @@ constexpr int kStSlots = 3;
 constexpr int kBtP = 72;     // LDS pitch (16-bit elements) of a pixel row of the B tile: 64 + 8
 
 // GRP = false: one conv group -- every chunk feeds every output-channel block, no table lookups.
-template <int ND, bool MOD, typename T, int MB, bool GRP>
+template <int ND, bool MOD, typename T, int MB, bool GRP, typename SE = typename T::Raw>
 __global__ __launch_bounds__(256, 2) void hp_fwd2_kernel(
     Geom g, HpDims hd, const typename T::Raw *__restrict__ xt, const U4 *__restrict__ wpf,
-    const typename T::Raw *__restrict__ bias, const typename T::Raw *__restrict__ offset,
-    const typename T::Raw *__restrict__ mask, typename T::Raw *__restrict__ output,
+    const typename T::Raw *__restrict__ bias, const SE *__restrict__ offset,
+    const SE *__restrict__ mask, typename T::Raw *__restrict__ output,
     const int2 *__restrict__ ctab) {
   using Raw = typename T::Raw;
   constexpr int NC = 1 << ND;
@@ -99,9 +99,9 @@ __global__ __launch_bounds__(256, 2) void hp_fwd2_kernel(
   // The RAW 16-bit values are kept until build(): converting them to float inside fetch() is a use of the load
   // right where it is issued -- a full memory round trip per sampling state, exposed (with the conversion in
   // fetch() "state build + fetch" was 22 % / 25 % of the kernel's wave-cycles at cfg5 / cfg3, tools/b1_timing.py).
-  Raw dlr[ND], mlr;
-  const Raw *off_px = offset + (int64_t)b * g.DG * (ND * g.K) * g.S_o + pix;
-  const Raw *msk_px = MOD ? mask + (int64_t)b * g.DG * g.K * g.S_o + pix : nullptr;
+  SE dlr[ND], mlr;
+  const SE *off_px = offset + (int64_t)b * g.DG * (ND * g.K) * g.S_o + pix;
+  const SE *msk_px = MOD ? mask + (int64_t)b * g.DG * g.K * g.S_o + pix : nullptr;
   const int px_base = b * g.S_i;
   auto store_state = [&](const TapCoef<ND, float> &tc, float ml, int slot) {
     HpCorners<ND> hc;
@@ -142,7 +142,7 @@ __global__ __launch_bounds__(256, 2) void hp_fwd2_kernel(
   auto fetch_pair = [&]() {   // offsets / mask of this lane's next state (clamped past the last one: built, never read)
     const int tp = min(b_tap, g.K - 1);
     const int idx = (dg0 + b_run) * g.K + tp;
-    const Raw *op = off_px + (int64_t)idx * (ND * g.S_o);
+    const SE *op = off_px + (int64_t)idx * (ND * g.S_o);
 #pragma unroll
     for (int a = 0; a < ND; ++a) dlr[a] = op[(int64_t)a * g.S_o];
     if (MOD) mlr = msk_px[(int64_t)idx * g.S_o];
@@ -150,8 +150,8 @@ __global__ __launch_bounds__(256, 2) void hp_fwd2_kernel(
   auto build_pair = [&](int sig0) {   // states sig0 (lanes 0-31) and sig0 + 1 (lanes 32-63) from the fetched values
     float dl[ND], ml = 1.f;
 #pragma unroll
-    for (int a = 0; a < ND; ++a) dl[a] = T::ldf(&dlr[a]);
-    if (MOD) ml = T::ldf(&mlr);
+    for (int a = 0; a < ND; ++a) dl[a] = samp_ld(&dlr[a]);
+    if (MOD) ml = samp_ld(&mlr);
     TapCoef<ND, float> tc;
     make_tap<ND, float>(g, oc, b_tcd, dl, false, tc);
     const int sg = sig0 + kh;
@@ -332,7 +332,7 @@ size_t hp_fwd2_lds_bytes(const Geom &g, const HpDims &hd) {
   return (size_t)2 * kStage * (g.G == 1 ? hd.MB : hd.fwd_nmax) * 1024 + (size_t)4 * 32 * kBtP * 2 + (size_t)4 * kStSlots * 32 * 2 * nc * 4 + win;
 }
 
-template <int ND, bool MOD, typename T>
+template <int ND, bool MOD, typename T, typename SE>
 static int launch_fwd2_hp(const Geom &g, const HpDims &hd, const Tensors &t, const void *xt,
                           const void *wpf, const int2 *ctab, hipStream_t stream) {
   using Raw = typename T::Raw;
@@ -345,14 +345,14 @@ static int launch_fwd2_hp(const Geom &g, const HpDims &hd, const Tensors &t, con
 #define HP_FWD2_(MBV, GRPV)                                                                      \
   do {                                                                                           \
     if (lds > 64 * 1024) {                                                                       \
-      hipError_t ea = hipFuncSetAttribute((const void *)hp_fwd2_kernel<ND, MOD, T, MBV, GRPV>,    \
+      hipError_t ea = hipFuncSetAttribute((const void *)hp_fwd2_kernel<ND, MOD, T, MBV, GRPV, SE>,    \
                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
       if (ea != hipSuccess) { set_error("hipFuncSetAttribute: %s", hipGetErrorString(ea)); return MDCONV_ELAUNCH; } \
     }                                                                                            \
-    hp_debug_plan("hp_fwd2", hp_fwd2_kernel<ND, MOD, T, MBV, GRPV>, 256, lds, (long)grid.x * grid.y);   \
-    hipLaunchKernelGGL((hp_fwd2_kernel<ND, MOD, T, MBV, GRPV>), grid, dim3(256), lds, stream, g, hd, \
-                       (const Raw *)xt, (const U4 *)wpf, (const Raw *)t.bias, (const Raw *)t.offset, \
-                       (const Raw *)t.mask, (Raw *)t.output, ctab);                              \
+    hp_debug_plan("hp_fwd2", hp_fwd2_kernel<ND, MOD, T, MBV, GRPV, SE>, 256, lds, (long)grid.x * grid.y);   \
+    hipLaunchKernelGGL((hp_fwd2_kernel<ND, MOD, T, MBV, GRPV, SE>), grid, dim3(256), lds, stream, g, hd, \
+                       (const Raw *)xt, (const U4 *)wpf, (const Raw *)t.bias, (const SE *)t.offset, \
+                       (const SE *)t.mask, (Raw *)t.output, ctab);                              \
   } while (0)
   switch (hd.MB) {
     case 1: HP_FWD2(1); break;
@@ -366,16 +366,20 @@ static int launch_fwd2_hp(const Geom &g, const HpDims &hd, const Tensors &t, con
 
 int hp_forward2_launch(const Geom &g, const HpDims &hd, int dtype, const Tensors &t, const void *xt,
                        const void *wpf, const int2 *ctab, hipStream_t stream) {
-#define HP_DISPATCH(T)                                                                       \
+#define HP_DISPATCH(T, SE)                                                                    \
   do {                                                                                       \
     if (g.nd == 2)                                                                           \
-      return g.modulated ? launch_fwd2_hp<2, true, T>(g, hd, t, xt, wpf, ctab, stream)        \
-                         : launch_fwd2_hp<2, false, T>(g, hd, t, xt, wpf, ctab, stream);      \
-    return g.modulated ? launch_fwd2_hp<3, true, T>(g, hd, t, xt, wpf, ctab, stream)          \
-                       : launch_fwd2_hp<3, false, T>(g, hd, t, xt, wpf, ctab, stream);        \
+      return g.modulated ? launch_fwd2_hp<2, true, T, SE>(g, hd, t, xt, wpf, ctab, stream)     \
+                         : launch_fwd2_hp<2, false, T, SE>(g, hd, t, xt, wpf, ctab, stream);   \
+    return g.modulated ? launch_fwd2_hp<3, true, T, SE>(g, hd, t, xt, wpf, ctab, stream)       \
+                       : launch_fwd2_hp<3, false, T, SE>(g, hd, t, xt, wpf, ctab, stream);     \
   } while (0)
-  if (dtype == MDCONV_F16) HP_DISPATCH(F16);
-  HP_DISPATCH(BF16);
+  if (t.samp32) {
+    if (dtype == MDCONV_F16) HP_DISPATCH(F16, float);
+    HP_DISPATCH(BF16, float);
+  }
+  if (dtype == MDCONV_F16) HP_DISPATCH(F16, F16::Raw);
+  HP_DISPATCH(BF16, BF16::Raw);
 #undef HP_DISPATCH
 }
 

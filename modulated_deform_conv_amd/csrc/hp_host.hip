@@ -350,6 +350,7 @@ int hp_forward(const Geom &gcall, int dtype, const Tensors &t, void *ws, hipStre
   const FwdLayout L = fwd_layout(g0, hd0);
   char *base = (char *)ws;
   const int nc_off = g.DG * g.nd * g.K, nc_m = g.DG * g.K;
+  const size_t es_s = samp_bytes(dtype, t);   // offset / mask element: 2, or 4 with fp32 sampling
   int rc;
   if ((rc = hp_pack_fwd_weights(g0, hd0, dtype, t.weight, base + L.off_w, (int2 *)(base + L.off_tab), stream)))
     return rc;
@@ -359,8 +360,8 @@ int hp_forward(const Geom &gcall, int dtype, const Tensors &t, void *ws, hipStre
     const HpDims hd = hp_dims(gc);
     Tensors tc = t;
     tc.input = (const char *)t.input + (size_t)b0 * caller_channels(g) * g.S_i * 2;
-    tc.offset = (const char *)t.offset + (size_t)b0 * nc_off * g.S_o * 2;
-    tc.mask = t.mask ? (const char *)t.mask + (size_t)b0 * nc_m * g.S_o * 2 : nullptr;
+    tc.offset = (const char *)t.offset + (size_t)b0 * nc_off * g.S_o * es_s;
+    tc.mask = t.mask ? (const char *)t.mask + (size_t)b0 * nc_m * g.S_o * es_s : nullptr;
     tc.output = (char *)t.output + (size_t)b0 * g.O * g.S_o * 2;
     const void *xt = base + L.off_xt;
     if (g.in_cl) xt = (const char *)t.input + (size_t)b0 * g.S_i * g.C * 2;   // already channels-last
@@ -391,6 +392,7 @@ int hp_backward(const Geom &gcall, int dtype, const Tensors &t, void *ws, hipStr
   const BwdLayout L = bwd_layout(g0, hd0, dtype);
   char *base = (char *)ws;
   const int nc_off = g.DG * g.nd * g.K, nc_m = g.DG * g.K;
+  const size_t es_s = samp_bytes(dtype, t);   // offset / mask element: 2, or 4 with fp32 sampling
   int rc;
   if ((rc = hp_pack_bwd_weights(g0, hd0, dtype, t.weight, base + L.off_w, (int4 *)(base + L.off_tab), stream)))
     return rc;
@@ -402,12 +404,12 @@ int hp_backward(const Geom &gcall, int dtype, const Tensors &t, void *ws, hipStr
     const HpDims hd = hp_dims(gc);
     Tensors tc = t;
     tc.input = (const char *)t.input + (size_t)b0 * caller_channels(g) * g.S_i * 2;
-    tc.offset = (const char *)t.offset + (size_t)b0 * nc_off * g.S_o * 2;
-    tc.mask = t.mask ? (const char *)t.mask + (size_t)b0 * nc_m * g.S_o * 2 : nullptr;
+    tc.offset = (const char *)t.offset + (size_t)b0 * nc_off * g.S_o * es_s;
+    tc.mask = t.mask ? (const char *)t.mask + (size_t)b0 * nc_m * g.S_o * es_s : nullptr;
     tc.grad_output = (const char *)t.grad_output + (size_t)b0 * g.O * g.S_o * 2;
     tc.grad_input = (char *)t.grad_input + (size_t)b0 * caller_channels(g) * g.S_i * 2;
-    tc.grad_offset = (char *)t.grad_offset + (size_t)b0 * nc_off * g.S_o * 2;
-    tc.grad_mask = t.grad_mask ? (char *)t.grad_mask + (size_t)b0 * nc_m * g.S_o * 2 : nullptr;
+    tc.grad_offset = (char *)t.grad_offset + (size_t)b0 * nc_off * g.S_o * es_s;
+    tc.grad_mask = t.grad_mask ? (char *)t.grad_mask + (size_t)b0 * nc_m * g.S_o * es_s : nullptr;
     int *cnt = (int *)(base + L.off_cnt), *rowptr = (int *)(base + L.off_rowptr);
     const void *xt = base + L.off_xt;
     if (g.in_cl) xt = (const char *)t.input + (size_t)b0 * g.S_i * g.C * 2;   // already channels-last

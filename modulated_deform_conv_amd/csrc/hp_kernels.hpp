@@ -39,12 +39,19 @@ int hp_forward2_launch(const Geom &g, const HpDims &hd, int dtype, const Tensors
 int hp_backward_launch(const Geom &g, const HpDims &hd, int dtype, const Tensors &t, const void *xt,
                        const void *wpb, const int4 *btab, void *gcol, float *part, int *cnt,
                        hipStream_t stream);
+// fp32 offsets / masks (t.samp32): instances in hp_bwd_s32.hip, reached through hp_backward_launch
+int hp_backward_launch_s32(const Geom &g, const HpDims &hd, int dtype, const Tensors &t, const void *xt,
+                           const void *wpb, const int4 *btab, void *gcol, float *part, int *cnt,
+                           hipStream_t stream);
 
 // hp_bwd2.hip: the same kernel with line-wide gathers (thread roles change between phases)
 size_t hp_bwd2_lds_bytes(const Geom &g, const HpDims &hd);
 int hp_backward2_launch(const Geom &g, const HpDims &hd, int dtype, const Tensors &t, const void *xt,
                         const void *wpb, const int4 *btab, void *gcol, float *part, int *cnt,
                         hipStream_t stream);
+int hp_backward2_launch_s32(const Geom &g, const HpDims &hd, int dtype, const Tensors &t, const void *xt,
+                            const void *wpb, const int4 *btab, void *gcol, float *part, int *cnt,
+                            hipStream_t stream);   // hp_bwd2_s32.hip
 
 // hp_bwd3.hip: pixel-stationary GEMM-1 + coordinate gradients + grad_col rows + column rows (GEMM-2 is
 // hp_gemm2.hip); one conv group, 1 / 2 / 4 deformable groups, Cp a power of two

@@ -105,9 +105,13 @@ int fill_geom(const mdconv_desc *d, Geom *g) {
     set_error("ndim must be 2 or 3 (got %d)", ndim);
     return MDCONV_EINVAL;
   }
-  if (d->dtype != MDCONV_F32 && d->dtype != MDCONV_F16 && d->dtype != MDCONV_F64 &&
-      d->dtype != MDCONV_BF16) {
+  const int dt = d->dtype & ~MDCONV_SAMPLING_F32;
+  if (dt != MDCONV_F32 && dt != MDCONV_F16 && dt != MDCONV_F64 && dt != MDCONV_BF16) {
     set_error("unsupported dtype %d", d->dtype);
+    return MDCONV_EINVAL;
+  }
+  if ((d->dtype & MDCONV_SAMPLING_F32) && dt != MDCONV_F16 && dt != MDCONV_BF16) {
+    set_error("MDCONV_SAMPLING_F32 needs fp16 or bf16 tensors, dtype is %s", dt == MDCONV_F32 ? "MDCONV_F32" : "MDCONV_F64");
     return MDCONV_EINVAL;
   }
   if (d->batch <= 0 || d->c_in <= 0 || d->c_out <= 0 || d->groups <= 0 || d->dgroups <= 0) {
@@ -209,6 +213,15 @@ static int require(const void *p, const char *name) {
   return MDCONV_OK;
 }
 
+// element type of the call's tensors (MDCONV_SAMPLING_F32 stripped) and whether offset / mask are fp32
+static int base_dtype(const mdconv_desc *d) { return d->dtype & ~MDCONV_SAMPLING_F32; }
+static int sampling_f32(const mdconv_desc *d) { return (d->dtype & MDCONV_SAMPLING_F32) ? 1 : 0; }
+// fp32 sampling outside the native 16-bit kernels runs the fp32 kernels of the family the 16-bit call would take
+// (samp32_forward / samp32_backward), so the MFMA family needs both dtypes
+static bool mfma_ok_for(const Geom &g, int dt, int s32, bool backward) {
+  return mfma_supported(g, dt, backward) && (!s32 || mfma_supported(g, MDCONV_F32, backward));
+}
+
 static int check_ws(void *ws, size_t have, size_t need) {
   if (need == 0) return MDCONV_OK;
   if (!ws || have < need) {
@@ -242,34 +255,44 @@ static int run_forward(const mdconv_desc *d, int nd, int modulated, Tensors t, v
   if (g.with_bias && (rc = require(t.bias, "bias"))) return rc;
   hipStream_t s = (hipStream_t)stream;
   const int path = md.path;
+  const int dt = base_dtype(d), s32 = sampling_f32(d);
+  t.samp32 = s32;
   g.in_cl = md.input_layout == MDCONV_LAYOUT_CHANNELS_LAST ? 1 : 0;
-  if (g.in_cl && !(path != MDCONV_PATH_DIRECT && hp_supported(g, d->dtype, false) && g.C % 32 == 0)) {
+  if (g.in_cl && !(path != MDCONV_PATH_DIRECT && hp_supported(g, dt, false) && g.C % 32 == 0)) {
     set_error("channels-last input is only supported by the native 16-bit kernels with C_in a multiple of 32");
     return MDCONV_EUNSUPPORTED;
   }
   // 16-bit tensors: native fp16 / bf16 kernels (hp_*.hip) when the shape qualifies (and is not one of the few-tile forwards
   // that the fp32 kernels run faster: hp_forward_preferred)
-  if (path != MDCONV_PATH_DIRECT && hp_supported(g, d->dtype, false) && (g.in_cl || hp_forward_preferred(g, d->dtype))) {
-    if ((rc = check_ws(ws, ws_bytes, hp_workspace_bytes(g, d->dtype, false)))) return rc;
+  if (path != MDCONV_PATH_DIRECT && hp_supported(g, dt, false) && (g.in_cl || hp_forward_preferred(g, dt))) {
+    if ((rc = check_ws(ws, ws_bytes, hp_workspace_bytes(g, dt, false)))) return rc;
     g_last_path = MDCONV_PATH_MFMA;
     g_last_kernels = MDCONV_KERNELS_HP;
-    return hp_forward(g, d->dtype, t, ws, s);
+    return hp_forward(g, dt, t, ws, s);
   }
-  const bool mfma_ok = mfma_supported(g, d->dtype, false);
+  const bool mfma_ok = mfma_ok_for(g, dt, s32, false);
   if (path == MDCONV_PATH_MFMA && !mfma_ok) {
     set_error("MDCONV_PATH=mfma but this shape/dtype is not supported by the MFMA kernels");
     return MDCONV_EUNSUPPORTED;
   }
   if (mfma_ok && path != MDCONV_PATH_DIRECT) {
-    if ((rc = check_ws(ws, ws_bytes, mfma_workspace_bytes(g, d->dtype, false)))) return rc;
     g_last_path = MDCONV_PATH_MFMA;
     g_last_kernels = MDCONV_KERNELS_F32;
-    return mfma_forward(g, d->dtype, t, ws, s);
+    if (s32) {
+      if ((rc = check_ws(ws, ws_bytes, samp32_workspace_bytes(g, false, true)))) return rc;
+      return samp32_forward(g, dt, t, ws, s, true);
+    }
+    if ((rc = check_ws(ws, ws_bytes, mfma_workspace_bytes(g, dt, false)))) return rc;
+    return mfma_forward(g, dt, t, ws, s);
   }
   g_last_path = MDCONV_PATH_DIRECT;
   g_last_kernels = MDCONV_KERNELS_DIRECT;
-  note_direct_fallback(g, d->dtype, false, path);
-  return direct_forward(g, d->dtype, t, s);
+  note_direct_fallback(g, dt, false, path);
+  if (s32) {
+    if ((rc = check_ws(ws, ws_bytes, samp32_workspace_bytes(g, false, false)))) return rc;
+    return samp32_forward(g, dt, t, ws, s, false);
+  }
+  return direct_forward(g, dt, t, s);
 }
 
 static int run_backward(const mdconv_desc *d, int nd, int modulated, Tensors t, void *ws,
@@ -296,39 +319,49 @@ static int run_backward(const mdconv_desc *d, int nd, int modulated, Tensors t, 
   hipStream_t s = (hipStream_t)stream;
   g.acc_data = g.acc_w = md.accumulate;
   const int path = md.path;
+  const int dt = base_dtype(d), s32 = sampling_f32(d);
+  t.samp32 = s32;
   g.in_cl = md.input_layout == MDCONV_LAYOUT_CHANNELS_LAST ? 1 : 0;
-  if (g.in_cl && !(path != MDCONV_PATH_DIRECT && hp_supported(g, d->dtype, true) && g.C % 32 == 0)) {
+  if (g.in_cl && !(path != MDCONV_PATH_DIRECT && hp_supported(g, dt, true) && g.C % 32 == 0)) {
     set_error("channels-last input is only supported by the native 16-bit kernels with C_in a multiple of 32");
     return MDCONV_EUNSUPPORTED;
   }
-  if (path != MDCONV_PATH_DIRECT && hp_supported(g, d->dtype, true)) {
-    if ((rc = check_ws(ws, ws_bytes, hp_workspace_bytes(g, d->dtype, true)))) return rc;
+  if (path != MDCONV_PATH_DIRECT && hp_supported(g, dt, true)) {
+    if ((rc = check_ws(ws, ws_bytes, hp_workspace_bytes(g, dt, true)))) return rc;
     g_last_path = MDCONV_PATH_MFMA;
     g_last_kernels = MDCONV_KERNELS_HP;
-    return hp_backward(g, d->dtype, t, ws, s);
+    return hp_backward(g, dt, t, ws, s);
   }
-  const bool mfma_ok = mfma_supported(g, d->dtype, true);
+  const bool mfma_ok = mfma_ok_for(g, dt, s32, true);
   if (path == MDCONV_PATH_MFMA && !mfma_ok) {
     set_error("MDCONV_PATH=mfma but this shape/dtype is not supported by the MFMA kernels");
     return MDCONV_EUNSUPPORTED;
   }
   if (mfma_ok && path != MDCONV_PATH_DIRECT) {
-    if ((rc = check_ws(ws, ws_bytes, mfma_workspace_bytes(g, d->dtype, true)))) return rc;
     g_last_path = MDCONV_PATH_MFMA;
     g_last_kernels = MDCONV_KERNELS_F32;
-    return mfma_backward(g, d->dtype, t, ws, s);
+    if (s32) {
+      if ((rc = check_ws(ws, ws_bytes, samp32_workspace_bytes(g, true, true)))) return rc;
+      return samp32_backward(g, dt, t, ws, s, true);
+    }
+    if ((rc = check_ws(ws, ws_bytes, mfma_workspace_bytes(g, dt, true)))) return rc;
+    return mfma_backward(g, dt, t, ws, s);
   }
   g_last_path = MDCONV_PATH_DIRECT;
   g_last_kernels = MDCONV_KERNELS_DIRECT;
-  note_direct_fallback(g, d->dtype, true, path);
-  if (d->dtype == MDCONV_F16 || d->dtype == MDCONV_BF16) {
+  note_direct_fallback(g, dt, true, path);
+  if (s32) {
+    if ((rc = check_ws(ws, ws_bytes, samp32_workspace_bytes(g, true, false)))) return rc;
+    return samp32_backward(g, dt, t, ws, s, false);
+  }
+  if (dt == MDCONV_F16 || dt == MDCONV_BF16) {
     if ((rc = check_ws(ws, ws_bytes, direct16_workspace_bytes(g)))) return rc;
-    if ((rc = direct16_backward(g, d->dtype, t, ws, s))) return rc;
+    if ((rc = direct16_backward(g, dt, t, ws, s))) return rc;
     return record_weight_ready(s);
   }
   if (!md.accumulate) {
     // the direct kernels scatter with atomics, so "overwrite" means: clear first
-    const size_t es = d->dtype == MDCONV_F64 ? 8 : (d->dtype == MDCONV_F32 ? 4 : 2);
+    const size_t es = dt == MDCONV_F64 ? 8 : (dt == MDCONV_F32 ? 4 : 2);
     const size_t n_off = (size_t)g.B * g.DG * g.nd * g.K * g.S_o, n_m = (size_t)g.B * g.DG * g.K * g.S_o;
     if ((rc = zero_bytes(t.grad_input, (size_t)g.B * g.C * g.S_i * es, s)) ||
         (rc = zero_bytes(t.grad_offset, n_off * es, s)) ||
@@ -337,7 +370,7 @@ static int run_backward(const mdconv_desc *d, int nd, int modulated, Tensors t, 
     if (modulated && (rc = zero_bytes(t.grad_mask, n_m * es, s))) return rc;
     if (g.with_bias && (rc = zero_bytes(t.grad_bias, (size_t)g.O * es, s))) return rc;
   }
-  if ((rc = direct_backward(g, d->dtype, t, s))) return rc;
+  if ((rc = direct_backward(g, dt, t, s))) return rc;
   return record_weight_ready(s);
 }
 
@@ -420,19 +453,25 @@ size_t mdconv_workspace_bytes(const mdconv_desc *d, int backward) {
   Modes md;
   if (fill_geom(d, &g) || call_modes(d, &md)) return 0;
   g.in_cl = md.input_layout == MDCONV_LAYOUT_CHANNELS_LAST ? 1 : 0;   // (the plan of a channels-last call, where the caller says so)
-  const bool half = d->dtype == MDCONV_F16 || d->dtype == MDCONV_BF16;
-  const size_t direct = backward && half ? direct16_workspace_bytes(g) : 0;   // fp32 copies for the scatter kernels
+  const int dt = base_dtype(d), s32 = sampling_f32(d);
+  const bool half = dt == MDCONV_F16 || dt == MDCONV_BF16;
+  // fp32 copies for the scatter kernels (fp32 sampling: for the shape-generic kernels in either direction)
+  const size_t direct = s32 ? samp32_workspace_bytes(g, backward != 0, false)
+                            : (backward && half ? direct16_workspace_bytes(g) : 0);
   if (md.path == MDCONV_PATH_DIRECT) return direct;
-  if (hp_supported(g, d->dtype, backward != 0)) {
-    const size_t hp = hp_workspace_bytes(g, d->dtype, backward != 0);
-    if (backward || hp_forward_preferred(g, d->dtype)) return hp;
+  const auto f32_route = [&](bool bwd) {   // fp32 matrix kernels through fp32 copies
+    return s32 ? samp32_workspace_bytes(g, bwd, true) : mfma_workspace_bytes(g, dt, bwd);
+  };
+  if (hp_supported(g, dt, backward != 0)) {
+    const size_t hp = hp_workspace_bytes(g, dt, backward != 0);
+    if (backward || hp_forward_preferred(g, dt)) return hp;
     // a few-tile forward: fp32 kernels through fp32 copies, unless the input turns out to be channels-last (not known
     // here): enough for either
-    const size_t f32 = mfma_workspace_bytes(g, d->dtype, false);
+    const size_t f32 = f32_route(false);
     return hp > f32 ? hp : f32;
   }
-  if (!mfma_supported(g, d->dtype, backward != 0)) return direct;
-  return mfma_workspace_bytes(g, d->dtype, backward != 0);
+  if (!mfma_ok_for(g, dt, s32, backward != 0)) return direct;
+  return f32_route(backward != 0);
 }
 
 int mdconv_set_input_layout(int layout) {
@@ -448,7 +487,7 @@ int mdconv_input_layout_supported(const mdconv_desc *d, int layout, int backward
   if (layout == MDCONV_LAYOUT_NCHW) return 1;
   if (layout != MDCONV_LAYOUT_CHANNELS_LAST) return 0;
   g.in_cl = 1;   // the plan of a channels-last call (the group-padded layout needs the library's own input copy)
-  return md.path != MDCONV_PATH_DIRECT && hp_supported(g, d->dtype, backward != 0) && g.C % 32 == 0;
+  return md.path != MDCONV_PATH_DIRECT && hp_supported(g, base_dtype(d), backward != 0) && g.C % 32 == 0;
 }
 
 int mdconv_set_accumulate(int on) {

@@ -415,7 +415,13 @@ int check_launch(const char *what);
 struct Tensors {
   const void *input, *weight, *bias, *offset, *mask, *grad_output;
   void *output, *grad_input, *grad_weight, *grad_bias, *grad_offset, *grad_mask;
+  // 1 = offset / mask / grad_offset / grad_mask are fp32 while the other tensors are 16-bit (MDCONV_SAMPLING_F32)
+  int samp32;
 };
+// bytes of one offset / mask element of a call
+inline size_t samp_bytes(int dtype, const Tensors &t) {
+  return t.samp32 ? 4 : (dtype == MDCONV_F64 ? 8 : (dtype == MDCONV_F32 ? 4 : 2));
+}
 
 // direct (VALU) path, any shape / dtype
 int direct_forward(const Geom &g, int dtype, const Tensors &t, hipStream_t stream);

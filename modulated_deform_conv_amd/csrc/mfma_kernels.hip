@@ -547,6 +547,93 @@ int direct16_backward(const Geom &g, int dtype, const Tensors &t, void *ws, hipS
   return MDCONV_OK;
 }
 
+// ---------------------------------------------------------------------------------------------
+// 16-bit tensors with fp32 offsets / masks (MDCONV_SAMPLING_F32) where the native 16-bit kernels do not run: the call
+// becomes an fp32 call of the same kernel family -- fp32 copies of input / weight / bias / grad_output in the workspace
+// (the route every such 16-bit call takes anyway, one rounding per result), the caller's fp32 offset / mask read in place
+// and its grad_offset / grad_mask written in place in the caller's mode (no widen, no narrow).  grad_input / grad_weight /
+// grad_bias go through fp32 buffers that start from the caller's values in accumulate mode.
+// ---------------------------------------------------------------------------------------------
+namespace {
+struct S32Plan { size_t off_x, off_w, off_b, off_o, off_gi, off_gw, off_inner, total; };   // off_o: output / grad_output
+S32Plan samp32_plan(const Geom &g, bool backward, bool mfma) {
+  S32Plan p;
+  size_t off = 0;
+  auto take = [&](size_t &slot, size_t elems) { slot = off; off += align_up(elems * sizeof(float)); };
+  const size_t n_x = (size_t)g.B * g.C * g.S_i, n_w = (size_t)g.O * g.Cg * g.K, n_o = (size_t)g.B * g.O * g.S_o;
+  take(p.off_x, n_x); take(p.off_w, n_w); take(p.off_b, g.O); take(p.off_o, n_o);
+  p.off_gi = p.off_gw = off;
+  if (backward) { take(p.off_gi, n_x); take(p.off_gw, n_w + g.O); }   // grad_bias follows grad_weight
+  p.off_inner = off;
+  p.total = off + (mfma ? mfma_workspace_bytes(g, MDCONV_F32, backward) : 0);
+  return p;
+}
+}  // namespace
+
+size_t samp32_workspace_bytes(const Geom &g, bool backward, bool mfma) { return samp32_plan(g, backward, mfma).total; }
+
+int samp32_forward(const Geom &g, int dtype, const Tensors &t, void *ws, hipStream_t stream, bool mfma) {
+  const S32Plan p = samp32_plan(g, false, mfma);
+  char *base = (char *)ws;
+  const int64_t n_x = (int64_t)g.B * g.C * g.S_i, n_w = (int64_t)g.O * g.Cg * g.K, n_o = (int64_t)g.B * g.O * g.S_o;
+  int rc;
+  if ((rc = widen(dtype, t.input, (float *)(base + p.off_x), n_x, stream))) return rc;
+  if ((rc = widen(dtype, t.weight, (float *)(base + p.off_w), n_w, stream))) return rc;
+  if (g.with_bias && (rc = widen(dtype, t.bias, (float *)(base + p.off_b), g.O, stream))) return rc;
+  Tensors tc = t;
+  tc.samp32 = 0;   // every tensor of the inner call is fp32
+  tc.input = base + p.off_x; tc.weight = base + p.off_w; tc.bias = g.with_bias ? base + p.off_b : nullptr;
+  tc.output = base + p.off_o;
+  rc = mfma ? mfma_forward(g, MDCONV_F32, tc, base + p.off_inner, stream) : direct_forward(g, MDCONV_F32, tc, stream);
+  if (rc) return rc;
+  return narrow(dtype, (const float *)tc.output, t.output, n_o, false, stream);
+}
+
+int samp32_backward(const Geom &g, int dtype, const Tensors &t, void *ws, hipStream_t stream, bool mfma) {
+  const S32Plan p = samp32_plan(g, true, mfma);
+  char *base = (char *)ws;
+  const int64_t n_x = (int64_t)g.B * g.C * g.S_i, n_w = (int64_t)g.O * g.Cg * g.K, n_o = (int64_t)g.B * g.O * g.S_o;
+  const int64_t n_off = (int64_t)g.B * g.DG * g.nd * g.K * g.S_o, n_m = (int64_t)g.B * g.DG * g.K * g.S_o;
+  float *gi = (float *)(base + p.off_gi), *gw = (float *)(base + p.off_gw), *gb = gw + n_w;
+  int rc;
+  if ((rc = widen(dtype, t.input, (float *)(base + p.off_x), n_x, stream))) return rc;
+  if ((rc = widen(dtype, t.weight, (float *)(base + p.off_w), n_w, stream))) return rc;
+  if ((rc = widen(dtype, t.grad_output, (float *)(base + p.off_o), n_o, stream))) return rc;
+  // the shape-generic kernels add with atomics: their buffers start from the caller's values or from zero
+  if (g.acc_data || !mfma) {
+    if (g.acc_data) rc = widen(dtype, t.grad_input, gi, n_x, stream);
+    else rc = zero_bytes(gi, (size_t)n_x * 4, stream);
+    if (rc) return rc;
+  }
+  if (g.acc_w || !mfma) {
+    if (g.acc_w) {
+      if ((rc = widen(dtype, t.grad_weight, gw, n_w, stream))) return rc;
+      if (g.with_bias && (rc = widen(dtype, t.grad_bias, gb, g.O, stream))) return rc;
+    } else if ((rc = zero_bytes(gw, (size_t)(n_w + g.O) * 4, stream))) {
+      return rc;
+    }
+  }
+  if (!mfma && !g.acc_data) {
+    if ((rc = zero_bytes(t.grad_offset, (size_t)n_off * 4, stream))) return rc;
+    if (t.grad_mask && (rc = zero_bytes(t.grad_mask, (size_t)n_m * 4, stream))) return rc;
+  }
+  Tensors tc = t;
+  tc.samp32 = 0;   // every tensor of the inner call is fp32
+  tc.input = base + p.off_x; tc.weight = base + p.off_w; tc.grad_output = base + p.off_o;
+  tc.bias = nullptr;   // (the backward reads no bias)
+  tc.grad_input = gi; tc.grad_weight = gw; tc.grad_bias = g.with_bias ? gb : nullptr;
+  Geom gc = g;
+  if (!mfma) gc.acc_data = gc.acc_w = 1;
+  rc = mfma ? mfma_backward(gc, MDCONV_F32, tc, base + p.off_inner, stream) : direct_backward(gc, MDCONV_F32, tc, stream);
+  if (rc) return rc;
+  // grad_weight / grad_bias first: the weights-ready event (mdconv_stream_wait_weight_ready) is recorded again once they
+  // are in the caller's buffers
+  if ((rc = narrow(dtype, gw, t.grad_weight, n_w, false, stream))) return rc;
+  if (g.with_bias && (rc = narrow(dtype, gb, t.grad_bias, g.O, false, stream))) return rc;
+  if ((rc = record_weight_ready(stream))) return rc;
+  return narrow(dtype, gi, t.grad_input, n_x, false, stream);
+}
+
 static bool native_supported(const Geom &g, int dtype, bool backward) {
   if (dtype != MDCONV_F32 && dtype != MDCONV_F16 && dtype != MDCONV_BF16) return false;
   if (g.in_sz[g.nd - 1] < 2) return false;   // paired-corner gathers need 2 columns

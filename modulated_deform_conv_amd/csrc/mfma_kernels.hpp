@@ -13,6 +13,12 @@ int mfma_backward(const Geom &g, int dtype, const Tensors &t, void *ws, hipStrea
 size_t direct16_workspace_bytes(const Geom &g);
 int direct16_backward(const Geom &g, int dtype, const Tensors &t, void *ws, hipStream_t stream);
 
+// 16-bit tensors with fp32 offsets / masks (MDCONV_SAMPLING_F32) on the fp32 kernels: fp32 copies of the 16-bit tensors,
+// the caller's fp32 offsets / masks / grad_offset / grad_mask as they are; `mfma` = the matrix kernels, else the shape-generic ones
+size_t samp32_workspace_bytes(const Geom &g, bool backward, bool mfma);
+int samp32_forward(const Geom &g, int dtype, const Tensors &t, void *ws, hipStream_t stream, bool mfma);
+int samp32_backward(const Geom &g, int dtype, const Tensors &t, void *ws, hipStream_t stream, bool mfma);
+
 // records the calling thread's "grad_weight / grad_bias are final" event on `stream`
 // (include/mdconv.h: mdconv_stream_wait_weight_ready)
 int record_weight_ready(hipStream_t stream);

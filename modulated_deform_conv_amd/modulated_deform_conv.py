@@ -8,6 +8,7 @@ four times; all compute goes through ``MDCONV_CUDA`` (this package's ctypes bind
 libmdconv_hip.so).  CPU tensors raise ``NotImplementedError`` exactly like the reference
 (modulated_deform_conv.py:22-23): there is no CPU fallback in the product.
 """
+import contextlib
 import math
 
 import torch
@@ -164,14 +165,23 @@ modulated_deform_conv3d = ModulatedDeformConv3dFunction.apply
 
 
 class _DeformConvNd(nn.Module):
-    """Shared body of the four modules (reference :354-537).  ``bias`` defaults to False."""
+    """Shared body of the four modules (reference :354-537).  ``bias`` defaults to False.
+
+    ``sampling_dtype`` (keyword only): ``None`` (default) runs every tensor in one dtype -- under autocast the
+    autocast dtype, offsets and masks included.  ``torch.float32``: under autocast the offsets and masks stay fp32
+    while input, weight and bias run in the autocast dtype ("fp32 sampling": 16-bit data on the matrix cores,
+    sampling positions as exact as in fp32); for the ``*Pack`` modules the offset / mask branch runs in the dtype
+    of its own weights (fp32 parameters: fp32) outside autocast.  Outside autocast the tensors go as they are."""
     _nd = 2
     _modulated = False
     _op = None
 
     def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, dilation=1,
-                 groups=1, deformable_groups=1, bias=False, in_step=64):
+                 groups=1, deformable_groups=1, bias=False, in_step=64, *, sampling_dtype=None):
         super().__init__()
+        if sampling_dtype not in (None, torch.float32):
+            raise ValueError("sampling_dtype must be None or torch.float32, got %s" % (sampling_dtype,))
+        self.sampling_dtype = sampling_dtype
         assert in_channels % groups == 0, \
             'in_channels {} cannot be divisible by groups {}'.format(in_channels, groups)
         assert out_channels % groups == 0, \
@@ -196,6 +206,25 @@ class _DeformConvNd(nn.Module):
         return (self.weight, self.bias, self.stride, self.padding, self.dilation, self.groups,
                 self.deformable_groups, self.in_step)
 
+    def _fp32_sampling(self):
+        return self.sampling_dtype is not None and torch.is_autocast_enabled("cuda")
+
+    def _conv(self, op, x, offset, mask=None):
+        """op(x, offset, [mask,] weight, bias, ...), with fp32 sampling under autocast when the module asks for it:
+        the casts happen here, differentiably, and the Function runs with autocast off, so it keeps the dtypes."""
+        if not self._fp32_sampling():
+            head = (x, offset) if mask is None else (x, offset, mask)
+            return op(*head, *self._conv_args())
+        dt = torch.get_autocast_dtype("cuda")
+        cast = lambda t, d: t if t is None or t.dtype == d else t.to(d)
+        weight, bias = self.weight, self.bias
+        with torch.autocast("cuda", enabled=False):
+            x, weight, bias = cast(x, dt), cast(weight, dt), cast(bias, dt)
+            head = (x, cast(offset, self.sampling_dtype))
+            if mask is not None:
+                head += (cast(mask, self.sampling_dtype),)
+            return op(*head, weight, bias, *self._conv_args()[2:])
+
     def extra_repr(self):
         return ("{in_channels}, {out_channels}, kernel_size={kernel_size}, stride={stride}, "
                 "padding={padding}, dilation={dilation}, groups={groups}, "
@@ -206,28 +235,28 @@ class DeformConv2d(_DeformConvNd):
     _nd, _modulated = 2, False
 
     def forward(self, x, offset):
-        return deform_conv2d(x, offset, *self._conv_args())
+        return self._conv(deform_conv2d, x, offset)
 
 
 class ModulatedDeformConv2d(_DeformConvNd):
     _nd, _modulated = 2, True
 
     def forward(self, x, offset, mask):
-        return modulated_deform_conv2d(x, offset, mask, *self._conv_args())
+        return self._conv(modulated_deform_conv2d, x, offset, mask)
 
 
 class DeformConv3d(_DeformConvNd):
     _nd, _modulated = 3, False
 
     def forward(self, x, offset):
-        return deform_conv3d(x, offset, *self._conv_args())
+        return self._conv(deform_conv3d, x, offset)
 
 
 class ModulatedDeformConv3d(_DeformConvNd):
     _nd, _modulated = 3, True
 
     def forward(self, x, offset, mask):
-        return modulated_deform_conv3d(x, offset, mask, *self._conv_args())
+        return self._conv(modulated_deform_conv3d, x, offset, mask)
 
 
 class _PackMixin:
@@ -260,6 +289,16 @@ class _PackMixin:
     init_offset_mask = init_offset
 
 
+def _branch_autocast(m):
+    """fp32 sampling under autocast: the offset / mask branch runs outside autocast (its output is the sampling
+    positions: computed in the 16-bit autocast dtype they would be rounded before the cast to fp32)."""
+    return torch.autocast("cuda", enabled=False) if m._fp32_sampling() else contextlib.nullcontext()
+
+
+def _branch_input(m, x, conv):
+    return x.to(conv.weight.dtype) if m._fp32_sampling() else x
+
+
 def _make_pack(base, name):
     def __init__(self, *args, **kwargs):
         base.__init__(self, *args, **kwargs)
@@ -286,18 +325,24 @@ def _make_pack(base, name):
             # submodules keep working.
             co, cm = self.conv_offset, self.conv_mask
             conv_cls = nn.Conv2d if self._nd == 2 else nn.Conv3d
-            if (_plain(co, conv_cls) and _plain(cm, conv_cls) and co.stride == cm.stride
-                    and co.padding == cm.padding and co.dilation == cm.dilation
-                    and co.kernel_size == cm.kernel_size and co.weight.dtype == cm.weight.dtype):
-                conv = torch.nn.functional.conv2d if self._nd == 2 else torch.nn.functional.conv3d
-                y = conv(x, torch.cat((co.weight, cm.weight)), torch.cat((co.bias, cm.bias)),
-                         co.stride, co.padding, co.dilation)
-                n_off = co.out_channels
-                return base.forward(self, x, y[:, :n_off].contiguous(), y[:, n_off:].contiguous())
-            return base.forward(self, x, co(x), cm(x))
+            with _branch_autocast(self):
+                xb = _branch_input(self, x, co)
+                if (_plain(co, conv_cls) and _plain(cm, conv_cls) and co.stride == cm.stride
+                        and co.padding == cm.padding and co.dilation == cm.dilation
+                        and co.kernel_size == cm.kernel_size and co.weight.dtype == cm.weight.dtype):
+                    conv = torch.nn.functional.conv2d if self._nd == 2 else torch.nn.functional.conv3d
+                    y = conv(xb, torch.cat((co.weight, cm.weight)), torch.cat((co.bias, cm.bias)),
+                             co.stride, co.padding, co.dilation)
+                    n_off = co.out_channels
+                    offset, mask = y[:, :n_off].contiguous(), y[:, n_off:].contiguous()
+                else:
+                    offset, mask = co(xb), cm(xb)
+            return base.forward(self, x, offset, mask)
     else:
         def forward(self, x):
-            return base.forward(self, x, self.conv_offset(x))
+            with _branch_autocast(self):
+                offset = self.conv_offset(_branch_input(self, x, self.conv_offset))
+            return base.forward(self, x, offset)
     return type(name, (_PackMixin, base), {"__init__": __init__, "forward": forward})
 
 

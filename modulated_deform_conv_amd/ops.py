@@ -77,9 +77,12 @@ def _validate(input, offset, mask, weight, bias, stride, padding, dilation, grou
         raise RuntimeError("deform_conv: grad_output must be %s, got %s"
                            % ([B, O] + osz, list(grad_output.shape)))
     tensors = [t for t in (input, offset, mask, weight, bias, grad_output) if t is not None]
-    if any(t.dtype != input.dtype for t in tensors):
-        raise RuntimeError("deform_conv: all tensors must share one dtype, got %s"
-                           % [str(t.dtype) for t in tensors])
+    # one dtype for every tensor, or fp16 / bf16 tensors with fp32 offset and mask ("fp32 sampling",
+    # MDCONV_CUDA._sampling_f32): the gradients then come back in those dtypes too
+    samp = torch.float32 if MDCONV_CUDA._sampling_f32(input, offset, mask) else input.dtype
+    if any(t.dtype != (samp if t is offset or t is mask else input.dtype) for t in tensors):
+        raise RuntimeError("deform_conv: all tensors must share one dtype (or be fp16 / bf16 with fp32 offset and "
+                           "mask), got %s" % [str(t.dtype) for t in tensors])
     if input.dtype not in (torch.float32, torch.float16, torch.float64, torch.bfloat16):   # = MDCONV_CUDA._DTYPES
         raise RuntimeError("deform_conv: dtype must be float32 / float16 / bfloat16 / float64, got %s" % input.dtype)
     if any(t.device != input.device for t in tensors):
