@@ -357,7 +357,14 @@ int hp_forward(const Geom &gcall, int dtype, const Tensors &t, void *ws, hipStre
   for (int b0 = 0; b0 < g.B; b0 += Bc) {
     const int bc = g.B - b0 < Bc ? g.B - b0 : Bc;
     const Geom gc = chunk_geom(g, bc);
-    const HpDims hd = hp_dims(gc);
+    // The row width is a decision of the CALL: hp_dims narrows the rows of a small grid (MB = 1), and a shorter last
+    // chunk can be such a grid -- but the weights are packed and the row table is filled once, for the full chunk's
+    // rows, so every chunk runs those (a tail with its own MB read table rows nobody had written and skipped its
+    // output-channel blocks).  The kernel choice below follows the rows.
+    HpDims hd = hp_dims(gc);
+    hd.MB = hd0.MB;
+    hd.oranges = hd0.oranges;
+    hd.fwd_nmax = hd0.fwd_nmax;
     Tensors tc = t;
     tc.input = (const char *)t.input + (size_t)b0 * caller_channels(g) * g.S_i * 2;
     tc.offset = (const char *)t.offset + (size_t)b0 * nc_off * g.S_o * es_s;
@@ -415,6 +422,9 @@ int hp_backward(const Geom &gcall, int dtype, const Tensors &t, void *ws, hipStr
     if (g.in_cl) xt = (const char *)t.input + (size_t)b0 * g.S_i * g.C * 2;   // already channels-last
     else if ((rc = hp_nchw_to_nhwc(gc, hd, tc.input, base + L.off_xt, stream))) return rc;
     if ((rc = hp_csr_zero(gc, cnt, stream))) return rc;
+    // pixel-stationary or tap-stationary PER CHUNK: both kernels read the same packed W^T and block table, write the same
+    // grad_col rows and fp32 partials sized for either (max_ranges), and use_bwd3 is monotonic in the tile count, so a
+    // chunk that takes hp_bwd3 implies the full chunk did and the layout has the column rows (off_col)
     const bool bwd3 = use_bwd3(gc, hd);
     const bool bwd2 = !bwd3 && bwd_version() >= 2 && g.DG <= 4 && hp_bwd2_lds_bytes(gc, hd) <= 160 * 1024;
     profile_mark(1, true, stream, bwd3 ? "hp_bwd3_kernel" : (bwd2 ? "hp_bwd2_kernel" : "hp_bwd_kernel"));

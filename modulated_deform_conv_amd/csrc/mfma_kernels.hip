@@ -293,6 +293,16 @@ bool make_plan(const Geom &g, int dtype, bool backward, Plan *p) {
   p->half_io = dtype == MDCONV_F16 || dtype == MDCONV_BF16;
   p->gc = chunk_geom(g, bc);
   p->core_bytes = core_bytes_for(p->gc, backward);
+  // A shorter last chunk lays its workspace out anew (bwd_dims per chunk) and can need MORE than a full one: below the
+  // channels-last threshold GEMM-2 pads its rows to 256 output channels and its split-K partials grow (C = O = 64 at
+  // 32 x 32: chunks of 8 images 35.7 MB, a last chunk of 5 images 43.8 MB), and the split-K count follows the occupancy
+  // of the instance N % 32 selects.  A call has at most two chunk sizes: size the kernels' part for the larger need.
+  // (Single-chunk calls skip this.  With MDCONV_DEBUG_PLAN, bwd_dims prints a GEMM-2 plan line for every sizing done
+  // here too -- one image, the full chunk, the tail -- besides the lines of the chunks that are launched.)
+  if (g.B % bc) {
+    const size_t tail_bytes = core_bytes_for(chunk_geom(g, g.B % bc), backward);
+    if (tail_bytes > p->core_bytes) p->core_bytes = tail_bytes;
+  }
   size_t off = p->core_bytes;
   auto take = [&](size_t &slot, size_t elems) { slot = off; off += align_up(elems * sizeof(float)); };
   p->off_w = p->off_b = p->off_x = p->off_off = p->off_m = p->off_go = p->off_out = 0;

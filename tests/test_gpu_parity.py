@@ -139,9 +139,12 @@ sys.path.insert(0, %r)
 from tests.cases import CASE_BY_NAME, make_inputs
 from tests.util import run_product, run_oracle, assert_close
 from modulated_deform_conv_amd import _capi
-for name, dt, tol in (("cfg2s_mdcn2d_c64_28x28_b4", torch.float32, 1e-4), ("cfg2s_mdcn2d_c64_28x28_b4", torch.float16, 5e-3),
-                      ("cfg4s_dcn3d_c16_12cubed_b2", torch.float32, 1e-4)):
-    case = CASE_BY_NAME[name]
+# uneven chunks: 5 images of 28 x 28 as 2 + 2 + 1 (one image's grad_col: 64 * 9 * 784 * 4 = 1 806 336 B), 3 volumes of
+# 12 x 12 x 8 as 2 + 1 (16 * 27 * 1152 * 4 = 1 990 656 B) -- the last chunk is shorter than the others
+for name, dt, tol, over in (("cfg2s_mdcn2d_c64_28x28_b4", torch.float32, 1e-4, dict(B=5)),
+                            ("cfg2s_mdcn2d_c64_28x28_b4", torch.float16, 5e-3, dict(B=5)),
+                            ("cfg4s_dcn3d_c16_12cubed_b2", torch.float32, 1e-4, dict(B=3, in_sz=(12, 12, 8)))):
+    case = dict(CASE_BY_NAME[name], **over)
     t = make_inputs(case, dtype=dt, device="cuda")
     out, g, paths = run_product(case, t, "mfma")
     assert paths == ["mfma", "mfma"], paths
@@ -152,7 +155,7 @@ for name, dt, tol in (("cfg2s_mdcn2d_c64_28x28_b4", torch.float32, 1e-4), ("cfg2
             assert_close(k, g[k], w[k], tol)
 print("CHUNK_OK")
 """ % os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    env = dict(os.environ, MDCONV_CHUNK_LIMIT_BYTES=str(4 * 1024 * 1024))   # 2 or 1 images per chunk at these sizes
+    env = dict(os.environ, MDCONV_CHUNK_LIMIT_BYTES=str(4 * 1024 * 1024))   # 2 images per chunk at these sizes
     r = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=600)
     assert "CHUNK_OK" in r.stdout, r.stdout + r.stderr
 

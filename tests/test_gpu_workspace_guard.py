@@ -6,45 +6,20 @@ margins must be untouched.  (Round 5: `tools/fuzz_more.py` ended in a GPU memory
 bias -- the split backward sized its per-slice workspace without the grad_bias stage buffer that the first slice of a
 conv group appends, and wrote 32 * C_out * 4 bytes past the end.  The parity tests could not see it: the bytes landed in
 whatever the caching allocator had next to the workspace.)"""
-import ctypes
-
 import pytest
 import torch
 
 from tests.cases import CASES, D2, D3, M2, M3, _c, make_inputs
-from tests.util import run_product
+from tests.util import guarded_run, run_product
 
 pytestmark = pytest.mark.gpu
-
-PAD = 1 << 20
-PATTERN = 0xA5
 
 
 @pytest.fixture
 def guarded(monkeypatch):
     from modulated_deform_conv_amd import MDCONV_CUDA as M
-    from modulated_deform_conv_amd import _capi
     touched = []
-
-    def run_guarded(fn_name, d, backward, args_before_ws, input):
-        L = _capi.lib()
-        d.input_layout = int(not input.is_contiguous() and M._is_channels_last(input))
-        with torch.cuda.device(input.device):
-            ws_bytes = L.mdconv_workspace_bytes(ctypes.byref(d), int(backward))
-            big = torch.full((ws_bytes + 2 * PAD,), PATTERN, dtype=torch.uint8, device=input.device)
-            stream = torch.cuda.current_stream().cuda_stream
-            rc = getattr(L, fn_name)(ctypes.byref(d), *args_before_ws, ctypes.c_void_p(big.data_ptr() + PAD),
-                                     ctypes.c_size_t(ws_bytes), ctypes.c_void_p(stream))
-            torch.cuda.synchronize()
-            for side, region in (("below", big[:PAD]), ("above", big[PAD + ws_bytes:])):
-                bad = (region != PATTERN).nonzero()
-                if bad.numel():
-                    touched.append("%s: %d bytes %s the workspace (%d bytes), first at %+d" % (
-                        fn_name, bad.numel(), side, ws_bytes, int(bad[0]) - (PAD if side == "below" else 0)))
-        if rc != 0:
-            raise RuntimeError("%s failed (%d): %s" % (fn_name, rc, _capi.last_error()))
-
-    monkeypatch.setattr(M, "_run", run_guarded)
+    monkeypatch.setattr(M, "_run", guarded_run(touched))
     return touched
 
 

@@ -1,4 +1,6 @@
 """Helpers shared by the GPU parity tests."""
+import ctypes
+
 import torch
 
 import oracle
@@ -53,6 +55,86 @@ def run_product(case, t, path=None):
     grads = dict(grad_input=gi, grad_offset=goff, grad_mask=gm, grad_weight=gw,
                  grad_bias=gb if case["bias"] else None)
     return out, grads, paths
+
+
+def run_product_into(case, t, out, grads, accumulate=True, path=None):
+    """Forward + backward of ``case`` into CALLER-allocated tensors, for all four operators: ``out`` and the ``grads`` dict
+    (keys as run_product returns them; grad_mask / grad_bias None where the case has none).  ``accumulate`` False asks the
+    library to write the gradients (mdconv_desc.accumulate = 0), True to add to what the buffers hold.  The 2-D modulated
+    exports of MDCONV_CUDA allocate their results themselves, so that operator goes through the helpers underneath them
+    with the same checks."""
+    from modulated_deform_conv_amd import MDCONV_CUDA as M
+    from modulated_deform_conv_amd import _capi
+    op, nd = case["op"], ndim(case)
+    k, s, p, d = (tup(case[x], nd) for x in ("k", "stride", "padding", "dilation"))
+    tail = (case["groups"], case["dgroups"], case["in_step"], case["bias"])
+    geo = k + s + p + d + tail
+    x, w, off, m, go = t["input"], t["weight"], t["offset"], t["mask"], t["grad_output"]
+    b = t["bias"] if case["bias"] else x.new_empty(0)
+    gi, gw, goff, gm = grads["grad_input"], grads["grad_weight"], grads["grad_offset"], grads["grad_mask"]
+    gb = grads["grad_bias"] if case["bias"] else x.new_empty(0)
+    prev = _capi.set_path(path) if path else None
+    mode = _capi.overwrite_grads() if not accumulate else None
+    try:
+        if mode:
+            mode.__enter__()
+        if op == M2:
+            M._forward(2, True, "mdconv_modulated_deform_conv2d_forward", x, w, b, off, m, out, k, s, p, d, *tail)
+            desc = M._desc(2, True, x, w, k, s, p, d, *tail)
+            M._check_side(desc, 2, M._prod(k), off, m, go, "grad_output", M._out_shape(desc, 2))
+            M._backward_checks(x, w, off, m, gi, gw, gb, goff, gm, go, desc, case["bias"])
+            ptr = M._ptr
+            M._run("mdconv_modulated_deform_conv2d_backward", desc, True,
+                   [ptr(x), ptr(w), ptr(b), ptr(off), ptr(m), ptr(go), ptr(gi), ptr(goff), ptr(gm), ptr(gw), ptr(gb)], x)
+        elif op == D2:
+            M.deform_conv2d_forward_cuda(x, w, b, off, out, *geo)
+            M.deform_conv2d_backward_cuda(x, w, b, off, gi, gw, gb, goff, go, *geo)
+        elif op == D3:
+            M.deform_conv3d_forward_cuda(x, w, b, off, out, *geo)
+            M.deform_conv3d_backward_cuda(x, w, b, off, gi, gw, gb, goff, go, *geo)
+        else:
+            M.modulated_deform_conv3d_forward_cuda(x, w, b, off, m, out, *geo)
+            M.modulated_deform_conv3d_backward_cuda(x, w, b, off, m, gi, gw, gb, goff, gm, go, *geo)
+    finally:
+        if mode:
+            mode.__exit__(None, None, None)
+        if prev is not None:
+            _capi.set_path(prev)
+
+
+GUARD_PAD = 1 << 20
+GUARD_PATTERN = 0xA5
+
+
+def guarded_run(touched, calls=None):
+    """A replacement for ``MDCONV_CUDA._run`` that places each call's workspace in the MIDDLE of a larger allocation
+    filled with a byte pattern -- the two margins and the workspace itself, so a kernel that reads a table row nobody
+    wrote sees the pattern, not zeros the caching allocator happened to leave -- and appends one line to ``touched``
+    for every margin that changed.  ``calls`` (a list) receives (entry point, workspace bytes) per call."""
+    from modulated_deform_conv_amd import MDCONV_CUDA as M
+    from modulated_deform_conv_amd import _capi
+
+    def run_guarded(fn_name, d, backward, args_before_ws, input):
+        L = _capi.lib()
+        d.input_layout = int(not input.is_contiguous() and M._is_channels_last(input))
+        with torch.cuda.device(input.device):
+            ws_bytes = L.mdconv_workspace_bytes(ctypes.byref(d), int(backward))
+            big = torch.full((ws_bytes + 2 * GUARD_PAD,), GUARD_PATTERN, dtype=torch.uint8, device=input.device)
+            stream = torch.cuda.current_stream().cuda_stream
+            rc = getattr(L, fn_name)(ctypes.byref(d), *args_before_ws, ctypes.c_void_p(big.data_ptr() + GUARD_PAD),
+                                     ctypes.c_size_t(ws_bytes), ctypes.c_void_p(stream))
+            torch.cuda.synchronize()
+            if calls is not None:
+                calls.append((fn_name, ws_bytes))
+            for side, region in (("below", big[:GUARD_PAD]), ("above", big[GUARD_PAD + ws_bytes:])):
+                bad = (region != GUARD_PATTERN).nonzero()
+                if bad.numel():
+                    touched.append("%s: %d bytes %s the workspace (%d bytes), first at %+d" % (
+                        fn_name, bad.numel(), side, ws_bytes, int(bad[0]) - (GUARD_PAD if side == "below" else 0)))
+        if rc != 0:
+            raise RuntimeError("%s failed (%d): %s" % (fn_name, rc, _capi.last_error()))
+
+    return run_guarded
 
 
 def run_oracle(case, t, dtype, intermediates=None):
