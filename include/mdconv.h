@@ -94,8 +94,25 @@ typedef struct mdconv_desc {
   int input_layout; /* MDCONV_LAYOUT_NCHW or MDCONV_LAYOUT_CHANNELS_LAST (see below) */
   int path;         /* MDCONV_PATH_AUTO = the process default (MDCONV_PATH / mdconv_set_path), or a forced
                        MDCONV_PATH_DIRECT / MDCONV_PATH_MFMA for this call */
-  int reserved[5];  /* must be 0 */
+  int reserved[5];  /* reserved[0..3] must be 0; reserved[4] is the per-call FLAGS word (MDCONV_FLAG_*, below):
+                       any bit other than the flags defined here is MDCONV_EINVAL */
 } mdconv_desc;
+
+/* Per-call flags, in the last slot of the v2 tail (`flags` = mdconv_desc.reserved[4]; MDCONV_DESC_FLAGS(&d) names it).
+ * A descriptor without MDCONV_DESC_V2 ends before the word and never requests a flag.
+ *
+ * MDCONV_FLAG_DETERMINISTIC -- deterministic mode.  With the flag, on one device, one build of the library and the
+ * same descriptor and inputs, EVERY output of forward and backward is bit-identical from call to call: in accumulate
+ * and in overwrite mode, eager or replayed from a HIP graph, whatever else runs on the GPU.  Nothing is promised across
+ * batch sizes, devices or builds.  Without it all results but one already are (on the matrix-core kernels): grad_input
+ * sums the entries of its scatter lists in the order the list build's integer atomics arrived, so it is reproducible
+ * to rounding only.  The flag adds one pass that sorts every list into a canonical order before the gather
+ * (DESIGN.md section 4.6); the workspace may grow with it (mdconv_workspace_bytes honours the flag).
+ * The shape-generic kernels scatter with floating-point atomics and cannot give the guarantee: a backward with the flag
+ * that would run on them returns MDCONV_EUNSUPPORTED before anything is launched (the message names the shape rule);
+ * mdconv_deterministic_supported() tells beforehand.  The forward is always deterministic and ignores the flag. */
+#define MDCONV_FLAG_DETERMINISTIC 1
+#define MDCONV_DESC_FLAGS(d) ((d)->reserved[4])
 
 /* Initialiser of a v2 descriptor: `mdconv_desc d = MDCONV_DESC_INIT(2);` then fill in the shape.
  * (reference semantics by default: accumulate, NCHW input, process-default path) */
@@ -154,6 +171,14 @@ int mdconv_set_input_layout(int layout);
  * forward), so a caller that saved a channels-last input for its backward asks here and makes a
  * contiguous copy when the answer is 0 (modulated_deform_conv_amd/MDCONV_CUDA.py does). */
 int mdconv_input_layout_supported(const mdconv_desc *d, int layout, int backward);
+
+/* 1 if the forward (backward = 0) / backward (backward = 1) of `d` can run in deterministic mode
+ * (MDCONV_FLAG_DETERMINISTIC; the flag itself need not be set in `d`), else 0.  Every forward can.  A backward can
+ * exactly when it runs on the fp32 matrix-core kernels or the native 16-bit kernels -- decided by the routing of the
+ * call itself (`path`, fp32 sampling, padded / split / chunked plans included); 0 for calls that end on the
+ * shape-generic kernels: narrow channel counts, MDCONV_PATH_DIRECT, every fp64 call -- mdconv_last_error() then names
+ * the shape rule.  0 for an invalid descriptor. */
+int mdconv_deterministic_supported(const mdconv_desc *d, int backward);
 
 /* Multi-GPU overlap: every backward records an event on its stream as soon
  * as grad_weight and grad_bias are final -- before the grad_input gather is enqueued.

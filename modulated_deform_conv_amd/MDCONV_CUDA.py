@@ -13,6 +13,7 @@ Put this directory on ``sys.path`` (or ``import modulated_deform_conv_amd.MDCONV
 MDCONV_CUDA``) and the reference's own ``modulated_deform_conv.py`` runs unchanged.
 """
 import ctypes
+import warnings
 
 import torch
 
@@ -62,6 +63,9 @@ def _desc(nd, modulated, input, weight, ksz, stride, pad, dil, group, deformable
     d = _capi.MdconvDesc()
     d.ndim, d.modulated, d.dtype = nd | _capi.DESC_V2, int(modulated), _DTYPES[input.dtype]
     d.accumulate, d.input_layout, d.path = _capi.accumulate_mode(), 0, _capi.PATH_AUTO
+    # deterministic mode (include/mdconv.h: MDCONV_FLAG_DETERMINISTIC): the one place the flag enters a descriptor, so
+    # workspace sizing and every entry point see it
+    d.flags = _capi.FLAG_DETERMINISTIC if _capi.deterministic_mode() else 0
     d.batch, d.c_in, d.c_out = input.shape[0], input.shape[1], weight.shape[0]
     fill = lambda v, f: tuple(int(x) for x in v) + (f,) * (3 - nd)
     d.in_sz = (ctypes.c_int * 3)(*fill(input.shape[2:], 1))
@@ -133,9 +137,35 @@ def _same(ref, **tensors):
                                % (name, ref.dtype, ref.device, t.dtype, t.device))
 
 
+_warned_nondeterministic = False
+
+
+def _check_deterministic(L, d):
+    """A backward in deterministic mode the library cannot run deterministically (it would end on the shape-generic
+    kernels: floating-point atomics): RuntimeError -- or, when the mode comes from torch.use_deterministic_algorithms
+    with warn_only=True, one UserWarning per process and the call runs without the flag."""
+    global _warned_nondeterministic
+    if L.mdconv_deterministic_supported(ctypes.byref(d), 1):
+        return
+    msg = _capi.last_error()   # the library's reason: floating-point atomics, and the shape rule that sent the call there
+    if _capi.deterministic_override() is None and torch.is_deterministic_algorithms_warn_only_enabled():
+        if not _warned_nondeterministic:
+            _warned_nondeterministic = True
+            warnings.warn("modulated_deform_conv_amd: " + msg + "; running it non-deterministically "
+                          "(torch.use_deterministic_algorithms(True, warn_only=True)). This warning is issued once.",
+                          UserWarning, stacklevel=3)
+        d.flags = 0
+        return
+    raise RuntimeError("modulated_deform_conv_amd does not have a deterministic implementation of this backward: " + msg
+                       + ". Use torch.use_deterministic_algorithms(True, warn_only=True) or "
+                       "modulated_deform_conv_amd._capi.deterministic(False) to run it anyway.")
+
+
 def _run(fn_name, d, backward, args_before_ws, input):
     L = _capi.lib()
     d.input_layout = int(not input.is_contiguous() and _is_channels_last(input))
+    if backward and d.flags & _capi.FLAG_DETERMINISTIC:
+        _check_deterministic(L, d)
     with torch.cuda.device(input.device):
         ws_bytes = L.mdconv_workspace_bytes(ctypes.byref(d), int(backward))
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=input.device) if ws_bytes else None

@@ -15,13 +15,14 @@ SAMPLING_F32 = 0x10   # MDCONV_SAMPLING_F32: ORed into F16 / BF16, offset / mask
 PATH_AUTO, PATH_DIRECT, PATH_MFMA = 0, 1, 2
 ABI_VERSION = 2
 DESC_V2 = 0x100   # MDCONV_DESC_V2: the descriptor carries accumulate / input_layout / path
+FLAG_DETERMINISTIC = 1   # MDCONV_FLAG_DETERMINISTIC, in the flags word (MdconvDesc.flags = reserved[4])
 
 EXPORTS = (
     "mdconv_abi_version", "mdconv_last_error", "mdconv_out_size", "mdconv_workspace_bytes",
     "mdconv_set_path", "mdconv_last_path", "mdconv_last_kernels",
     "mdconv_profile_enable", "mdconv_profile_read", "mdconv_profile_reset", "mdconv_profile_name",
     "mdconv_stream_wait_weight_ready", "mdconv_stream_wait_weight_ready_on", "mdconv_set_accumulate", "mdconv_set_input_layout",
-    "mdconv_input_layout_supported",
+    "mdconv_input_layout_supported", "mdconv_deterministic_supported",
     "mdconv_deform_conv2d_forward", "mdconv_deform_conv2d_backward",
     "mdconv_modulated_deform_conv2d_forward", "mdconv_modulated_deform_conv2d_backward",
     "mdconv_deform_conv3d_forward", "mdconv_deform_conv3d_backward",
@@ -39,6 +40,15 @@ class MdconvDesc(ctypes.Structure):
                 ("with_bias", ctypes.c_int),
                 ("accumulate", ctypes.c_int), ("input_layout", ctypes.c_int), ("path", ctypes.c_int),
                 ("reserved", ctypes.c_int * 5)]
+
+    @property
+    def flags(self):
+        """The per-call flags word (MDCONV_FLAG_*): the last slot of the v2 tail, ``reserved[4]``."""
+        return self.reserved[4]
+
+    @flags.setter
+    def flags(self, value):
+        self.reserved[4] = int(value)
 
 
 _lib = None
@@ -75,6 +85,8 @@ def lib():
         L.mdconv_stream_wait_weight_ready_on.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
         L.mdconv_last_kernels.restype = ctypes.c_int
         L.mdconv_input_layout_supported.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int]
+        L.mdconv_deterministic_supported.restype = ctypes.c_int
+        L.mdconv_deterministic_supported.argtypes = [ctypes.c_void_p, ctypes.c_int]
         for name in EXPORTS[11:]:
             getattr(L, name).restype = ctypes.c_int
         if L.mdconv_abi_version() != ABI_VERSION:
@@ -125,6 +137,43 @@ class overwrite_grads:
 
     def __exit__(self, *exc):
         _modes.accumulate = self._prev
+        return False
+
+
+def deterministic_override():
+    """True / False inside a ``deterministic`` context manager of this thread, None outside."""
+    return getattr(_modes, "deterministic", None)
+
+
+def deterministic_mode():
+    """Whether a descriptor built now asks for deterministic mode (``MDCONV_FLAG_DETERMINISTIC``, include/mdconv.h):
+    the innermost ``deterministic`` context manager of this thread when one is active, otherwise
+    ``torch.are_deterministic_algorithms_enabled()`` -- read at the call, so a backward issued from an autograd worker
+    thread follows the process-wide torch setting."""
+    over = deterministic_override()
+    if over is not None:
+        return bool(over)
+    import torch
+    return bool(torch.are_deterministic_algorithms_enabled())
+
+
+class deterministic:
+    """Context manager: calls of MDCONV_CUDA issued inside by this thread run in deterministic mode (``on=True``: every
+    gradient bit-identical from call to call; a backward that would run on the shape-generic kernels raises) or out
+    of it (``on=False``), whatever ``torch.use_deterministic_algorithms`` says.  Thread-local, nests, and travels in
+    each call's descriptor like ``overwrite_grads``.  (A backward that autograd runs on a worker thread is outside the
+    ``with`` block of the thread that called ``.backward()``: use the torch setting there.)"""
+
+    def __init__(self, on=True):
+        self._on = bool(on)
+
+    def __enter__(self):
+        self._prev = deterministic_override()
+        _modes.deterministic = self._on
+        return self
+
+    def __exit__(self, *exc):
+        _modes.deterministic = self._prev
         return False
 
 

@@ -84,7 +84,7 @@ bool use_bwd3(const Geom &g, const HpDims &hd) {
 }
 
 struct FwdLayout { size_t off_xt, off_w, off_tab, total; };
-struct BwdLayout { size_t off_xt, off_w, off_tab, off_gcol, off_col, off_part, off_gw32, off_cnt, off_rowptr, off_entries, off_sums, total; };
+struct BwdLayout { size_t off_xt, off_w, off_tab, off_gcol, off_col, off_part, off_gw32, off_cnt, off_rowptr, off_entries, off_sums, off_sort, total; };
 
 // grad_input gather: MDCONV_HP_C2I = 1 -> one pass (every row read 2^(nd-1) times), 2 (default) -> two passes
 bool use_col2im2() {
@@ -114,6 +114,9 @@ FwdLayout fwd_layout(const Geom &gc, const HpDims &hd) {
   return L;
 }
 
+// int4 per list entry: short entries for 2-D fp16 tensors, long ones otherwise (hp_col2im.hip: ShortEntry)
+int hp_entry_width(const Geom &g, int dtype) { return g.nd == 2 && dtype == MDCONV_F16 ? 1 : 2; }
+
 BwdLayout bwd_layout(const Geom &gc, const HpDims &hd, int dtype) {
   BwdLayout L;
   size_t off = 0;
@@ -132,6 +135,9 @@ BwdLayout bwd_layout(const Geom &gc, const HpDims &hd, int dtype) {
   L.off_rowptr = off; off += align_up((size_t)gc.B * gc.DG * (S_e + 1) * sizeof(int));
   L.off_entries = off; off += align_up((size_t)gc.B * gc.DG * gc.K * gc.S_o * 32);
   L.off_sums = off; off += use_col2im2() ? align_up(hp_col2im_sums_bytes(gc, hd, dtype)) : 0;
+  // deterministic mode (Geom::det): scratch of the list sort, shaped like the entries (csr_sort.hip)
+  L.off_sort = off;
+  off += gc.det ? align_up(csr_sort_scratch_bytes(hp_entry_width(gc, dtype), (int64_t)gc.K * gc.S_o, gc.B * gc.DG)) : 0;
   L.total = off;
   return L;
 }
@@ -465,6 +471,10 @@ int hp_backward(const Geom &gcall, int dtype, const Tensors &t, void *ws, hipStr
     };
     if (!forked && (rc = weight_tail())) return rc;
     rc = hp_csr_build(gc, dtype, tc, cnt, rowptr, base + L.off_entries, gs);
+    // deterministic mode: the lists in canonical order before the gather sums them (on the gather's stream)
+    if (!rc && gc.det)
+      rc = csr_sort_rows(rowptr, base + L.off_entries, base + L.off_sort, hp_entry_width(gc, dtype), hp_anchor_space(gc),
+                         (int64_t)gc.K * gc.S_o, gc.B * gc.DG, gs);
     if (!rc) {
       profile_mark(3, true, gs, use_col2im2() ? "hp_col2im_sums_kernel" : "hp_col2im_kernel");
       rc = use_col2im2() ? hp_col2im2(gc, hd, dtype, tc, base + L.off_gcol, rowptr, base + L.off_entries, base + L.off_sums, gs)

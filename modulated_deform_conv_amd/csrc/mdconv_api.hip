@@ -69,8 +69,9 @@ static int current_path() {
 static int desc_ndim(const mdconv_desc *d) { return d->ndim & ~MDCONV_DESC_V2; }
 
 // Call modes of one call: from the descriptor (ABI v2) or from the v1 setters of the calling thread / process.
-struct Modes { int accumulate, input_layout, path; };
+struct Modes { int accumulate, input_layout, path, deterministic; };
 static int call_modes(const mdconv_desc *d, Modes *m) {
+  m->deterministic = 0;   // v1 descriptors end before the flag word: they never request the mode
   if (!(d->ndim & MDCONV_DESC_V2)) {
     m->accumulate = g_accumulate;
     m->input_layout = g_input_layout;
@@ -84,11 +85,17 @@ static int call_modes(const mdconv_desc *d, Modes *m) {
               d->input_layout, d->path);
     return MDCONV_EINVAL;
   }
-  for (int i = 0; i < 5; ++i)
+  for (int i = 0; i < 4; ++i)
     if (d->reserved[i] != 0) {
       set_error("mdconv_desc.reserved must be 0");
       return MDCONV_EINVAL;
     }
+  if (d->reserved[4] & ~MDCONV_FLAG_DETERMINISTIC) {
+    set_error("unknown bits 0x%x in the flags word of the descriptor (mdconv_desc.reserved[4]); MDCONV_FLAG_DETERMINISTIC is the only flag",
+              (unsigned)(d->reserved[4] & ~MDCONV_FLAG_DETERMINISTIC));
+    return MDCONV_EINVAL;
+  }
+  m->deterministic = (d->reserved[4] & MDCONV_FLAG_DETERMINISTIC) ? 1 : 0;
   m->accumulate = d->accumulate;
   m->input_layout = d->input_layout;
   m->path = d->path == MDCONV_PATH_AUTO ? current_path() : d->path;
@@ -222,6 +229,32 @@ static bool mfma_ok_for(const Geom &g, int dt, int s32, bool backward) {
   return mfma_supported(g, dt, backward) && (!s32 || mfma_supported(g, MDCONV_F32, backward));
 }
 
+// Kernel family a backward runs on -- the one routing decision, shared by run_backward, mdconv_workspace_bytes and
+// mdconv_deterministic_supported.  `g.in_cl` must be set.  (MDCONV_PATH_MFMA with a shape outside the matrix-core kernels
+// comes back as ROUTE_DIRECT: an error in run_backward.)
+enum Route { ROUTE_HP, ROUTE_F32, ROUTE_DIRECT };
+static Route backward_route(const Geom &g, int dt, int s32, int path) {
+  if (path != MDCONV_PATH_DIRECT && hp_supported(g, dt, true)) return ROUTE_HP;
+  if (path != MDCONV_PATH_DIRECT && mfma_ok_for(g, dt, s32, true)) return ROUTE_F32;
+  return ROUTE_DIRECT;
+}
+// why a backward ends on the shape-generic kernels (the text of the deterministic-mode refusal)
+static const char *direct_reason(const Geom &g, int dt, int path) {
+  if (path == MDCONV_PATH_DIRECT) return "the call selects MDCONV_PATH_DIRECT";
+  if (dt == MDCONV_F64) return "fp64 tensors have no matrix-core kernels";
+  if (g.in_sz[g.nd - 1] < 2) return "the last input axis is shorter than 2 (the matrix-core gathers read column pairs)";
+  if (g.C < 16 || g.O < 16 || g.C % 8)
+    return "the matrix-core backward needs C_in and C_out of at least 16 and C_in a multiple of 8";
+  if (g.DG > 1) return "the matrix-core backward needs C_in / deformable_groups of at least 8, aligned with the conv groups";
+  return "the shape is outside the matrix-core backward (grad_out tile beyond the LDS, or one image beyond 32-bit offsets)";
+}
+
+static void set_det_refusal(const Geom &g, int dt, int path) {
+  set_error("deterministic mode (MDCONV_FLAG_DETERMINISTIC): this backward would run on the shape-generic kernels, which "
+            "scatter grad_input and grad_weight with floating-point atomics (sums in arrival order) -- %s",
+            direct_reason(g, dt, path));
+}
+
 static int check_ws(void *ws, size_t have, size_t need) {
   if (need == 0) return MDCONV_OK;
   if (!ws || have < need) {
@@ -326,18 +359,23 @@ static int run_backward(const mdconv_desc *d, int nd, int modulated, Tensors t, 
     set_error("channels-last input is only supported by the native 16-bit kernels with C_in a multiple of 32");
     return MDCONV_EUNSUPPORTED;
   }
-  if (path != MDCONV_PATH_DIRECT && hp_supported(g, dt, true)) {
+  g.det = md.deterministic;
+  const Route route = backward_route(g, dt, s32, path);
+  if (route == ROUTE_HP) {
     if ((rc = check_ws(ws, ws_bytes, hp_workspace_bytes(g, dt, true)))) return rc;
     g_last_path = MDCONV_PATH_MFMA;
     g_last_kernels = MDCONV_KERNELS_HP;
     return hp_backward(g, dt, t, ws, s);
   }
-  const bool mfma_ok = mfma_ok_for(g, dt, s32, true);
-  if (path == MDCONV_PATH_MFMA && !mfma_ok) {
+  if (path == MDCONV_PATH_MFMA && route == ROUTE_DIRECT) {
     set_error("MDCONV_PATH=mfma but this shape/dtype is not supported by the MFMA kernels");
     return MDCONV_EUNSUPPORTED;
   }
-  if (mfma_ok && path != MDCONV_PATH_DIRECT) {
+  if (route == ROUTE_DIRECT && md.deterministic) {   // nothing has been launched
+    set_det_refusal(g, dt, path);
+    return MDCONV_EUNSUPPORTED;
+  }
+  if (route == ROUTE_F32) {
     g_last_path = MDCONV_PATH_MFMA;
     g_last_kernels = MDCONV_KERNELS_F32;
     if (s32) {
@@ -456,6 +494,7 @@ size_t mdconv_workspace_bytes(const mdconv_desc *d, int backward) {
   const int dt = base_dtype(d), s32 = sampling_f32(d);
   const bool half = dt == MDCONV_F16 || dt == MDCONV_BF16;
   // fp32 copies for the scatter kernels (fp32 sampling: for the shape-generic kernels in either direction)
+  g.det = backward ? md.deterministic : 0;   // the list sort's scratch (backward on the matrix-core kernels only)
   const size_t direct = s32 ? samp32_workspace_bytes(g, backward != 0, false)
                             : (backward && half ? direct16_workspace_bytes(g) : 0);
   if (md.path == MDCONV_PATH_DIRECT) return direct;
@@ -488,6 +527,18 @@ int mdconv_input_layout_supported(const mdconv_desc *d, int layout, int backward
   if (layout != MDCONV_LAYOUT_CHANNELS_LAST) return 0;
   g.in_cl = 1;   // the plan of a channels-last call (the group-padded layout needs the library's own input copy)
   return md.path != MDCONV_PATH_DIRECT && hp_supported(g, base_dtype(d), backward != 0) && g.C % 32 == 0;
+}
+
+int mdconv_deterministic_supported(const mdconv_desc *d, int backward) {
+  Geom g;
+  Modes md;
+  if (fill_geom(d, &g) || call_modes(d, &md)) return 0;
+  if (!backward) return 1;   // every forward is a fixed-order sum per output element
+  g.in_cl = md.input_layout == MDCONV_LAYOUT_CHANNELS_LAST ? 1 : 0;
+  g.det = 1;
+  if (backward_route(g, base_dtype(d), sampling_f32(d), md.path) != ROUTE_DIRECT) return 1;
+  set_det_refusal(g, base_dtype(d), md.path);   // the reason, for mdconv_last_error()
+  return 0;
 }
 
 int mdconv_set_accumulate(int on) {

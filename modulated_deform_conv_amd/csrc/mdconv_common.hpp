@@ -40,6 +40,9 @@ struct Geom {
   // channel c of it is channel (c / cm_pad) * cm_real + c % cm_pad of the caller's C_caller-channel tensors when
   // c % cm_pad < cm_real, else padding (zero input, zero weights).  cm_pad == 0: channels are the caller's.
   int cm_pad, cm_real, C_caller;
+  // 1 = deterministic mode (MDCONV_FLAG_DETERMINISTIC): the backward sorts the lists of its inverted scatter map into a
+  // canonical order before the grad_input gather (csr_sort.hip) and has the scratch for it in its workspace layout
+  int det;
 };
 // channel of the caller's input / weight / grad_input / grad_weight behind channel c of the kernels' rows; -1 = padding
 __host__ __device__ __forceinline__ int caller_channel(const Geom &g, int c) {
@@ -406,6 +409,14 @@ __device__ __forceinline__ void csr_scan_chunk(int S, const int *__restrict__ cn
   }
   if (hi == S && tid == 0) rp[S] = running;
 }
+
+// ---- deterministic mode: canonical order of the scatter lists (csr_sort.hip) --------------------
+// Sorts every list of rowptr [nseg][S_e + 1] in place: entries [nseg][seg_stride] of `width` int4 (1 or 2), ascending by
+// word 0, ties by the remaining words as unsigned integers.  `scratch`: csr_sort_scratch_bytes(), the shape of `entries`
+// (rows longer than a wave are ranked into it and copied back).  One kernel on `stream`, no host synchronisation.
+size_t csr_sort_scratch_bytes(int width, int64_t seg_stride, int nseg);
+int csr_sort_rows(const int *rowptr, void *entries, void *scratch, int width, int S_e, int64_t seg_stride, int nseg,
+                  hipStream_t stream);
 
 // ---- host-side helpers ------------------------------------------------------------------------
 int fill_geom(const mdconv_desc *d, Geom *g);  // validates; returns MDCONV_* code

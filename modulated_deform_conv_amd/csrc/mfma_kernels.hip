@@ -216,6 +216,11 @@ BwdDims bwd_dims(const Geom &g) {
   bd.two_pass = bd.sample_keyed && c2i_env >= 2 ? 1 : 0;
   bd.off_sums = off; off += bd.two_pass ? align_up(col2im3d_sums_bytes(g)) : 0;
   bd.off_bstage = off; off += g.with_bias ? align_up(grad_bias_stage_bytes(g)) : 0;
+  // deterministic mode: scratch of the list sort, shaped like the entries (csr_sort.hip); after everything else, so the
+  // default layout is untouched
+  bd.off_sort = off;
+  off += g.det ? align_up(csr_sort_scratch_bytes(bd.sample_keyed ? 2 : 1, (int64_t)g.K * g.S_o * (bd.sample_keyed ? 1 : nc / 2),
+                                                 g.B * g.DG)) : 0;
   bd.off_end = off;
   return bd;
 }
@@ -470,6 +475,10 @@ int backward_chunk_f32(const Geom &g, const Tensors &t, char *base, hipStream_t 
   }
   if (!rc && gemm2_first) rc = gemm2(false);
   if (!rc) rc = csr_build_f32(g, bd, t, cnt, rowptr, entries, gs);
+  // deterministic mode: the lists in canonical order before the gather sums them (on the gather's stream)
+  if (!rc && g.det)
+    rc = csr_sort_rows(rowptr, entries, base + bd.off_sort, bd.sample_keyed ? 2 : 1, bd.S_e,
+                       (int64_t)g.K * g.S_o * (bd.sample_keyed ? 1 : (1 << g.nd) / 2), g.B * g.DG, gs);
   if (!rc) {
     profile_mark(3, true, gs, bd.sample_keyed ? (bd.two_pass ? "col2im3d_sums_kernel" : "col2im3d_kernel") : "col2im_gather_kernel");
     rc = col2im_f32(g, bd, t, gcol, rowptr, entries, (float *)(base + bd.off_sums), gs);

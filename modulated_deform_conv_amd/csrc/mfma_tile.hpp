@@ -87,7 +87,8 @@ struct BwdDims {
   int sample_keyed;     // scatter lists: 1 = one entry per SAMPLE (3-D, mfma_csr3d.hip), 0 = per corner pair
   int S_e;              // list heads per (image, deformable group): anchor space (3-D) or S_i
   size_t off_wq, off_ga, off_table, off_part, off_gcol, off_cnt, off_rowptr, off_entries, off_bias,
-      off_xt, off_sums, off_bstage, off_end;   // off_sums: per-anchor partial sums of the two-pass 3-D gather (0 bytes otherwise)
+      off_xt, off_sums, off_bstage, off_sort, off_end;   // off_sums: per-anchor partial sums of the two-pass 3-D gather (0 bytes otherwise)
+  // off_sort: scratch of the list sort in deterministic mode (Geom::det; 0 bytes otherwise)
   int two_pass;         // 3-D grad_input gather: 1 = per-anchor partial sums + stencil (mfma_csr3d.hip), 0 = block walk
 };
 BwdDims bwd_dims(const Geom &g);

@@ -171,7 +171,14 @@ class _DeformConvNd(nn.Module):
     autocast dtype, offsets and masks included.  ``torch.float32``: under autocast the offsets and masks stay fp32
     while input, weight and bias run in the autocast dtype ("fp32 sampling": 16-bit data on the matrix cores,
     sampling positions as exact as in fp32); for the ``*Pack`` modules the offset / mask branch runs in the dtype
-    of its own weights (fp32 parameters: fp32) outside autocast.  Outside autocast the tensors go as they are."""
+    of its own weights (fp32 parameters: fp32) outside autocast.  Outside autocast the tensors go as they are.
+
+    Deterministic mode: under ``torch.use_deterministic_algorithms(True)`` (or inside ``_capi.deterministic()``) forward and
+    backward are bit-identical from call to call on one device and one build (the backward sorts its scatter lists before
+    summing them; INTEGRATION.md, Reproducibility).  Shapes whose backward runs on the shape-generic kernels -- fp64 tensors,
+    C_in or C_out below 16 on images of a few hundred pixels (e.g. 4 -> 4 channels at 8 x 8) -- scatter with floating-point
+    atomics and refuse the mode: their backward raises ``RuntimeError`` (with ``warn_only=True``: one ``UserWarning``, then
+    runs as usual); their forward is deterministic and runs."""
     _nd = 2
     _modulated = False
     _op = None
