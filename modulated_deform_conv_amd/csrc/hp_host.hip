@@ -12,6 +12,7 @@
 
 #include <stdlib.h>
 
+#include "host_util.hpp"
 #include "mfma_kernels.hpp"
 
 namespace mdconv {
@@ -19,8 +20,6 @@ namespace mdconv {
 int num_cus();   // mfma_bwd_data.hip
 
 namespace {
-
-size_t align_up(size_t x) { return (x + 255) & ~(size_t)255; }
 
 int pow2_ceil(int x) {
   int p = 1;
@@ -33,22 +32,7 @@ bool hp_enabled() {
   return on != 0;
 }
 
-size_t hp_chunk_limit() {
-  static size_t lim = 0;
-  if (!lim) {
-    lim = (size_t)0x7e000000;   // below kHpOob
-    const char *e = getenv("MDCONV_CHUNK_LIMIT_BYTES");
-    if (e && atoll(e) > 0 && (size_t)atoll(e) < lim) lim = (size_t)atoll(e);
-  }
-  return lim;
-}
-
-Geom chunk_geom(const Geom &g, int bc) {
-  Geom c = g;
-  c.B = bc;
-  c.N = bc * g.S_o;
-  return c;
-}
+constexpr size_t kHpChunkCeiling = 0x7e000000;   // below kHpOob
 
 // which backward kernel: MDCONV_HP_BWD = 1 -> hp_bwd (lane = pixel), 2 -> hp_bwd2 (fused, tap-stationary),
 // 3 (default) -> hp_bwd3 + hp_gemm2 where the shape qualifies and is large enough to fill the chip (use_bwd3), else as 2;
@@ -94,7 +78,7 @@ bool use_col2im2() {
 
 // images per chunk: channels-last input copy (and one image's grad_col) below the limit
 int chunk_batch(const Geom &g, const HpDims &hd, bool backward) {
-  const size_t lim = hp_chunk_limit();
+  const size_t lim = chunk_limit(kHpChunkCeiling);
   size_t per = (size_t)g.S_i * hd.Cp * 2;
   const size_t per_out = (size_t)g.S_o * (backward ? hd.Op : g.O) * 2;
   if (per_out > per) per = per_out;

@@ -15,7 +15,7 @@
 
 #include "mdconv_common.hpp"
 #include "hp_kernels.hpp"
-#include "mfma_kernels.hpp"
+#include "mfma_plan.hpp"
 
 namespace mdconv {
 
@@ -200,7 +200,7 @@ int fill_geom(const mdconv_desc *d, Geom *g) {
 static void note_direct_fallback(const Geom &g, int dtype, bool backward, int path) {
   static std::atomic<bool> said{false};
   if (g.Cg < 16 || g.Og < 16 || dtype == MDCONV_F64 || path == MDCONV_PATH_DIRECT) return;
-  if (!backward && g.Cg < 64) return;   // narrow conv groups: the shape-generic forward is no slower (mfma_kernels.hip)
+  if (!backward && g.Cg < 64) return;   // narrow conv groups: the shape-generic forward is no slower (mfma_plans.hip)
   if (said.exchange(true)) return;
   const char *q = getenv("MDCONV_QUIET");
   if (q && atoi(q) != 0) return;
@@ -223,20 +223,84 @@ static int require(const void *p, const char *name) {
 // element type of the call's tensors (MDCONV_SAMPLING_F32 stripped) and whether offset / mask are fp32
 static int base_dtype(const mdconv_desc *d) { return d->dtype & ~MDCONV_SAMPLING_F32; }
 static int sampling_f32(const mdconv_desc *d) { return (d->dtype & MDCONV_SAMPLING_F32) ? 1 : 0; }
-// fp32 sampling outside the native 16-bit kernels runs the fp32 kernels of the family the 16-bit call would take
-// (samp32_forward / samp32_backward), so the MFMA family needs both dtypes
-static bool mfma_ok_for(const Geom &g, int dt, int s32, bool backward) {
-  return mfma_supported(g, dt, backward) && (!s32 || mfma_supported(g, MDCONV_F32, backward));
-}
 
-// Kernel family a backward runs on -- the one routing decision, shared by run_backward, mdconv_workspace_bytes and
-// mdconv_deterministic_supported.  `g.in_cl` must be set.  (MDCONV_PATH_MFMA with a shape outside the matrix-core kernels
-// comes back as ROUTE_DIRECT: an error in run_backward.)
-enum Route { ROUTE_HP, ROUTE_F32, ROUTE_DIRECT };
-static Route backward_route(const Geom &g, int dt, int s32, int path) {
-  if (path != MDCONV_PATH_DIRECT && hp_supported(g, dt, true)) return ROUTE_HP;
-  if (path != MDCONV_PATH_DIRECT && mfma_ok_for(g, dt, s32, true)) return ROUTE_F32;
-  return ROUTE_DIRECT;
+// ---------------------------------------------------------------------------------------------
+// The plan of one call: the kernel family it runs on, the copies it runs through and its workspace -- the one routing
+// decision, made by plan_call() and read by run_forward / run_backward, mdconv_workspace_bytes,
+// mdconv_deterministic_supported and mdconv_input_layout_supported.
+// ---------------------------------------------------------------------------------------------
+enum Route {
+  ROUTE_HP,              // native 16-bit kernels
+  ROUTE_F32,             // fp32 matrix kernels (16-bit tensors: chunk-wise fp32 copies inside the family)
+  ROUTE_F32_SAMP32,      // ... through the fp32 copies of a call with fp32 offsets / masks (`s32`)
+  ROUTE_DIRECT,          // shape-generic kernels
+  ROUTE_DIRECT_16,       // ... 16-bit backward through fp32 copies (`d16`)
+  ROUTE_DIRECT_SAMP32    // ... through the fp32 copies of a call with fp32 offsets / masks (`s32`)
+};
+// A call can be refused; `route` and the byte counts then still say where it would have gone (the sizing query reports them).
+enum Refusal { REFUSE_NONE, REFUSE_CHANNELS_LAST, REFUSE_PATH_MFMA, REFUSE_DETERMINISTIC };
+struct CallPlan {
+  Route route;
+  Refusal refused;
+  size_t bytes;      // workspace the route needs
+  size_t reported;   // what mdconv_workspace_bytes answers: `bytes`, but see the few-tile forwards in plan_call
+  MfmaPlan f32;      // ROUTE_F32
+  S32Plan s32;       // ROUTE_*_SAMP32
+  D16Plan d16;       // ROUTE_DIRECT_16
+};
+static bool route_is_direct(Route r) { return r == ROUTE_DIRECT || r == ROUTE_DIRECT_16 || r == ROUTE_DIRECT_SAMP32; }
+
+// `g` with in_cl and det set; `dt` the tensors' element type, `s32` fp32 offsets / masks, `path` the caller's MDCONV_PATH_*.
+static void plan_call(const Geom &g, int dt, int s32, int path, bool backward, CallPlan *cp) {
+  const bool half = dt == MDCONV_F16 || dt == MDCONV_BF16;
+  const bool hp = path != MDCONV_PATH_DIRECT && hp_supported(g, dt, backward);
+  cp->refused = g.in_cl && !(hp && g.C % 32 == 0) ? REFUSE_CHANNELS_LAST : REFUSE_NONE;
+  const size_t hp_bytes = hp ? hp_workspace_bytes(g, dt, backward) : 0;
+  // 16-bit forwards of a few tiles run faster on the fp32 kernels (hp_forward_preferred)
+  const bool few_tile = hp && !backward && !hp_forward_preferred(g, dt);
+  if (hp && !few_tile) {
+    cp->route = ROUTE_HP;
+    cp->bytes = cp->reported = hp_bytes;
+    return;
+  }
+  // fp32 sampling outside the native 16-bit kernels runs the fp32 kernels of the family the 16-bit call would take, so the
+  // matrix family needs a plan for both dtypes
+  bool mfma = false;
+  if (path != MDCONV_PATH_DIRECT) {
+    if (s32) {
+      if (mfma_supported(g, dt, backward)) samp32_plan(g, backward, true, &cp->s32), mfma = cp->s32.mfma;
+    } else {
+      mfma = mfma_plan(g, dt, backward, &cp->f32);
+    }
+  }
+  if (mfma) {
+    cp->route = s32 ? ROUTE_F32_SAMP32 : ROUTE_F32;
+    cp->bytes = s32 ? cp->s32.total : cp->f32.total;
+  } else if (s32) {
+    cp->route = ROUTE_DIRECT_SAMP32;
+    samp32_plan(g, backward, false, &cp->s32);
+    cp->bytes = cp->s32.total;
+  } else if (backward && half) {   // 16-bit atomics round at every add: fp32 copies for the scatter kernels
+    cp->route = ROUTE_DIRECT_16;
+    cp->d16 = direct16_plan(g);
+    cp->bytes = cp->d16.total;
+  } else {
+    cp->route = ROUTE_DIRECT;
+    cp->bytes = 0;
+  }
+  cp->reported = cp->bytes;
+  if (few_tile) {
+    // ... unless the input is channels-last, which only the native kernels read in place -- and which a sizing query
+    // made without the layout cannot know: the reported size is enough for either family
+    if (hp_bytes > cp->reported) cp->reported = hp_bytes;
+    if (g.in_cl) {
+      cp->route = ROUTE_HP;
+      cp->bytes = hp_bytes;
+    }
+  }
+  if (cp->refused || !route_is_direct(cp->route)) return;
+  if (path == MDCONV_PATH_MFMA) cp->refused = REFUSE_PATH_MFMA;
+  else if (g.det) cp->refused = REFUSE_DETERMINISTIC;   // the shape-generic backward sums in arrival order
 }
 // why a backward ends on the shape-generic kernels (the text of the deterministic-mode refusal)
 static const char *direct_reason(const Geom &g, int dt, int path) {
@@ -253,6 +317,17 @@ static void set_det_refusal(const Geom &g, int dt, int path) {
   set_error("deterministic mode (MDCONV_FLAG_DETERMINISTIC): this backward would run on the shape-generic kernels, which "
             "scatter grad_input and grad_weight with floating-point atomics (sums in arrival order) -- %s",
             direct_reason(g, dt, path));
+}
+
+// the error of a refused call (nothing has been launched)
+static int refuse(const CallPlan &cp, const Geom &g, int dt, int path) {
+  if (cp.refused == REFUSE_CHANNELS_LAST)
+    set_error("channels-last input is only supported by the native 16-bit kernels with C_in a multiple of 32");
+  else if (cp.refused == REFUSE_PATH_MFMA)
+    set_error("MDCONV_PATH=mfma but this shape/dtype is not supported by the MFMA kernels");
+  else
+    set_det_refusal(g, dt, path);
+  return MDCONV_EUNSUPPORTED;
 }
 
 static int check_ws(void *ws, size_t have, size_t need) {
@@ -291,41 +366,30 @@ static int run_forward(const mdconv_desc *d, int nd, int modulated, Tensors t, v
   const int dt = base_dtype(d), s32 = sampling_f32(d);
   t.samp32 = s32;
   g.in_cl = md.input_layout == MDCONV_LAYOUT_CHANNELS_LAST ? 1 : 0;
-  if (g.in_cl && !(path != MDCONV_PATH_DIRECT && hp_supported(g, dt, false) && g.C % 32 == 0)) {
-    set_error("channels-last input is only supported by the native 16-bit kernels with C_in a multiple of 32");
-    return MDCONV_EUNSUPPORTED;
+  CallPlan cp;
+  plan_call(g, dt, s32, path, false, &cp);
+  if (cp.refused) return refuse(cp, g, dt, path);
+  switch (cp.route) {
+    case ROUTE_HP:
+      if ((rc = check_ws(ws, ws_bytes, cp.bytes))) return rc;
+      g_last_path = MDCONV_PATH_MFMA;
+      g_last_kernels = MDCONV_KERNELS_HP;
+      return hp_forward(g, dt, t, ws, s);
+    case ROUTE_F32:
+    case ROUTE_F32_SAMP32:
+      g_last_path = MDCONV_PATH_MFMA;
+      g_last_kernels = MDCONV_KERNELS_F32;
+      if ((rc = check_ws(ws, ws_bytes, cp.bytes))) return rc;
+      if (cp.route == ROUTE_F32_SAMP32) return samp32_forward(g, dt, cp.s32, t, ws, s);
+      return mfma_forward(g, dt, cp.f32, t, ws, s);
+    default:
+      g_last_path = MDCONV_PATH_DIRECT;
+      g_last_kernels = MDCONV_KERNELS_DIRECT;
+      note_direct_fallback(g, dt, false, path);
+      if (cp.route != ROUTE_DIRECT_SAMP32) return direct_forward(g, dt, t, s);
+      if ((rc = check_ws(ws, ws_bytes, cp.bytes))) return rc;
+      return samp32_forward(g, dt, cp.s32, t, ws, s);
   }
-  // 16-bit tensors: native fp16 / bf16 kernels (hp_*.hip) when the shape qualifies (and is not one of the few-tile forwards
-  // that the fp32 kernels run faster: hp_forward_preferred)
-  if (path != MDCONV_PATH_DIRECT && hp_supported(g, dt, false) && (g.in_cl || hp_forward_preferred(g, dt))) {
-    if ((rc = check_ws(ws, ws_bytes, hp_workspace_bytes(g, dt, false)))) return rc;
-    g_last_path = MDCONV_PATH_MFMA;
-    g_last_kernels = MDCONV_KERNELS_HP;
-    return hp_forward(g, dt, t, ws, s);
-  }
-  const bool mfma_ok = mfma_ok_for(g, dt, s32, false);
-  if (path == MDCONV_PATH_MFMA && !mfma_ok) {
-    set_error("MDCONV_PATH=mfma but this shape/dtype is not supported by the MFMA kernels");
-    return MDCONV_EUNSUPPORTED;
-  }
-  if (mfma_ok && path != MDCONV_PATH_DIRECT) {
-    g_last_path = MDCONV_PATH_MFMA;
-    g_last_kernels = MDCONV_KERNELS_F32;
-    if (s32) {
-      if ((rc = check_ws(ws, ws_bytes, samp32_workspace_bytes(g, false, true)))) return rc;
-      return samp32_forward(g, dt, t, ws, s, true);
-    }
-    if ((rc = check_ws(ws, ws_bytes, mfma_workspace_bytes(g, dt, false)))) return rc;
-    return mfma_forward(g, dt, t, ws, s);
-  }
-  g_last_path = MDCONV_PATH_DIRECT;
-  g_last_kernels = MDCONV_KERNELS_DIRECT;
-  note_direct_fallback(g, dt, false, path);
-  if (s32) {
-    if ((rc = check_ws(ws, ws_bytes, samp32_workspace_bytes(g, false, false)))) return rc;
-    return samp32_forward(g, dt, t, ws, s, false);
-  }
-  return direct_forward(g, dt, t, s);
 }
 
 static int run_backward(const mdconv_desc *d, int nd, int modulated, Tensors t, void *ws,
@@ -355,46 +419,33 @@ static int run_backward(const mdconv_desc *d, int nd, int modulated, Tensors t, 
   const int dt = base_dtype(d), s32 = sampling_f32(d);
   t.samp32 = s32;
   g.in_cl = md.input_layout == MDCONV_LAYOUT_CHANNELS_LAST ? 1 : 0;
-  if (g.in_cl && !(path != MDCONV_PATH_DIRECT && hp_supported(g, dt, true) && g.C % 32 == 0)) {
-    set_error("channels-last input is only supported by the native 16-bit kernels with C_in a multiple of 32");
-    return MDCONV_EUNSUPPORTED;
-  }
   g.det = md.deterministic;
-  const Route route = backward_route(g, dt, s32, path);
-  if (route == ROUTE_HP) {
-    if ((rc = check_ws(ws, ws_bytes, hp_workspace_bytes(g, dt, true)))) return rc;
+  CallPlan cp;
+  plan_call(g, dt, s32, path, true, &cp);
+  if (cp.refused) return refuse(cp, g, dt, path);
+  if (cp.route == ROUTE_HP) {
+    if ((rc = check_ws(ws, ws_bytes, cp.bytes))) return rc;
     g_last_path = MDCONV_PATH_MFMA;
     g_last_kernels = MDCONV_KERNELS_HP;
     return hp_backward(g, dt, t, ws, s);
   }
-  if (path == MDCONV_PATH_MFMA && route == ROUTE_DIRECT) {
-    set_error("MDCONV_PATH=mfma but this shape/dtype is not supported by the MFMA kernels");
-    return MDCONV_EUNSUPPORTED;
-  }
-  if (route == ROUTE_DIRECT && md.deterministic) {   // nothing has been launched
-    set_det_refusal(g, dt, path);
-    return MDCONV_EUNSUPPORTED;
-  }
-  if (route == ROUTE_F32) {
+  if (cp.route == ROUTE_F32 || cp.route == ROUTE_F32_SAMP32) {
     g_last_path = MDCONV_PATH_MFMA;
     g_last_kernels = MDCONV_KERNELS_F32;
-    if (s32) {
-      if ((rc = check_ws(ws, ws_bytes, samp32_workspace_bytes(g, true, true)))) return rc;
-      return samp32_backward(g, dt, t, ws, s, true);
-    }
-    if ((rc = check_ws(ws, ws_bytes, mfma_workspace_bytes(g, dt, true)))) return rc;
-    return mfma_backward(g, dt, t, ws, s);
+    if ((rc = check_ws(ws, ws_bytes, cp.bytes))) return rc;
+    if (cp.route == ROUTE_F32_SAMP32) return samp32_backward(g, dt, cp.s32, t, ws, s);
+    return mfma_backward(g, dt, cp.f32, t, ws, s);
   }
   g_last_path = MDCONV_PATH_DIRECT;
   g_last_kernels = MDCONV_KERNELS_DIRECT;
   note_direct_fallback(g, dt, true, path);
-  if (s32) {
-    if ((rc = check_ws(ws, ws_bytes, samp32_workspace_bytes(g, true, false)))) return rc;
-    return samp32_backward(g, dt, t, ws, s, false);
+  if (cp.route == ROUTE_DIRECT_SAMP32) {
+    if ((rc = check_ws(ws, ws_bytes, cp.bytes))) return rc;
+    return samp32_backward(g, dt, cp.s32, t, ws, s);
   }
-  if (dt == MDCONV_F16 || dt == MDCONV_BF16) {
-    if ((rc = check_ws(ws, ws_bytes, direct16_workspace_bytes(g)))) return rc;
-    if ((rc = direct16_backward(g, dt, t, ws, s))) return rc;
+  if (cp.route == ROUTE_DIRECT_16) {
+    if ((rc = check_ws(ws, ws_bytes, cp.bytes))) return rc;
+    if ((rc = direct16_backward(g, dt, cp.d16, t, ws, s))) return rc;
     return record_weight_ready(s);
   }
   if (!md.accumulate) {
@@ -491,26 +542,10 @@ size_t mdconv_workspace_bytes(const mdconv_desc *d, int backward) {
   Modes md;
   if (fill_geom(d, &g) || call_modes(d, &md)) return 0;
   g.in_cl = md.input_layout == MDCONV_LAYOUT_CHANNELS_LAST ? 1 : 0;   // (the plan of a channels-last call, where the caller says so)
-  const int dt = base_dtype(d), s32 = sampling_f32(d);
-  const bool half = dt == MDCONV_F16 || dt == MDCONV_BF16;
-  // fp32 copies for the scatter kernels (fp32 sampling: for the shape-generic kernels in either direction)
   g.det = backward ? md.deterministic : 0;   // the list sort's scratch (backward on the matrix-core kernels only)
-  const size_t direct = s32 ? samp32_workspace_bytes(g, backward != 0, false)
-                            : (backward && half ? direct16_workspace_bytes(g) : 0);
-  if (md.path == MDCONV_PATH_DIRECT) return direct;
-  const auto f32_route = [&](bool bwd) {   // fp32 matrix kernels through fp32 copies
-    return s32 ? samp32_workspace_bytes(g, bwd, true) : mfma_workspace_bytes(g, dt, bwd);
-  };
-  if (hp_supported(g, dt, backward != 0)) {
-    const size_t hp = hp_workspace_bytes(g, dt, backward != 0);
-    if (backward || hp_forward_preferred(g, dt)) return hp;
-    // a few-tile forward: fp32 kernels through fp32 copies, unless the input turns out to be channels-last (not known
-    // here): enough for either
-    const size_t f32 = f32_route(false);
-    return hp > f32 ? hp : f32;
-  }
-  if (!mfma_ok_for(g, dt, s32, backward != 0)) return direct;
-  return f32_route(backward != 0);
+  CallPlan cp;
+  plan_call(g, base_dtype(d), sampling_f32(d), md.path, backward != 0, &cp);
+  return cp.reported;
 }
 
 int mdconv_set_input_layout(int layout) {
@@ -526,7 +561,9 @@ int mdconv_input_layout_supported(const mdconv_desc *d, int layout, int backward
   if (layout == MDCONV_LAYOUT_NCHW) return 1;
   if (layout != MDCONV_LAYOUT_CHANNELS_LAST) return 0;
   g.in_cl = 1;   // the plan of a channels-last call (the group-padded layout needs the library's own input copy)
-  return md.path != MDCONV_PATH_DIRECT && hp_supported(g, base_dtype(d), backward != 0) && g.C % 32 == 0;
+  CallPlan cp;
+  plan_call(g, base_dtype(d), sampling_f32(d), md.path, backward != 0, &cp);
+  return cp.refused != REFUSE_CHANNELS_LAST;
 }
 
 int mdconv_deterministic_supported(const mdconv_desc *d, int backward) {
@@ -536,7 +573,9 @@ int mdconv_deterministic_supported(const mdconv_desc *d, int backward) {
   if (!backward) return 1;   // every forward is a fixed-order sum per output element
   g.in_cl = md.input_layout == MDCONV_LAYOUT_CHANNELS_LAST ? 1 : 0;
   g.det = 1;
-  if (backward_route(g, base_dtype(d), sampling_f32(d), md.path) != ROUTE_DIRECT) return 1;
+  CallPlan cp;
+  plan_call(g, base_dtype(d), sampling_f32(d), md.path, true, &cp);
+  if (!route_is_direct(cp.route)) return 1;
   set_det_refusal(g, base_dtype(d), md.path);   // the reason, for mdconv_last_error()
   return 0;
 }

@@ -4,20 +4,9 @@
 
 namespace mdconv {
 
-bool mfma_supported(const Geom &g, int dtype, bool backward);
-size_t mfma_workspace_bytes(const Geom &g, int dtype, bool backward);
-int mfma_forward(const Geom &g, int dtype, const Tensors &t, void *ws, hipStream_t stream);
-int mfma_backward(const Geom &g, int dtype, const Tensors &t, void *ws, hipStream_t stream);
-
-// 16-bit tensors on the shape-generic backward kernels: fp32 copies in the workspace, one rounding per gradient
-size_t direct16_workspace_bytes(const Geom &g);
-int direct16_backward(const Geom &g, int dtype, const Tensors &t, void *ws, hipStream_t stream);
-
-// 16-bit tensors with fp32 offsets / masks (MDCONV_SAMPLING_F32) on the fp32 kernels: fp32 copies of the 16-bit tensors,
-// the caller's fp32 offsets / masks / grad_offset / grad_mask as they are; `mfma` = the matrix kernels, else the shape-generic ones
-size_t samp32_workspace_bytes(const Geom &g, bool backward, bool mfma);
-int samp32_forward(const Geom &g, int dtype, const Tensors &t, void *ws, hipStream_t stream, bool mfma);
-int samp32_backward(const Geom &g, int dtype, const Tensors &t, void *ws, hipStream_t stream, bool mfma);
+// the family's plans and their execution: mfma_plan.hpp (host code only)
+bool mfma_supported(const Geom &g, int dtype, bool backward);            // mfma_plan() finds a plan
+size_t mfma_workspace_bytes(const Geom &g, int dtype, bool backward);    // its `total` (0: none)
 
 // records the calling thread's "grad_weight / grad_bias are final" event on `stream`
 // (include/mdconv.h: mdconv_stream_wait_weight_ready)

@@ -51,7 +51,7 @@ CASES = [
     _c("cfg3s_mdcn2d_c256_g32_dg4_10x10", M2, 2, 256, 256, (10, 10), 3, groups=32, dgroups=4, bias=False, tier="medium", seed=35),
     _c("mfma_dcn2d_dg4_c1024_o16", D2, 1, 1024, 16, (6, 6), 3, dgroups=4, bias=False, tier="medium", seed=36),
     # deformable groups the fp32 matrix-core backward does not tile (C_in/DG of 16, 24, 32, 48): DG independent
-    # single-group slices (mfma_kernels.hip, split_backward) -- one conv group, a slice inside a conv group
+    # single-group slices (mfma_plans.hip, split_backward) -- one conv group, a slice inside a conv group
     # (weight / grad_output slices), a slice made of whole conv groups, 3-D
     _c("mfma_split_mdcn2d_dg4_c128_o128", M2, 2, 128, 128, (14, 13), 3, dgroups=4, tier="medium", seed=71),
     _c("mfma_split_dcn2d_g2_dg4_c128_o64", D2, 3, 128, 64, (9, 11), 3, groups=2, dgroups=4, in_step=1, tier="medium", seed=72),

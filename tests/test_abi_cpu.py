@@ -293,3 +293,18 @@ def test_a_c_caller_builds_against_the_header_and_links_the_library(capi, tmp_pa
     if shutil.which("g++"):
         subprocess.run(["g++", "-std=c++17", "-Wall", "-Werror", "-fsyntax-only", "-x", "c++", "-I", os.path.join(ROOT, "include"),
                         str(src)], check=True, capture_output=True)
+
+
+def test_plan_table_tool_lists_every_combination(capi):
+    """tools/plan_table.py (the routing / workspace table two builds are compared by) runs without a device: one line per
+    (case, dtype, direction, path, deterministic flag, layout) over tests/cases.py CASES, three integers each."""
+    import subprocess
+    import sys
+    from tests.cases import CASES
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "plan_table.py"), "--cases-only"], cwd=ROOT,
+                       capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = r.stdout.splitlines()
+    assert len(lines) == len(CASES) * 6 * 2 * 3 * 2 * 2
+    assert len(set(ln.split(":")[0] for ln in lines)) == len(lines)
+    assert all(re.fullmatch(r"\S+ \w+ (fwd|bwd) (auto|direct|mfma) det[01] cl[01]: \d+ [01] [01]", ln) for ln in lines)

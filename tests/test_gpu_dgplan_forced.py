@@ -1,4 +1,4 @@
-"""Deformable groups the fp32 matrix kernels do not tile have two plans (mfma_kernels.hip): ONE problem with every group padded
+"""Deformable groups the fp32 matrix kernels do not tile have two plans (mfma_plans.hip): ONE problem with every group padded
 to a tileable size (the default since round 6, one conv group) or DG single-group slices (conv groups, and every such shape
 until round 6).  The plan is chosen once per process (MDCONV_DG_PLAN), hence child processes: the split / padded parity cases
 run under both and are compared with the oracle as usual (tests/test_gpu_parity.py), so the slices stay covered for the
@@ -26,7 +26,7 @@ def test_parity_with_the_deformable_group_plan_forced(plan):
 @pytest.mark.parametrize("on", ["1", "0"])
 def test_parity_with_channel_padding_forced(on):
     """One deformable group and C_in not a multiple of 64: padded to 64 channels the shape runs on the channels-last fp32 kernels
-    (mfma_kernels.hip, pad_channels_preferred: 3-D from 2048 pixels, narrow 2-D from 8192).  MDCONV_PAD_CHANNELS = 1 takes the
+    (mfma_plans.hip, pad_channels_preferred: 3-D from 2048 pixels, narrow 2-D from 8192).  MDCONV_PAD_CHANNELS = 1 takes the
     plan for every eligible shape, 0 for none: the matrix-path parity cases and the fp32 random shapes run under both."""
     env = dict(os.environ, MDCONV_PAD_CHANNELS=on)
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
