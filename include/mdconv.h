@@ -57,6 +57,20 @@ enum { MDCONV_F32 = 0, MDCONV_F16 = 1, MDCONV_F64 = 2, MDCONV_BF16 = 3 };
  * 0.25 px).  Every shape and call mode of the 16-bit type runs with it, on the same kernel family.
  * With MDCONV_F32 / MDCONV_F64 the flag is MDCONV_EINVAL. */
 #define MDCONV_SAMPLING_F32 0x10
+/* "fp32 weight gradients": flag ORed into mdconv_desc.dtype next to MDCONV_SAMPLING_F32 (the two combine freely) --
+ * MDCONV_F16 | MDCONV_WGRAD_F32, MDCONV_BF16 | MDCONV_SAMPLING_F32 | MDCONV_WGRAD_F32, ...  The backward's grad_weight and
+ * grad_bias are then fp32 buffers ([C_out, C_in/groups, k...] and [C_out] floats) while every other tensor keeps its type.
+ * Every 16-bit backward sums these two gradients in fp32 and rounds them once on the way out; with the flag that last
+ * rounding is left out: overwrite mode (`accumulate` = 0) stores the fp32 sums, accumulate mode adds them to the buffers in
+ * fp32 (grad = grad + sum, one fp32 add per element).  So a sum over B x S_o samples that exceeds the fp16 range stays
+ * finite, fp32 master weights receive all 24 bits, and micro-batches or data-parallel ranks accumulate without a 16-bit
+ * round trip.  The flag never changes the route of a call (kernel family, plan, batch chunks); the workspace can grow by
+ * the wider grad_weight rows of a padded or sliced plan (mdconv_workspace_bytes honours the flag).  The weights-ready event
+ * is recorded once the fp32 buffers are final.  Forward entry points accept and ignore the flag, so one descriptor serves
+ * both directions.  With MDCONV_F32 / MDCONV_F64 the flag is MDCONV_EINVAL.
+ * (The value skips 0x20: callers and tests written against earlier releases rely on `MDCONV_F16 | 0x20` being
+ * MDCONV_EINVAL, like every other dtype value that was invalid before the flag existed; it still is.) */
+#define MDCONV_WGRAD_F32 0x40
 
 enum {
   MDCONV_OK = 0,
@@ -75,7 +89,8 @@ typedef struct mdconv_desc {
   int ndim;       /* 2 or 3, | MDCONV_DESC_V2 when the v2 fields below are filled in */
   int modulated;  /* 0 = DeformConv (DCNv1), 1 = ModulatedDeformConv (DCNv2) */
   int dtype;      /* MDCONV_F32 / F16 / F64 / BF16 -- element type of every tensor (offset / mask and their
-                     gradients: fp32 when MDCONV_SAMPLING_F32 is ORed in, see above) */
+                     gradients: fp32 when MDCONV_SAMPLING_F32 is ORed in; grad_weight / grad_bias: fp32 when
+                     MDCONV_WGRAD_F32 is, see above) */
   int batch;      /* B */
   int c_in;       /* C_in  */
   int c_out;      /* C_out */

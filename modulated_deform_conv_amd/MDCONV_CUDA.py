@@ -128,6 +128,23 @@ def _check_dtypes(d, input, offset, mask, **tensors):
     d.dtype |= _capi.SAMPLING_F32
 
 
+def _wgrad_f32(d, input, grad_weight, grad_bias, with_bias):
+    """fp16 / bf16 tensors with fp32 `grad_weight` (and `grad_bias`, where the call has one): "fp32 weight gradients"
+    (include/mdconv.h: MDCONV_WGRAD_F32) -- sets the bit in the descriptor and returns True.  One fp32 and one 16-bit
+    tensor of the pair is refused, like any other mix of dtypes."""
+    if input.dtype not in (torch.float16, torch.bfloat16):
+        return False
+    has_bias = with_bias and grad_bias is not None and grad_bias.numel() > 0
+    if grad_weight.dtype != torch.float32 and not (has_bias and grad_bias.dtype == torch.float32):
+        return False
+    for name, g in (("grad_weight", grad_weight),) + ((("grad_bias", grad_bias),) if has_bias else ()):
+        if g.dtype != torch.float32 or g.device != input.device:
+            raise RuntimeError("%s must be fp32 on the device of input when the other weight gradient is fp32 "
+                               "(fp32 weight gradients), got %s/%s" % (name, g.dtype, g.device))
+    d.dtype |= _capi.WGRAD_F32
+    return True
+
+
 def _same(ref, **tensors):
     for name, t in tensors.items():
         if t is None or t.numel() == 0:
@@ -245,9 +262,10 @@ def deform_conv2d_backward_cuda(input, weight, bias, offset, grad_input, grad_we
 
 def _backward_checks(input, weight, offset, mask, grad_input, grad_weight, grad_bias, grad_offset,
                      grad_mask, grad_output, d, with_bias):
-    _check_dtypes(d, input, offset, mask, weight=weight, grad_input=grad_input,
-                  grad_weight=grad_weight, grad_offset=grad_offset, grad_mask=grad_mask,
-                  grad_output=grad_output, grad_bias=grad_bias if with_bias else None)
+    wgrads = {} if _wgrad_f32(d, input, grad_weight, grad_bias, with_bias) else dict(
+        grad_weight=grad_weight, grad_bias=grad_bias if with_bias else None)
+    _check_dtypes(d, input, offset, mask, weight=weight, grad_input=grad_input, grad_offset=grad_offset,
+                  grad_mask=grad_mask, grad_output=grad_output, **wgrads)
     for name, g, ref in (("grad_input", grad_input, input), ("grad_weight", grad_weight, weight),
                          ("grad_offset", grad_offset, offset), ("grad_mask", grad_mask, mask)):
         if ref is not None and g.numel() != ref.numel():
@@ -294,7 +312,9 @@ def _modulated2d_backward(fused, input, weight, bias, offset, mask, grad_output,
     grad_mask = torch.empty_like(mask)
     # grad_weight || grad_bias live in ONE flat buffer: the data-parallel exchange is then a single in-place all-reduce
     # (distributed.py: fused_grad_buffers / FusedGradAllReduce)
-    grad_weight, grad_bias = fused_grad_buffers(weight, bias) if fused else (torch.empty_like(weight), torch.empty_like(bias))
+    # (inside _capi.weight_grads_f32(): fp32 for 16-bit tensors -- the unrounded sums, reduced in place by the exchange)
+    wdt = torch.float32 if _capi.weight_grads_f32_mode() and input.dtype in (torch.float16, torch.bfloat16) else None
+    grad_weight, grad_bias = fused_grad_buffers(weight, bias, wdt) if fused else (torch.empty_like(weight), torch.empty_like(bias))
     _backward_checks(input, weight, offset, mask, grad_input, grad_weight, grad_bias, grad_offset,
                      grad_mask, grad_output, d, with_bias)
     d.accumulate = 0

@@ -12,6 +12,7 @@ LIB_PATH = os.environ.get("MDCONV_LIB") or os.path.join(HERE, "libmdconv_hip.so"
 
 F32, F16, F64, BF16 = 0, 1, 2, 3
 SAMPLING_F32 = 0x10   # MDCONV_SAMPLING_F32: ORed into F16 / BF16, offset / mask and their gradients are fp32
+WGRAD_F32 = 0x40      # MDCONV_WGRAD_F32: ORed into F16 / BF16, the backward's grad_weight / grad_bias are fp32
 PATH_AUTO, PATH_DIRECT, PATH_MFMA = 0, 1, 2
 ABI_VERSION = 2
 DESC_V2 = 0x100   # MDCONV_DESC_V2: the descriptor carries accumulate / input_layout / path
@@ -174,6 +175,34 @@ class deterministic:
 
     def __exit__(self, *exc):
         _modes.deterministic = self._prev
+        return False
+
+
+def weight_grads_f32_mode():
+    """True inside a ``weight_grads_f32`` context manager of this thread (innermost one: its ``on``), else False."""
+    return bool(getattr(_modes, "weight_grads_f32", False))
+
+
+class weight_grads_f32:
+    """Context manager: fp16 / bf16 backwards issued inside by this thread hand back fp32 weight and bias gradients
+    (``MDCONV_WGRAD_F32``, include/mdconv.h) wherever this package allocates them: the fp32 sums every 16-bit backward
+    holds, without the final rounding to 16 bits.  ``MDCONV_CUDA.modulated_deform_conv2d_backward_cuda`` returns fp32
+    ``grad_weight`` / ``grad_bias``; the autograd Functions called inside with 16-bit data and fp32 ``weight`` (AMP with
+    fp32 master weights) cast the parameters themselves and return the unrounded gradients.  The caller-allocated entry
+    points need no context: they take the mode from the dtype of the ``grad_weight`` they are handed.  ``on=False``
+    switches the mode off inside an outer block.  Thread-local, nests, and travels in each call's descriptor like
+    ``overwrite_grads``."""
+
+    def __init__(self, on=True):
+        self._on = bool(on)
+
+    def __enter__(self):
+        self._prev = weight_grads_f32_mode()
+        _modes.weight_grads_f32 = self._on
+        return self
+
+    def __exit__(self, *exc):
+        _modes.weight_grads_f32 = self._prev
         return False
 
 

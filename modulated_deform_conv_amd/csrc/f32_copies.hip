@@ -33,6 +33,7 @@ int direct16_backward(const Geom &g, int dtype, const D16Plan &p, const Tensors 
   if ((rc = widen(dtype, t.grad_output, (float *)(base + p.off_go), n_go, stream))) return rc;
   if ((rc = zero_bytes(base + p.off_gi, p.total - p.off_gi, stream))) return rc;   // the five gradient buffers are contiguous
   Tensors tc = t;
+  tc.wgrad32 = 0;   // every tensor of the inner call is fp32
   tc.input = base + p.off_x; tc.offset = base + p.off_off; tc.mask = t.mask ? base + p.off_m : nullptr;
   tc.weight = base + p.off_w; tc.grad_output = base + p.off_go;
   tc.grad_input = base + p.off_gi; tc.grad_offset = base + p.off_goff;
@@ -44,8 +45,8 @@ int direct16_backward(const Geom &g, int dtype, const D16Plan &p, const Tensors 
   if ((rc = narrow(dtype, (const float *)tc.grad_input, t.grad_input, n_x, g.acc_data != 0, stream))) return rc;
   if ((rc = narrow(dtype, (const float *)tc.grad_offset, t.grad_offset, n_off, g.acc_data != 0, stream))) return rc;
   if (t.grad_mask && (rc = narrow(dtype, (const float *)tc.grad_mask, t.grad_mask, n_m, g.acc_data != 0, stream))) return rc;
-  if ((rc = narrow(dtype, (const float *)tc.grad_weight, t.grad_weight, n_w, g.acc_w != 0, stream))) return rc;
-  if (g.with_bias && (rc = narrow(dtype, (const float *)tc.grad_bias, t.grad_bias, g.O, g.acc_w != 0, stream))) return rc;
+  if ((rc = narrow_wgrad(dtype, t, (const float *)tc.grad_weight, t.grad_weight, n_w, g.acc_w != 0, stream))) return rc;
+  if (g.with_bias && (rc = narrow_wgrad(dtype, t, (const float *)tc.grad_bias, t.grad_bias, g.O, g.acc_w != 0, stream))) return rc;
   return MDCONV_OK;
 }
 
@@ -101,7 +102,10 @@ int samp32_backward(const Geom &g, int dtype, const S32Plan &p, const Tensors &t
     if (rc) return rc;
   }
   if (g.acc_w || !mfma) {
-    if (g.acc_w) {
+    if (g.acc_w && t.wgrad32) {   // fp32 grad_weight / grad_bias: the caller's values as they are, not through 16 bits
+      if ((rc = store_f32((const float *)t.grad_weight, gw, n_w, false, stream))) return rc;
+      if (g.with_bias && (rc = store_f32((const float *)t.grad_bias, gb, g.O, false, stream))) return rc;
+    } else if (g.acc_w) {
       if ((rc = widen(dtype, t.grad_weight, gw, n_w, stream))) return rc;
       if (g.with_bias && (rc = widen(dtype, t.grad_bias, gb, g.O, stream))) return rc;
     } else if ((rc = zero_bytes(gw, (size_t)(n_w + g.O) * 4, stream))) {
@@ -113,7 +117,7 @@ int samp32_backward(const Geom &g, int dtype, const S32Plan &p, const Tensors &t
     if (t.grad_mask && (rc = zero_bytes(t.grad_mask, (size_t)n_m * 4, stream))) return rc;
   }
   Tensors tc = t;
-  tc.samp32 = 0;   // every tensor of the inner call is fp32
+  tc.samp32 = tc.wgrad32 = 0;   // every tensor of the inner call is fp32
   tc.input = base + p.off_x; tc.weight = base + p.off_w; tc.grad_output = base + p.off_o;
   tc.bias = nullptr;   // (the backward reads no bias)
   tc.grad_input = gi; tc.grad_weight = gw; tc.grad_bias = g.with_bias ? gb : nullptr;
@@ -123,8 +127,8 @@ int samp32_backward(const Geom &g, int dtype, const S32Plan &p, const Tensors &t
   if (rc) return rc;
   // grad_weight / grad_bias first: the weights-ready event (mdconv_stream_wait_weight_ready) is recorded again once they
   // are in the caller's buffers
-  if ((rc = narrow(dtype, gw, t.grad_weight, n_w, false, stream))) return rc;
-  if (g.with_bias && (rc = narrow(dtype, gb, t.grad_bias, g.O, false, stream))) return rc;
+  if ((rc = narrow_wgrad(dtype, t, gw, t.grad_weight, n_w, false, stream))) return rc;
+  if (g.with_bias && (rc = narrow_wgrad(dtype, t, gb, t.grad_bias, g.O, false, stream))) return rc;
   if ((rc = record_weight_ready(stream))) return rc;
   return narrow(dtype, gi, t.grad_input, n_x, false, stream);
 }

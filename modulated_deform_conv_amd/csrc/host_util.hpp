@@ -38,6 +38,12 @@ inline size_t chunk_limit(size_t ceiling) {
 // fp16 / bf16 <-> fp32 (`accum`: add to the 16-bit destination)
 int widen(int dtype, const void *src, float *dst, int64_t n, hipStream_t s);
 int narrow(int dtype, const float *src, void *dst, int64_t n, bool accum, hipStream_t s);
+// the fp32-destination twin of narrow (MDCONV_WGRAD_F32): dst = src, or dst += src with `accum` -- nothing is rounded
+int store_f32(const float *src, float *dst, int64_t n, bool accum, hipStream_t s);
+// grad_weight / grad_bias of a 16-bit call on their way out of an fp32 buffer: rounded once, or kept fp32 (t.wgrad32)
+inline int narrow_wgrad(int dtype, const Tensors &t, const float *src, void *dst, int64_t n, bool accum, hipStream_t s) {
+  return t.wgrad32 ? store_f32(src, (float *)dst, n, accum, s) : narrow(dtype, src, dst, n, accum, s);
+}
 // strided row copy; pitches and widths in bytes, multiples of 2
 int copy_rows(void *dst, size_t dpitch, const void *src, size_t spitch, size_t width, size_t rows, hipStream_t stream);
 // dst[r][0 .. dwidth) = src[r][0 .. width) followed by zeros

@@ -393,7 +393,7 @@ int hp_backward(const Geom &gcall, int dtype, const Tensors &t, void *ws, hipStr
   int rc;
   if ((rc = hp_pack_bwd_weights(g0, hd0, dtype, t.weight, base + L.off_w, (int4 *)(base + L.off_tab), stream)))
     return rc;
-  if (g.with_bias && (rc = hp_grad_bias(g, dtype, t.grad_output, t.grad_bias, stream))) return rc;
+  if (g.with_bias && (rc = hp_grad_bias(g, dtype, t.grad_output, t.grad_bias, t.wgrad32 != 0, stream))) return rc;
   for (int b0 = 0; b0 < g.B; b0 += Bc) {
     const int bc = g.B - b0 < Bc ? g.B - b0 : Bc;
     Geom gc = chunk_geom(g, bc);
@@ -448,7 +448,7 @@ int hp_backward(const Geom &gcall, int dtype, const Tensors &t, void *ws, hipStr
         if (r) return r;
       }
       if ((r = hp_reduce_grad_weight(gc, hd, bwd3 ? hd.ranges_w : hd.ranges, dtype, (const float *)(base + L.off_part),
-                                     (const int4 *)(base + L.off_tab), t.grad_weight,
+                                     (const int4 *)(base + L.off_tab), t.grad_weight, t.wgrad32 != 0,
                                      multi ? (float *)(base + L.off_gw32) : nullptr, first, last, stream)))
         return r;
       return last ? record_weight_ready(stream) : MDCONV_OK;

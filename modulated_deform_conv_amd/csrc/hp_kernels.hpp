@@ -21,10 +21,11 @@ int hp_pack_bwd_weights(const Geom &g, const HpDims &hd, int dtype, const void *
                         int4 *btab, hipStream_t stream);
 // gw32 != nullptr (calls cut into batch chunks): running fp32 sum; grad_weight is written by the last chunk
 // `ranges` = pixel ranges per tap in `part` (hd.ranges_w after hp_gemm2, hd.ranges after hp_bwd)
+// `wgrad32`: grad_weight / grad_bias are fp32 buffers and receive the fp32 sums (Tensors::wgrad32)
 int hp_reduce_grad_weight(const Geom &g, const HpDims &hd, int ranges, int dtype, const float *part,
-                          const int4 *btab, void *grad_weight, float *gw32, bool first, bool last,
+                          const int4 *btab, void *grad_weight, bool wgrad32, float *gw32, bool first, bool last,
                           hipStream_t stream);
-int hp_grad_bias(const Geom &g, int dtype, const void *grad_output, void *grad_bias,
+int hp_grad_bias(const Geom &g, int dtype, const void *grad_output, void *grad_bias, bool wgrad32,
                  hipStream_t stream);
 
 // hp_fwd.hip

@@ -222,12 +222,19 @@ __device__ __forceinline__ int4 hp_btab_entry(const Geom &g, int cblk) {
   return make_int4(base, (o_hi - base + 31) / 32, 0, 0);
 }
 
+// fp32 grad_weight / grad_bias (MDCONV_WGRAD_F32): the output type of the two kernels below that keeps the fp32 sum
+struct OutF32 {
+  using Raw = float;
+  static __device__ __forceinline__ float ldf(const Raw *p) { return *p; }
+  static __device__ __forceinline__ void stf(Raw *p, float v) { *p = v; }
+};
+
 // grad_weight[o][c][tap] (+)= sum over the pixel ranges of part[tap][range][cblk][ob][lane][16]
-// (the 32x32 fp32 accumulator blocks of the fused backward kernel, D[i = o][j = c])
-template <typename T>
+// (the 32x32 fp32 accumulator blocks of the fused backward kernel, D[i = o][j = c]); OUT = the type it is stored in
+template <typename T, typename OUT = T>
 __global__ __launch_bounds__(256) void hp_reduce_gw_kernel(Geom g, HpDims hd, int ranges, const int4 *__restrict__ btab,
                                                            const float *__restrict__ part,
-                                                           typename T::Raw *__restrict__ gw,
+                                                           typename OUT::Raw *__restrict__ gw,
                                                            float *__restrict__ gw32, int first, int last) {
   const int64_t total = (int64_t)g.K * hd.cblks * hd.MB2 * 1024;
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
@@ -258,8 +265,8 @@ __global__ __launch_bounds__(256) void hp_reduce_gw_kernel(Geom g, HpDims hd, in
         if (!first) s += gw32[e];
         if (!last) { gw32[e] = s; continue; }
       }
-      typename T::Raw *dst = gw + e;
-      T::stf(dst, g.acc_w ? T::ldf(dst) + s : s);
+      typename OUT::Raw *dst = gw + e;
+      OUT::stf(dst, g.acc_w ? OUT::ldf(dst) + s : s);
     }
   }
 }
@@ -274,9 +281,9 @@ __device__ __forceinline__ float sum8(const U4 &v) {
   return ((T::lo(v.x) + T::hi(v.x)) + (T::lo(v.y) + T::hi(v.y))) + ((T::lo(v.z) + T::hi(v.z)) + (T::lo(v.w) + T::hi(v.w)));
 }
 constexpr int kBiasThreads = 1024;
-template <typename T>
+template <typename T, typename OUT = T>
 __global__ __launch_bounds__(kBiasThreads) void hp_grad_bias_kernel(Geom g, const typename T::Raw *__restrict__ go,
-                                                                    typename T::Raw *__restrict__ gb) {
+                                                                    typename OUT::Raw *__restrict__ gb) {
   __shared__ float red[kBiasThreads];
   const int o = blockIdx.x, tid = threadIdx.x;
   float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
@@ -305,7 +312,7 @@ __global__ __launch_bounds__(kBiasThreads) void hp_grad_bias_kernel(Geom g, cons
     if (tid < d) red[tid] += red[tid + d];
     __syncthreads();
   }
-  if (tid == 0) T::stf(gb + o, g.acc_w ? T::ldf(gb + o) + red[0] : red[0]);
+  if (tid == 0) OUT::stf(gb + o, g.acc_w ? OUT::ldf(gb + o) + red[0] : red[0]);
 }
 
 }  // namespace
@@ -341,10 +348,13 @@ int hp_pack_bwd_weights(const Geom &g, const HpDims &hd, int dtype, const void *
 }
 
 int hp_reduce_grad_weight(const Geom &g, const HpDims &hd, int ranges, int dtype, const float *part,
-                          const int4 *btab, void *grad_weight, float *gw32, bool first, bool last,
+                          const int4 *btab, void *grad_weight, bool wgrad32, float *gw32, bool first, bool last,
                           hipStream_t stream) {
   const int64_t total = (int64_t)g.K * hd.cblks * hd.MB2 * 1024;
-  if (dtype == MDCONV_F16)
+  if (wgrad32)   // (the kernel reads fp32 partials whatever the tensors' type: one instance)
+    hipLaunchKernelGGL((hp_reduce_gw_kernel<F16, OutF32>), dim3(grid_for(total)), dim3(256), 0, stream, g, hd,
+                       ranges, btab, part, (float *)grad_weight, gw32, first ? 1 : 0, last ? 1 : 0);
+  else if (dtype == MDCONV_F16)
     hipLaunchKernelGGL((hp_reduce_gw_kernel<F16>), dim3(grid_for(total)), dim3(256), 0, stream, g, hd,
                        ranges, btab, part, (_Float16 *)grad_weight, gw32, first ? 1 : 0, last ? 1 : 0);
   else
@@ -353,9 +363,15 @@ int hp_reduce_grad_weight(const Geom &g, const HpDims &hd, int ranges, int dtype
   return check_launch("hp_reduce_gw");
 }
 
-int hp_grad_bias(const Geom &g, int dtype, const void *grad_output, void *grad_bias,
+int hp_grad_bias(const Geom &g, int dtype, const void *grad_output, void *grad_bias, bool wgrad32,
                  hipStream_t stream) {
-  if (dtype == MDCONV_F16)
+  if (wgrad32 && dtype == MDCONV_F16)
+    hipLaunchKernelGGL((hp_grad_bias_kernel<F16, OutF32>), dim3(g.O), dim3(kBiasThreads), 0, stream, g,
+                       (const _Float16 *)grad_output, (float *)grad_bias);
+  else if (wgrad32)
+    hipLaunchKernelGGL((hp_grad_bias_kernel<BF16, OutF32>), dim3(g.O), dim3(kBiasThreads), 0, stream, g,
+                       (const __bf16 *)grad_output, (float *)grad_bias);
+  else if (dtype == MDCONV_F16)
     hipLaunchKernelGGL((hp_grad_bias_kernel<F16>), dim3(g.O), dim3(kBiasThreads), 0, stream, g,
                        (const _Float16 *)grad_output, (_Float16 *)grad_bias);
   else

@@ -112,13 +112,17 @@ int fill_geom(const mdconv_desc *d, Geom *g) {
     set_error("ndim must be 2 or 3 (got %d)", ndim);
     return MDCONV_EINVAL;
   }
-  const int dt = d->dtype & ~MDCONV_SAMPLING_F32;
+  const int dt = d->dtype & ~(MDCONV_SAMPLING_F32 | MDCONV_WGRAD_F32);
   if (dt != MDCONV_F32 && dt != MDCONV_F16 && dt != MDCONV_F64 && dt != MDCONV_BF16) {
     set_error("unsupported dtype %d", d->dtype);
     return MDCONV_EINVAL;
   }
   if ((d->dtype & MDCONV_SAMPLING_F32) && dt != MDCONV_F16 && dt != MDCONV_BF16) {
     set_error("MDCONV_SAMPLING_F32 needs fp16 or bf16 tensors, dtype is %s", dt == MDCONV_F32 ? "MDCONV_F32" : "MDCONV_F64");
+    return MDCONV_EINVAL;
+  }
+  if ((d->dtype & MDCONV_WGRAD_F32) && dt != MDCONV_F16 && dt != MDCONV_BF16) {
+    set_error("MDCONV_WGRAD_F32 needs fp16 or bf16 tensors, dtype is %s", dt == MDCONV_F32 ? "MDCONV_F32" : "MDCONV_F64");
     return MDCONV_EINVAL;
   }
   if (d->batch <= 0 || d->c_in <= 0 || d->c_out <= 0 || d->groups <= 0 || d->dgroups <= 0) {
@@ -220,9 +224,11 @@ static int require(const void *p, const char *name) {
   return MDCONV_OK;
 }
 
-// element type of the call's tensors (MDCONV_SAMPLING_F32 stripped) and whether offset / mask are fp32
-static int base_dtype(const mdconv_desc *d) { return d->dtype & ~MDCONV_SAMPLING_F32; }
+// element type of the call's tensors (the dtype flags stripped), whether offset / mask are fp32, and whether a backward's
+// grad_weight / grad_bias are (the forward ignores that bit: one descriptor serves both directions)
+static int base_dtype(const mdconv_desc *d) { return d->dtype & ~(MDCONV_SAMPLING_F32 | MDCONV_WGRAD_F32); }
 static int sampling_f32(const mdconv_desc *d) { return (d->dtype & MDCONV_SAMPLING_F32) ? 1 : 0; }
+static int wgrad_f32(const mdconv_desc *d, bool backward) { return backward && (d->dtype & MDCONV_WGRAD_F32) ? 1 : 0; }
 
 // ---------------------------------------------------------------------------------------------
 // The plan of one call: the kernel family it runs on, the copies it runs through and its workspace -- the one routing
@@ -251,7 +257,9 @@ struct CallPlan {
 static bool route_is_direct(Route r) { return r == ROUTE_DIRECT || r == ROUTE_DIRECT_16 || r == ROUTE_DIRECT_SAMP32; }
 
 // `g` with in_cl and det set; `dt` the tensors' element type, `s32` fp32 offsets / masks, `path` the caller's MDCONV_PATH_*.
-static void plan_call(const Geom &g, int dt, int s32, int path, bool backward, CallPlan *cp) {
+// `wg32` (fp32 grad_weight / grad_bias of a 16-bit backward) never changes the route: only the fp32 matrix family's padded /
+// sliced plans hold grad_weight rows in the caller's element size, and size them for it.
+static void plan_call(const Geom &g, int dt, int s32, int wg32, int path, bool backward, CallPlan *cp) {
   const bool half = dt == MDCONV_F16 || dt == MDCONV_BF16;
   const bool hp = path != MDCONV_PATH_DIRECT && hp_supported(g, dt, backward);
   cp->refused = g.in_cl && !(hp && g.C % 32 == 0) ? REFUSE_CHANNELS_LAST : REFUSE_NONE;
@@ -270,7 +278,7 @@ static void plan_call(const Geom &g, int dt, int s32, int path, bool backward, C
     if (s32) {
       if (mfma_supported(g, dt, backward)) samp32_plan(g, backward, true, &cp->s32), mfma = cp->s32.mfma;
     } else {
-      mfma = mfma_plan(g, dt, backward, &cp->f32);
+      mfma = mfma_plan(g, dt, backward, &cp->f32, wg32 != 0);
     }
   }
   if (mfma) {
@@ -367,7 +375,7 @@ static int run_forward(const mdconv_desc *d, int nd, int modulated, Tensors t, v
   t.samp32 = s32;
   g.in_cl = md.input_layout == MDCONV_LAYOUT_CHANNELS_LAST ? 1 : 0;
   CallPlan cp;
-  plan_call(g, dt, s32, path, false, &cp);
+  plan_call(g, dt, s32, 0, path, false, &cp);
   if (cp.refused) return refuse(cp, g, dt, path);
   switch (cp.route) {
     case ROUTE_HP:
@@ -418,10 +426,11 @@ static int run_backward(const mdconv_desc *d, int nd, int modulated, Tensors t, 
   const int path = md.path;
   const int dt = base_dtype(d), s32 = sampling_f32(d);
   t.samp32 = s32;
+  t.wgrad32 = wgrad_f32(d, true);
   g.in_cl = md.input_layout == MDCONV_LAYOUT_CHANNELS_LAST ? 1 : 0;
   g.det = md.deterministic;
   CallPlan cp;
-  plan_call(g, dt, s32, path, true, &cp);
+  plan_call(g, dt, s32, t.wgrad32, path, true, &cp);
   if (cp.refused) return refuse(cp, g, dt, path);
   if (cp.route == ROUTE_HP) {
     if ((rc = check_ws(ws, ws_bytes, cp.bytes))) return rc;
@@ -544,7 +553,7 @@ size_t mdconv_workspace_bytes(const mdconv_desc *d, int backward) {
   g.in_cl = md.input_layout == MDCONV_LAYOUT_CHANNELS_LAST ? 1 : 0;   // (the plan of a channels-last call, where the caller says so)
   g.det = backward ? md.deterministic : 0;   // the list sort's scratch (backward on the matrix-core kernels only)
   CallPlan cp;
-  plan_call(g, base_dtype(d), sampling_f32(d), md.path, backward != 0, &cp);
+  plan_call(g, base_dtype(d), sampling_f32(d), wgrad_f32(d, backward != 0), md.path, backward != 0, &cp);
   return cp.reported;
 }
 
@@ -562,7 +571,7 @@ int mdconv_input_layout_supported(const mdconv_desc *d, int layout, int backward
   if (layout != MDCONV_LAYOUT_CHANNELS_LAST) return 0;
   g.in_cl = 1;   // the plan of a channels-last call (the group-padded layout needs the library's own input copy)
   CallPlan cp;
-  plan_call(g, base_dtype(d), sampling_f32(d), md.path, backward != 0, &cp);
+  plan_call(g, base_dtype(d), sampling_f32(d), wgrad_f32(d, backward != 0), md.path, backward != 0, &cp);
   return cp.refused != REFUSE_CHANNELS_LAST;
 }
 
@@ -574,7 +583,7 @@ int mdconv_deterministic_supported(const mdconv_desc *d, int backward) {
   g.in_cl = md.input_layout == MDCONV_LAYOUT_CHANNELS_LAST ? 1 : 0;
   g.det = 1;
   CallPlan cp;
-  plan_call(g, base_dtype(d), sampling_f32(d), md.path, true, &cp);
+  plan_call(g, base_dtype(d), sampling_f32(d), wgrad_f32(d, true), md.path, true, &cp);
   if (!route_is_direct(cp.route)) return 1;
   set_det_refusal(g, base_dtype(d), md.path);   // the reason, for mdconv_last_error()
   return 0;

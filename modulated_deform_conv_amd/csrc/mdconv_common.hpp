@@ -428,10 +428,17 @@ struct Tensors {
   void *output, *grad_input, *grad_weight, *grad_bias, *grad_offset, *grad_mask;
   // 1 = offset / mask / grad_offset / grad_mask are fp32 while the other tensors are 16-bit (MDCONV_SAMPLING_F32)
   int samp32;
+  // 1 = grad_weight / grad_bias are fp32 while the other tensors are 16-bit (MDCONV_WGRAD_F32): the fp32 sums, not rounded
+  int wgrad32;
 };
 // bytes of one offset / mask element of a call
 inline size_t samp_bytes(int dtype, const Tensors &t) {
   return t.samp32 ? 4 : (dtype == MDCONV_F64 ? 8 : (dtype == MDCONV_F32 ? 4 : 2));
+}
+
+// bytes of one grad_weight / grad_bias element of a call
+inline size_t wgrad_bytes(int dtype, const Tensors &t) {
+  return t.wgrad32 ? 4 : (dtype == MDCONV_F64 ? 8 : (dtype == MDCONV_F32 ? 4 : 2));
 }
 
 // direct (VALU) path, any shape / dtype

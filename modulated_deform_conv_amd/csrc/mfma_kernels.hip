@@ -531,8 +531,10 @@ int native_backward(const Geom &g, int dtype, const Plan &p, const Tensors &t, v
     }
   }
   if (p.half_io) {
-    if ((rc = narrow(dtype, (const float *)(base + p.off_gw), t.grad_weight, n_w, g.acc_w != 0, stream))) return rc;
-    if (g.with_bias && (rc = narrow(dtype, (const float *)(base + p.off_gb), t.grad_bias, g.O, g.acc_w != 0, stream))) return rc;
+    // (fp32 grad_weight / grad_bias, t.wgrad32: the sums as they are, copied or added)
+    if ((rc = narrow_wgrad(dtype, t, (const float *)(base + p.off_gw), t.grad_weight, n_w, g.acc_w != 0, stream))) return rc;
+    if (g.with_bias && (rc = narrow_wgrad(dtype, t, (const float *)(base + p.off_gb), t.grad_bias, g.O, g.acc_w != 0, stream)))
+      return rc;
     if ((rc = record_weight_ready(stream))) return rc;
   }
   return MDCONV_OK;

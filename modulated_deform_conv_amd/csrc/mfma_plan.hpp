@@ -64,8 +64,9 @@ struct MfmaPlan {
   SplitPlan split_bwd;
 };
 // Priority: padded where the padded problem is the faster one (pad_channels_preferred), native, padded, split.
-// false: the family does not run this shape / dtype.
-bool mfma_plan(const Geom &g, int dtype, bool backward, MfmaPlan *p);
+// false: the family does not run this shape / dtype.  `wgrad32` (a 16-bit backward with fp32 grad_weight / grad_bias,
+// MDCONV_WGRAD_F32) sizes the padded / sliced plans' grad_weight rows for 4-byte elements; it never changes the kind.
+bool mfma_plan(const Geom &g, int dtype, bool backward, MfmaPlan *p, bool wgrad32 = false);
 int mfma_forward(const Geom &g, int dtype, const MfmaPlan &p, const Tensors &t, void *ws, hipStream_t stream);
 int mfma_backward(const Geom &g, int dtype, const MfmaPlan &p, const Tensors &t, void *ws, hipStream_t stream);
 

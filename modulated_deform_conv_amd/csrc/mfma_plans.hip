@@ -35,7 +35,7 @@ bool split_slice_geom(const Geom &g, Geom *out, bool *copy_w, bool *copy_go) {
   *out = s;
   return true;
 }
-bool split_plan(const Geom &g, int dtype, SplitPlan *p) {
+bool split_plan(const Geom &g, int dtype, bool wgrad32, SplitPlan *p) {
   if (!split_slice_geom(g, &p->gs, &p->copy_w, &p->copy_go)) return false;
   // The slices' workspace is sized from the geometry the FIRST slice of a conv group runs with (split_backward): that
   // slice carries grad_bias and has the grad_bias stage buffer at the end of its layout -- sized without it, it wrote
@@ -46,6 +46,7 @@ bool split_plan(const Geom &g, int dtype, SplitPlan *p) {
   p->rest = p->first;
   if (first.with_bias && !native_plan(p->gs, dtype, true, &p->rest)) return false;
   const size_t es = dtype == MDCONV_F32 ? 4 : 2;
+  const size_t es_w = wgrad32 ? 4 : es;   // grad_weight rows (fp32 with MDCONV_WGRAD_F32)
   const Geom &s = p->gs;
   Bump ws;
   p->off_x = ws.take((size_t)g.B * s.C * g.S_i * es);
@@ -56,7 +57,7 @@ bool split_plan(const Geom &g, int dtype, SplitPlan *p) {
   p->off_gi = ws.take((size_t)g.B * s.C * g.S_i * es);
   p->off_goff = ws.take((size_t)g.B * g.nd * g.K * g.S_o * es);
   p->off_gm = ws.take(g.modulated ? (size_t)g.B * g.K * g.S_o * es : 0);
-  p->off_gw = ws.take(p->copy_w ? (size_t)s.O * s.Cg * g.K * es : 0);
+  p->off_gw = ws.take(p->copy_w ? (size_t)s.O * s.Cg * g.K * es_w : 0);
   p->off_sub = ws.off;
   p->total = ws.off + p->first.total;
   return true;
@@ -65,12 +66,14 @@ bool split_plan(const Geom &g, int dtype, SplitPlan *p) {
 int split_backward(const Geom &g, int dtype, const SplitPlan &p, const Tensors &t, void *ws, hipStream_t stream) {
   char *base = (char *)ws;
   const size_t es = dtype == MDCONV_F32 ? 4 : 2;
+  const size_t es_w = wgrad_bytes(dtype, t);   // grad_weight / grad_bias elements
   const Geom &s = p.gs;
   const size_t w_x = (size_t)s.C * g.S_i * es, p_x = (size_t)g.C * g.S_i * es;
   const size_t w_off = (size_t)g.nd * g.K * g.S_o * es, p_off = w_off * g.DG;
   const size_t w_m = (size_t)g.K * g.S_o * es, p_m = w_m * g.DG;
   const size_t w_go = (size_t)s.O * g.S_o * es, p_go = (size_t)g.O * g.S_o * es;
   const size_t w_w = (size_t)s.Cg * g.K * es, p_w = (size_t)g.Cg * g.K * es;
+  const size_t w_gw = (size_t)s.Cg * g.K * es_w, p_gw = (size_t)g.Cg * g.K * es_w;
   int rc;
   for (int dg = 0; dg < g.DG; ++dg) {
     const int c0 = dg * g.Cdg;            // first input channel of the slice
@@ -82,7 +85,7 @@ int split_backward(const Geom &g, int dtype, const SplitPlan &p, const Tensors &
     const char *src_off = (const char *)t.offset + (size_t)dg * w_off;
     char *dst_gi = (char *)t.grad_input + (size_t)c0 * g.S_i * es;
     char *dst_goff = (char *)t.grad_offset + (size_t)dg * w_off;
-    char *dst_gw = (char *)t.grad_weight + ((size_t)o0 * g.Cg + cw) * g.K * es;
+    char *dst_gw = (char *)t.grad_weight + ((size_t)o0 * g.Cg + cw) * g.K * es_w;
     if ((rc = copy_rows(base + p.off_x, w_x, src_x, p_x, w_x, g.B, stream))) return rc;
     if ((rc = copy_rows(base + p.off_off, w_off, src_off, p_off, w_off, g.B, stream))) return rc;
     ts.input = base + p.off_x; ts.offset = base + p.off_off;
@@ -106,7 +109,7 @@ int split_backward(const Geom &g, int dtype, const SplitPlan &p, const Tensors &
     // grad_bias belongs to the output channels: once per conv group, with the first slice that touches it
     gs.with_bias = g.with_bias && cw == 0 ? 1 : 0;
     ts.bias = nullptr;
-    ts.grad_bias = gs.with_bias ? (char *)t.grad_bias + (size_t)o0 * es : nullptr;
+    ts.grad_bias = gs.with_bias ? (char *)t.grad_bias + (size_t)o0 * es_w : nullptr;
     if (g.acc_data) {   // accumulate mode: the slice starts from the caller's values
       if ((rc = copy_rows(base + p.off_gi, w_x, dst_gi, p_x, w_x, g.B, stream))) return rc;
       if ((rc = copy_rows(base + p.off_goff, w_off, dst_goff, p_off, w_off, g.B, stream))) return rc;
@@ -114,14 +117,14 @@ int split_backward(const Geom &g, int dtype, const SplitPlan &p, const Tensors &
           (rc = copy_rows(base + p.off_gm, w_m, (const char *)t.grad_mask + (size_t)dg * w_m, p_m, w_m, g.B, stream)))
         return rc;
     }
-    if (g.acc_w && p.copy_w && (rc = copy_rows(base + p.off_gw, w_w, dst_gw, p_w, w_w, s.O, stream))) return rc;
+    if (g.acc_w && p.copy_w && (rc = copy_rows(base + p.off_gw, w_gw, dst_gw, p_gw, w_gw, s.O, stream))) return rc;
     if ((rc = native_backward(gs, dtype, gs.with_bias ? p.first : p.rest, ts, base + p.off_sub, stream))) return rc;
     if ((rc = copy_rows(dst_gi, p_x, base + p.off_gi, w_x, w_x, g.B, stream))) return rc;
     if ((rc = copy_rows(dst_goff, p_off, base + p.off_goff, w_off, w_off, g.B, stream))) return rc;
     if (g.modulated &&
         (rc = copy_rows((char *)t.grad_mask + (size_t)dg * w_m, p_m, base + p.off_gm, w_m, w_m, g.B, stream)))
       return rc;
-    if (p.copy_w && (rc = copy_rows(dst_gw, p_w, base + p.off_gw, w_w, w_w, s.O, stream))) return rc;
+    if (p.copy_w && (rc = copy_rows(dst_gw, p_gw, base + p.off_gw, w_gw, w_gw, s.O, stream))) return rc;
   }
   return record_weight_ready(stream);   // after the last slice's copies
 }
@@ -273,7 +276,7 @@ int pad_group_channels(const Geom &g, bool backward, bool native_ok) {
   return backward ? cdp_b : cdp_f;
 }
 // native_ok: the kernels tile `g` itself
-bool pad_plan(const Geom &g, int dtype, bool backward, bool native_ok, PadPlan *p) {
+bool pad_plan(const Geom &g, int dtype, bool backward, bool native_ok, bool wgrad32, PadPlan *p) {
   if (dg_plan_env() == 2) return false;
   Geom gp = g;
   if (g.G == 1) {
@@ -331,14 +334,15 @@ bool pad_plan(const Geom &g, int dtype, bool backward, bool native_ok, PadPlan *
   if (!native_plan(gp, dtype, backward, &p->sub)) return false;
   p->gp = gp;
   const size_t es = dtype == MDCONV_F32 ? 4 : 2;
+  const size_t es_w = wgrad32 ? 4 : es;   // grad_weight / grad_bias (fp32 with MDCONV_WGRAD_F32)
   Bump ws;
   p->off_x = ws.take(p->pad_c ? (size_t)g.B * gp.C * g.S_i * es : 0);
   p->off_w = ws.take((size_t)gp.O * gp.Cg * g.K * es);
   p->off_gi = ws.take(backward && p->pad_c ? (size_t)g.B * gp.C * g.S_i * es : 0);
-  p->off_gw = ws.take(backward ? (size_t)gp.O * gp.Cg * g.K * es : 0);
+  p->off_gw = ws.take(backward ? (size_t)gp.O * gp.Cg * g.K * es_w : 0);
   p->off_o = ws.take(p->pad_o ? (size_t)g.B * gp.O * g.S_o * es : 0);
   p->off_b = ws.take(p->pad_o && g.with_bias && !backward ? (size_t)gp.O * es : 0);
-  p->off_gb = ws.take(p->pad_o && g.with_bias && backward ? (size_t)gp.O * es : 0);
+  p->off_gb = ws.take(p->pad_o && g.with_bias && backward ? (size_t)gp.O * es_w : 0);
   p->off_sub = ws.off;
   p->total = ws.off + p->sub.total;
   return true;
@@ -381,8 +385,9 @@ int pad_backward(const Geom &g, int dtype, const PadPlan &p, const Tensors &t, v
   char *base = (char *)ws;
   const size_t es = dtype == MDCONV_F32 ? 4 : 2;
   const size_t w_x = (size_t)p.cin * g.S_i * es, p_x = (size_t)p.cinp * g.S_i * es;
-  const size_t w_w = (size_t)p.cin * g.K * es, p_w = (size_t)p.cinp * g.K * es;
   const size_t w_o = (size_t)p.og * g.S_o * es, p_o = (size_t)p.ogp * g.S_o * es;
+  const size_t es_w = wgrad_bytes(dtype, t);   // grad_weight / grad_bias elements
+  const size_t w_gw = (size_t)p.cin * g.K * es_w, p_gw = (size_t)p.cinp * g.K * es_w;
   const size_t wi = (size_t)p.og * p.wsub, wip = (size_t)p.ogp * p.wsub;   // weight rows of one output group (caller's / padded)
   int rc;
   Tensors tp = t;   // grad_offset / grad_mask have no channel axis: written in place, in the caller's mode
@@ -392,38 +397,38 @@ int pad_backward(const Geom &g, int dtype, const PadPlan &p, const Tensors &t, v
     if (g.acc_data && (rc = pad_rows(base + p.off_gi, p_x, t.grad_input, w_x, (size_t)g.B * p.ng, stream))) return rc;
     tp.grad_input = base + p.off_gi;
   }
-  if (g.acc_w && (rc = pad_rows_grouped(base + p.off_gw, p_w, t.grad_weight, w_w, wi, wip, p.nog, stream))) return rc;
+  if (g.acc_w && (rc = pad_rows_grouped(base + p.off_gw, p_gw, t.grad_weight, w_gw, wi, wip, p.nog, stream))) return rc;
   tp.grad_weight = base + p.off_gw;
   if (p.pad_o) {
     if ((rc = pad_rows(base + p.off_o, p_o, t.grad_output, w_o, (size_t)g.B * p.nog, stream))) return rc;   // zero planes for the padding channels
     tp.grad_output = base + p.off_o;
     if (g.with_bias) {
-      if (g.acc_w && (rc = pad_rows(base + p.off_gb, (size_t)p.ogp * es, t.grad_bias, (size_t)p.og * es, p.nog, stream))) return rc;
+      if (g.acc_w && (rc = pad_rows(base + p.off_gb, (size_t)p.ogp * es_w, t.grad_bias, (size_t)p.og * es_w, p.nog, stream))) return rc;
       tp.grad_bias = base + p.off_gb;
     }
   }
   if ((rc = native_backward(p.gp, dtype, p.sub, tp, base + p.off_sub, stream))) return rc;
   if (p.pad_c && (rc = copy_rows(t.grad_input, w_x, base + p.off_gi, p_x, w_x, (size_t)g.B * p.ng, stream))) return rc;
-  if ((rc = unpad_rows_grouped(t.grad_weight, w_w, base + p.off_gw, p_w, wi, wip, p.nog, stream))) return rc;
+  if ((rc = unpad_rows_grouped(t.grad_weight, w_gw, base + p.off_gw, p_gw, wi, wip, p.nog, stream))) return rc;
   if (p.pad_o && g.with_bias &&
-      (rc = copy_rows(t.grad_bias, (size_t)p.og * es, base + p.off_gb, (size_t)p.ogp * es, (size_t)p.og * es, p.nog, stream)))
+      (rc = copy_rows(t.grad_bias, (size_t)p.og * es_w, base + p.off_gb, (size_t)p.ogp * es_w, (size_t)p.og * es_w, p.nog, stream)))
     return rc;
   return record_weight_ready(stream);   // after the copy back
 }
 }  // namespace
 
-bool mfma_plan(const Geom &g, int dtype, bool backward, MfmaPlan *p) {
+bool mfma_plan(const Geom &g, int dtype, bool backward, MfmaPlan *p, bool wgrad32) {
   p->backward = backward;
   const bool native_ok = native_plan(g, dtype, backward, &p->native);
   // the padded problem where it is the faster one (pad_channels_preferred), else native tiling, else padded, else slices
-  if ((pad_channels_preferred(g) || !native_ok) && pad_plan(g, dtype, backward, native_ok, &p->pad)) {
+  if ((pad_channels_preferred(g) || !native_ok) && pad_plan(g, dtype, backward, native_ok, wgrad32, &p->pad)) {
     p->kind = MfmaPlan::PADDED;
     p->total = p->pad.total;
   } else if (native_ok) {
     p->kind = MfmaPlan::NATIVE;
     p->total = p->native.total;
   } else if (backward) {
-    if (!split_plan(g, dtype, &p->split_bwd)) return false;
+    if (!split_plan(g, dtype, wgrad32, &p->split_bwd)) return false;
     p->kind = MfmaPlan::SPLIT_BWD;
     p->total = p->split_bwd.total;
   } else {

@@ -27,6 +27,11 @@ __global__ __launch_bounds__(256) void narrow_kernel(const float *__restrict__ s
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256)
     st(dst + i, ACCUM ? ld(dst + i) + src[i] : src[i]);
 }
+template <bool ACCUM>
+__global__ __launch_bounds__(256) void store_f32_kernel(const float *__restrict__ src, float *__restrict__ dst, int64_t n) {
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256)
+    dst[i] = ACCUM ? dst[i] + src[i] : src[i];
+}
 
 template <typename W>
 __global__ __launch_bounds__(256) void copy_rows_kernel(W *__restrict__ dst, int64_t dpitch, const W *__restrict__ src,
@@ -155,6 +160,12 @@ int narrow(int dtype, const float *src, void *dst, int64_t n, bool accum, hipStr
   if (dtype == MDCONV_BF16) narrow_t<bf16_t>(src, dst, n, accum, s);
   else narrow_t<__half>(src, dst, n, accum, s);
   return check_launch("narrow");
+}
+int store_f32(const float *src, float *dst, int64_t n, bool accum, hipStream_t s) {
+  if (n == 0) return MDCONV_OK;
+  if (accum) hipLaunchKernelGGL(store_f32_kernel<true>, grid_for(n, 16384), dim3(256), 0, s, src, dst, n);
+  else hipLaunchKernelGGL(store_f32_kernel<false>, grid_for(n, 16384), dim3(256), 0, s, src, dst, n);
+  return check_launch("store_f32");
 }
 
 int copy_rows(void *dst, size_t dpitch, const void *src, size_t spitch, size_t width, size_t rows, hipStream_t stream) {

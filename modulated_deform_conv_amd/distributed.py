@@ -35,14 +35,15 @@ def shard_batch(tensors, world_size=None, rank=None):
     return type(tensors)(cut(v) for v in tensors)
 
 
-def fused_grad_buffers(weight, bias=None):
-    """-> (grad_weight, grad_bias): views of ONE flat buffer [grad_weight || grad_bias] in the dtype of `weight`, so that
+def fused_grad_buffers(weight, bias=None, dtype=None):
+    """-> (grad_weight, grad_bias): views of ONE flat buffer [grad_weight || grad_bias] in the dtype of `weight` (or in
+    `dtype`: torch.float32 for the fp32 weight gradients of a 16-bit backward, MDCONV_WGRAD_F32), so that
     the data-parallel exchange is a single plain all-reduce of memory the backward wrote in place -- no staging copies, no
     grouped launch ("a fused fp32 buffer").  The bindings allocate their weight gradients this way
     (MDCONV_CUDA.modulated_deform_conv2d_backward_cuda, the autograd Functions, ops.py); `fused_view` finds the flat buffer
     again from the two views.  `grad_bias` is a 0-element view when `bias` is None or empty."""
     nb = 0 if bias is None else bias.numel()
-    flat = torch.empty(weight.numel() + nb, dtype=weight.dtype, device=weight.device)
+    flat = torch.empty(weight.numel() + nb, dtype=weight.dtype if dtype is None else dtype, device=weight.device)
     return flat[:weight.numel()].view(weight.shape), flat[weight.numel():]
 
 

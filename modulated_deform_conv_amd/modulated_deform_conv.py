@@ -79,6 +79,16 @@ def _make_function(nd, modulated, name):
             dt = torch.get_autocast_dtype("cuda")
             cast = lambda t: t if t is None or not t.is_floating_point() or t.dtype == dt else t.to(dt)
             input, offset, mask, weight, bias = (cast(t) for t in (input, offset, mask, weight, bias))
+        # fp32 weight gradients (_capi.weight_grads_f32, include/mdconv.h: MDCONV_WGRAD_F32): 16-bit data with fp32 parameters
+        # -- AMP with fp32 master weights.  The parameters are cast here, like above, and the backward hands their
+        # gradients back as the fp32 sums it holds instead of rounding them to 16 bits and widening them again.  (16-bit
+        # parameters: autograd wants the gradient in their dtype, the mode has no effect.)
+        ctx.wgrad32 = bool(_capi.weight_grads_f32_mode() and input.dtype in (torch.float16, torch.bfloat16)
+                           and ctx.in_dtypes[3] == torch.float32
+                           and (not ctx.with_bias or ctx.in_dtypes[4] == torch.float32))
+        if ctx.wgrad32:
+            weight = weight.to(input.dtype)
+            bias = bias.to(input.dtype)
         if needs_grad:
             saved = (input, offset, mask, weight, bias) if modulated else (input, offset, weight, bias)
             ctx.save_for_backward(*saved)
@@ -102,16 +112,21 @@ def _make_function(nd, modulated, name):
             input, offset, weight, bias = ctx.saved_tensors
             mask = None
         geo = _geometry(ctx, weight)
+        wdt = torch.float32 if ctx.wgrad32 else None
         if returns_tensors:
-            grad_input, grad_offset, grad_mask, grad_weight, grad_bias = bwd(
-                input, weight, bias, offset, mask, grad_output, *geo)
+            # (autograd runs this on its own thread: the mode recorded in forward is entered here)
+            with _capi.weight_grads_f32(ctx.wgrad32):
+                grad_input, grad_offset, grad_mask, grad_weight, grad_bias = bwd(
+                    input, weight, bias, offset, mask, grad_output, *geo)
         else:
             # the reference wrapper zero-fills and the entry points add (:53-56); here the buffers
             # are fresh, so the library is asked to write them instead (mdconv_set_accumulate)
             grad_input = torch.empty_like(input, memory_format=torch.contiguous_format)
             grad_offset = torch.empty_like(offset)
-            grad_weight, grad_bias = fused_grad_buffers(weight, bias)   # one flat buffer: one in-place all-reduce (distributed.py)
-            with _capi.overwrite_grads():
+            # one flat buffer: one in-place all-reduce (distributed.py); fp32 for fp32 weight gradients -- the entry points
+            # take the mode from the buffers' dtype
+            grad_weight, grad_bias = fused_grad_buffers(weight, bias, wdt)
+            with _capi.overwrite_grads(), _capi.weight_grads_f32(ctx.wgrad32):
                 if modulated:
                     grad_mask = torch.empty_like(mask)
                     bwd(input, weight, bias, offset, mask, grad_input, grad_weight, grad_bias,
@@ -173,6 +188,11 @@ class _DeformConvNd(nn.Module):
     sampling positions as exact as in fp32); for the ``*Pack`` modules the offset / mask branch runs in the dtype
     of its own weights (fp32 parameters: fp32) outside autocast.  Outside autocast the tensors go as they are.
 
+    ``weight_grad_dtype`` (keyword only): ``None`` (default) rounds ``weight.grad`` / ``bias.grad`` of a 16-bit backward to
+    16 bits before they are widened to the parameters' dtype.  ``torch.float32``: with fp32 parameters and 16-bit data
+    (autocast) the gradients are the fp32 sums the backward holds -- finite where the fp16 value overflows, all 24 bits for
+    fp32 master weights (``_capi.weight_grads_f32``).  No effect with 16-bit parameters or fp32 data.
+
     Deterministic mode: under ``torch.use_deterministic_algorithms(True)`` (or inside ``_capi.deterministic()``) forward and
     backward are bit-identical from call to call on one device and one build (the backward sorts its scatter lists before
     summing them; INTEGRATION.md, Reproducibility).  Shapes whose backward runs on the shape-generic kernels -- fp64 tensors,
@@ -184,11 +204,14 @@ class _DeformConvNd(nn.Module):
     _op = None
 
     def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, dilation=1,
-                 groups=1, deformable_groups=1, bias=False, in_step=64, *, sampling_dtype=None):
+                 groups=1, deformable_groups=1, bias=False, in_step=64, *, sampling_dtype=None, weight_grad_dtype=None):
         super().__init__()
         if sampling_dtype not in (None, torch.float32):
             raise ValueError("sampling_dtype must be None or torch.float32, got %s" % (sampling_dtype,))
+        if weight_grad_dtype not in (None, torch.float32):
+            raise ValueError("weight_grad_dtype must be None or torch.float32, got %s" % (weight_grad_dtype,))
         self.sampling_dtype = sampling_dtype
+        self.weight_grad_dtype = weight_grad_dtype
         assert in_channels % groups == 0, \
             'in_channels {} cannot be divisible by groups {}'.format(in_channels, groups)
         assert out_channels % groups == 0, \
@@ -219,14 +242,20 @@ class _DeformConvNd(nn.Module):
     def _conv(self, op, x, offset, mask=None):
         """op(x, offset, [mask,] weight, bias, ...), with fp32 sampling under autocast when the module asks for it:
         the casts happen here, differentiably, and the Function runs with autocast off, so it keeps the dtypes."""
+        wg32 = self.weight_grad_dtype is not None
+        mode = _capi.weight_grads_f32() if wg32 else contextlib.nullcontext()
         if not self._fp32_sampling():
             head = (x, offset) if mask is None else (x, offset, mask)
-            return op(*head, *self._conv_args())
+            with mode:
+                return op(*head, *self._conv_args())
         dt = torch.get_autocast_dtype("cuda")
         cast = lambda t, d: t if t is None or t.dtype == d else t.to(d)
         weight, bias = self.weight, self.bias
-        with torch.autocast("cuda", enabled=False):
-            x, weight, bias = cast(x, dt), cast(weight, dt), cast(bias, dt)
+        with torch.autocast("cuda", enabled=False), mode:
+            x = cast(x, dt)
+            # (fp32 weight gradients: fp32 parameters go through uncast, the Function casts them itself)
+            if not (wg32 and weight.dtype == torch.float32 and (bias is None or bias.dtype == torch.float32)):
+                weight, bias = cast(weight, dt), cast(bias, dt)
             head = (x, cast(offset, self.sampling_dtype))
             if mask is not None:
                 head += (cast(mask, self.sampling_dtype),)
