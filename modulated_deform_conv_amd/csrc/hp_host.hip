@@ -1,4 +1,4 @@
-// hp_host.hip -- dispatch, workspace layout and kernel sequence of the native 16-bit path.
+// hp_host.hip -- the planner (hp_plan.hpp) and the kernel sequence of the native 16-bit path.
 //
 // forward : pack weights -> channels-last input copy -> hp_fwd_kernel
 // backward: pack W^T -> channels-last input copy -> hp_bwd3_kernel (GEMM-1 + coordinate gradients +
@@ -8,11 +8,10 @@
 //           col2im gather
 // Calls whose channels-last copy would exceed 2 GiB (32-bit buffer offsets) are cut into batch
 // chunks; grad_weight accumulates across chunks.
-#include "hp_kernels.hpp"
+#include "hp_plan.hpp"
 
 #include <stdlib.h>
 
-#include "host_util.hpp"
 #include "mfma_kernels.hpp"
 
 namespace mdconv {
@@ -27,27 +26,39 @@ int pow2_ceil(int x) {
   return p;
 }
 
-bool hp_enabled() {
-  static const int on = getenv("MDCONV_HP") ? atoi(getenv("MDCONV_HP")) : 1;
-  return on != 0;
+// The family's environment switches, read once per process.
+struct HpSwitches {
+  bool enabled;          // MDCONV_HP (default 1): 0 -> the family takes no call
+  // MDCONV_HP_FWD = 2 (default) -> hp_fwd2 where its quad-contiguous gathers apply, else hp_fwd; 1 -> hp_fwd.  SET at all:
+  // the kernel is selected explicitly, so no forward is handed to the fp32 kernels (forward_preferred; the forced-path tests)
+  bool fwd_set;
+  int fwd;
+  // which backward kernel: MDCONV_HP_BWD = 1 -> hp_bwd (lane = pixel), 2 -> hp_bwd2 (fused, tap-stationary),
+  // 3 (default) -> hp_bwd3 + hp_gemm2 where the shape qualifies and is large enough to fill the chip (use_bwd3), else as 2;
+  // 4 -> hp_bwd3 wherever it is supported (the test suite's way to reach every instance with small shapes)
+  int bwd;
+  // grad_input gather: MDCONV_HP_C2I = 1 -> one pass (every row read 2^(nd-1) times), 2 (default) -> two passes
+  bool two_pass_gather;
+  bool blocked;          // MDCONV_HP_BLOCKED (default 1): 0 -> the pixel-stationary kernels' tiles in linear order everywhere
+};
+int env_int(const char *name, int dflt) { return getenv(name) ? atoi(getenv(name)) : dflt; }
+const HpSwitches &hp_switches() {
+  static const HpSwitches s = {env_int("MDCONV_HP", 1) != 0, getenv("MDCONV_HP_FWD") != nullptr, env_int("MDCONV_HP_FWD", 2),
+                               env_int("MDCONV_HP_BWD", 3), env_int("MDCONV_HP_C2I", 2) >= 2, env_int("MDCONV_HP_BLOCKED", 1) != 0};
+  return s;
 }
 
 constexpr size_t kHpChunkCeiling = 0x7e000000;   // below kHpOob
+constexpr int kHpWgPerCu8 = 2;   // workgroups per CU the fused backward kernel is sized for when it has 8 + 2 waves (C_in > 128)
 
-// which backward kernel: MDCONV_HP_BWD = 1 -> hp_bwd (lane = pixel), 2 -> hp_bwd2 (fused, tap-stationary),
-// 3 (default) -> hp_bwd3 + hp_gemm2 where the shape qualifies and is large enough to fill the chip (use_bwd3), else as 2;
-// 4 -> hp_bwd3 wherever it is supported (the test suite's way to reach every instance with small shapes)
-int bwd_version() {
-  static const int v = getenv("MDCONV_HP_BWD") ? atoi(getenv("MDCONV_HP_BWD")) : 3;
-  return v;
-}
 // hp_bwd2 instances that hold W^T[tap] and the grad_W[tap] accumulators without spilling (tools/kres.py hp_bwd2: 16 k-steps,
 // or 8 with the 8 + 2-wave workgroup, go to scratch) and shapes it takes at all (deformable groups of whole 32-channel blocks)
-static bool bwd2_takes(const Geom &g, const HpDims &hd) {
+// This is THE tap-stationary rule: use_bwd3 and the kernel choice of a chunk (bwd_kernel) both go through it.
+bool bwd2_takes(const Geom &g, const HpDims &hd) {
   if (g.DG > 4 || (g.DG > 1 && g.Cdg % 32)) return false;
   return hp_bwd2_lds_bytes(g, hd) <= 160 * 1024;
 }
-static bool bwd2_spills(const HpDims &hd) { return hd.nks >= 16 || (hd.waves >= 8 && hd.nks >= 8); }
+bool bwd2_spills(const HpDims &hd) { return hd.nks >= 16 || (hd.waves >= 8 && hd.nks >= 8); }
 // Pixel-stationary (hp_bwd3 + hp_gemm2) or tap-stationary (hp_bwd2)?  hp_bwd3's workgroup walks ALL taps of its 128 pixels -- a
 // grid of at most one workgroup per CU is one long latency chain per CU -- while hp_bwd2's grid is (tap, pixel range): parallel
 // over the taps.  Measured crossover (profiles/r06_experiments.md 9: 27 shapes, both kernels): up to ~one 128-pixel tile per CU
@@ -58,22 +69,18 @@ static bool bwd2_spills(const HpDims &hd) { return hd.nks >= 16 || (hd.waves >= 
 // 25-98 for 2-D 128 -> 256, beyond 49 for 3-D 128 -> 256 -- tiles <= CUs x 16 (36 in 3-D) / C_in.  (Round 6 first shipped
 // "(tile, tap) pairs <= CUs" from one data point: 3-D 256 -> 256 at 4 x 14 x 14, B = 2 went to hp_bwd3 at 0.88 ms against 0.56.)
 bool use_bwd3(const Geom &g, const HpDims &hd) {
-  if (bwd_version() < 3 || !hp_bwd3_supported(g, hd)) return false;
-  if (bwd_version() == 3 && bwd2_takes(g, hd)) {
+  const int version = hp_switches().bwd;
+  if (version < 3 || !hp_bwd3_supported(g, hd)) return false;
+  if (version == 3 && bwd2_takes(g, hd)) {
     const long tiles = (g.N + 127) / 128;
     const long limit = bwd2_spills(hd) ? (long)num_cus() * (g.nd == 3 ? 36 : 16) / hd.Cp : num_cus();
     if (tiles <= limit) return false;
   }
   return true;
 }
-
-struct FwdLayout { size_t off_xt, off_w, off_tab, total; };
-struct BwdLayout { size_t off_xt, off_w, off_tab, off_gcol, off_col, off_part, off_gw32, off_cnt, off_rowptr, off_entries, off_sums, off_sort, total; };
-
-// grad_input gather: MDCONV_HP_C2I = 1 -> one pass (every row read 2^(nd-1) times), 2 (default) -> two passes
-bool use_col2im2() {
-  static const int v = getenv("MDCONV_HP_C2I") ? atoi(getenv("MDCONV_HP_C2I")) : 2;
-  return v >= 2;
+HpChunk::Bwd bwd_kernel(const Geom &g, const HpDims &hd) {
+  if (use_bwd3(g, hd)) return HpChunk::BWD3;
+  return hp_switches().bwd >= 2 && bwd2_takes(g, hd) ? HpChunk::BWD2 : HpChunk::BWD1;
 }
 
 // images per chunk: channels-last input copy (and one image's grad_col) below the limit
@@ -88,51 +95,84 @@ int chunk_batch(const Geom &g, const HpDims &hd, bool backward) {
   return bc > g.B ? g.B : bc;
 }
 
-FwdLayout fwd_layout(const Geom &gc, const HpDims &hd) {
-  FwdLayout L;
-  size_t off = 0;
-  L.off_xt = off;  off += align_up((size_t)gc.B * gc.S_i * hd.Cp * 2);
-  L.off_w = off;   off += align_up((size_t)gc.K * (hd.Cp / 16) * hd.oblks * 1024);
-  L.off_tab = off; off += align_up((size_t)hd.oranges * (hd.Cp / 16 + 1) * sizeof(int2));
-  L.total = off;
+HpFwdLayout fwd_layout(const Geom &gc, const HpDims &hd) {
+  HpFwdLayout L;
+  Bump b;
+  L.off_xt = b.take((size_t)gc.B * gc.S_i * hd.Cp * 2);
+  L.off_w = b.take((size_t)gc.K * (hd.Cp / 16) * hd.oblks * 1024);
+  L.off_tab = b.take((size_t)hd.oranges * (hd.Cp / 16 + 1) * sizeof(int2));
+  L.total = b.off;
   return L;
 }
 
 // int4 per list entry: short entries for 2-D fp16 tensors, long ones otherwise (hp_col2im.hip: ShortEntry)
 int hp_entry_width(const Geom &g, int dtype) { return g.nd == 2 && dtype == MDCONV_F16 ? 1 : 2; }
 
-BwdLayout bwd_layout(const Geom &gc, const HpDims &hd, int dtype) {
-  BwdLayout L;
-  size_t off = 0;
-  L.off_xt = off;   off += align_up((size_t)gc.B * gc.S_i * hd.Cp * 2);
-  L.off_w = off;    off += align_up((size_t)gc.K * hd.cblks * hd.nks * 1024);
-  L.off_tab = off;  off += align_up((size_t)hd.cblks * sizeof(int4));
-  L.off_gcol = off; off += align_up((size_t)gc.B * gc.K * gc.S_o * hd.Cp * 2);
-  L.off_col = off;  off += use_bwd3(gc, hd) ? align_up((size_t)gc.B * gc.K * gc.S_o * hd.Cp * 2) : 0;   // column rows for GEMM-2
-  // a shorter last chunk can have MORE ranges than a full one (ranges is not monotonic in the tile
-  // count), so the partials are sized for the bound; gw32 = running fp32 grad_weight over chunks
-  L.off_part = off; off += align_up((size_t)gc.K * hd.max_ranges * hd.cblks * hd.MB2 * 4096);
-  L.off_gw32 = off; off += align_up((size_t)gc.O * gc.Cg * gc.K * sizeof(float));
+// Bytes one chunk needs in every slot of the backward layout whose size depends on the chunk (the packed W^T, the block
+// table and the running fp32 grad_weight depend on the call alone); `ranges`: pixel ranges per tap in the fp32 partials
+struct BwdNeed { size_t xt, gcol, col, part, cnt, rowptr, entries, sums, sort; };
+BwdNeed bwd_need(const HpChunk &c, int ranges, int dtype, bool two_pass_gather) {
+  const Geom &gc = c.gc;
+  const HpDims &hd = c.hd;
+  const size_t rows = (size_t)gc.B * gc.K * gc.S_o * hd.Cp * 2;
+  BwdNeed n;
+  n.xt = (size_t)gc.B * gc.S_i * hd.Cp * 2;
+  n.gcol = rows;
+  n.col = c.bwd == HpChunk::BWD3 ? rows : 0;   // column rows for GEMM-2
+  n.part = (size_t)gc.K * ranges * hd.cblks * hd.MB2 * 4096;
   // scatter lists: one 32-byte entry per sample, keyed by its extended anchor (hp_col2im.hip)
   const size_t S_e = (size_t)hp_anchor_space(gc);
-  L.off_cnt = off;  off += align_up((size_t)gc.B * gc.DG * S_e * sizeof(int));
-  L.off_rowptr = off; off += align_up((size_t)gc.B * gc.DG * (S_e + 1) * sizeof(int));
-  L.off_entries = off; off += align_up((size_t)gc.B * gc.DG * gc.K * gc.S_o * 32);
-  L.off_sums = off; off += use_col2im2() ? align_up(hp_col2im_sums_bytes(gc, hd, dtype)) : 0;
+  n.cnt = (size_t)gc.B * gc.DG * S_e * sizeof(int);
+  n.rowptr = (size_t)gc.B * gc.DG * (S_e + 1) * sizeof(int);
+  n.entries = (size_t)gc.B * gc.DG * gc.K * gc.S_o * 32;
+  n.sums = two_pass_gather ? hp_col2im_sums_bytes(gc, hd, dtype) : 0;
   // deterministic mode (Geom::det): scratch of the list sort, shaped like the entries (csr_sort.hip)
-  L.off_sort = off;
-  off += gc.det ? align_up(csr_sort_scratch_bytes(hp_entry_width(gc, dtype), (int64_t)gc.K * gc.S_o, gc.B * gc.DG)) : 0;
-  L.total = off;
+  n.sort = gc.det ? csr_sort_scratch_bytes(hp_entry_width(gc, dtype), (int64_t)gc.K * gc.S_o, gc.B * gc.DG) : 0;
+  return n;
+}
+
+// the layout of a call, made for its full chunk
+HpBwdLayout bwd_layout(const HpChunk &c, int dtype, bool two_pass_gather) {
+  const Geom &gc = c.gc;
+  const HpDims &hd = c.hd;
+  // a shorter last chunk can have MORE ranges than a full one (ranges is not monotonic in the tile
+  // count), so the partials are sized for the bound; gw32 = running fp32 grad_weight over chunks
+  const BwdNeed n = bwd_need(c, hd.max_ranges, dtype, two_pass_gather);
+  HpBwdLayout L;
+  Bump b;
+  L.off_xt = b.take(n.xt);
+  L.off_w = b.take((size_t)gc.K * hd.cblks * hd.nks * 1024);
+  L.off_tab = b.take((size_t)hd.cblks * sizeof(int4));
+  L.off_gcol = b.take(n.gcol);
+  L.off_col = b.take(n.col);
+  L.off_part = b.take(n.part);
+  L.off_gw32 = b.take((size_t)gc.O * gc.Cg * gc.K * sizeof(float));
+  L.off_cnt = b.take(n.cnt);
+  L.off_rowptr = b.take(n.rowptr);
+  L.off_entries = b.take(n.entries);
+  L.off_sums = b.take(n.sums);
+  L.off_sort = b.take(n.sort);
+  L.total = b.off;
   return L;
 }
 
-}  // namespace
-
-
-// workgroups per CU the fused backward kernel is sized for when it has 8 + 2 waves (C_in > 128)
-static int hp_wg_per_cu8() {
-  return 2;
+// The layout is made for the full chunk; a tail chunk has its own dimensions and picks its own kernel (it may take hp_bwd3
+// where the full chunk did not, or have more pixel ranges), so what it needs is compared with every slot it uses.
+// Returns the name of a slot that is too small for chunk `c`, or null.
+const char *bwd_short_slot(const HpBwdLayout &L, const HpChunk &c, int dtype, bool two_pass_gather) {
+  const BwdNeed n = bwd_need(c, c.bwd == HpChunk::BWD3 ? c.hd.ranges_w : c.hd.ranges, dtype, two_pass_gather);
+  const struct { const char *name; size_t need, have; } slots[] = {
+      {"channels-last input copy", n.xt, L.off_w - L.off_xt},   {"grad_col rows", n.gcol, L.off_col - L.off_gcol},
+      {"column rows", n.col, L.off_part - L.off_col},           {"grad_weight partials", n.part, L.off_gw32 - L.off_part},
+      {"list counters", n.cnt, L.off_rowptr - L.off_cnt},       {"list row pointers", n.rowptr, L.off_entries - L.off_rowptr},
+      {"list entries", n.entries, L.off_sums - L.off_entries},  {"partial sums", n.sums, L.off_sort - L.off_sums},
+      {"sort scratch", n.sort, L.total - L.off_sort}};
+  for (const auto &s : slots)
+    if (s.need > s.have) return s.name;
+  return nullptr;
 }
+
+}  // namespace
 
 HpDims hp_dims(const Geom &g) {
   HpDims hd;
@@ -184,12 +224,11 @@ HpDims hp_dims(const Geom &g) {
   hd.waves = pow2_ceil(hd.cblks);
   hd.ntiles = (g.N + 31) / 32;
   {
-    static const int blocked_env = getenv("MDCONV_HP_BLOCKED") ? atoi(getenv("MDCONV_HP_BLOCKED")) : 1;
-    hd.blocked = blocked_env && hp_blocked_ok(g) ? 1 : 0;
+    hd.blocked = hp_switches().blocked && hp_blocked_ok(g) ? 1 : 0;
   }
   // pixel ranges per tap of the fused kernel: about one dispatch round of workgroups (2 workgroups of
   // 4 + 1 waves per CU, 1-2 of 8 + 2)
-  const int slots = num_cus() * (hd.waves >= 8 ? hp_wg_per_cu8() : 2 * (4 / hd.waves));
+  const int slots = num_cus() * (hd.waves >= 8 ? kHpWgPerCu8 : 2 * (4 / hd.waves));
   int ranges = slots / g.K;
   if (ranges < 1) ranges = 1;
   hd.max_ranges = ranges;
@@ -218,7 +257,7 @@ HpDims hp_dims(const Geom &g) {
 // through workspace copies (fp16 96 -> 96 at 40 x 40, 4 groups: 1.11 -> 0.33 ms; profiles/r06_experiments.md 17).  Not for a
 // channels-last input (read in place, C wide) nor with the one-pass gather (MDCONV_HP_C2I=1 writes grad_input itself).
 static bool group_padded(const Geom &g, Geom *gv) {
-  if (g.cm_pad || g.G != 1 || g.DG == 1 || g.in_cl || !use_col2im2()) return false;
+  if (g.cm_pad || g.G != 1 || g.DG == 1 || g.in_cl || !hp_switches().two_pass_gather) return false;
   int cdp = (g.DG == 2 || g.DG == 4) ? pow2_ceil(g.Cdg) : (g.Cdg + 31) / 32 * 32;
   if (cdp < 16) cdp = 16;
   if (cdp == g.Cdg) return false;
@@ -232,14 +271,12 @@ static bool group_padded(const Geom &g, Geom *gv) {
   return true;
 }
 
-static bool hp_supported_as(const Geom &g, int dtype, bool backward);
-// the geometry the native kernels run for `g`: g itself or its group-padded form
 // One deformable group and 96 / 160 / 192 / 224 padded channels: the pixel-stationary backward gives a pixel a power-of-two lane count,
 // so these widths ran on the tap-stationary kernels at any size; padded to 128 / 256 channels (the same channel map, one "group") they
 // take hp_bwd3 where its size rule applies (fp16 192 -> 192 at 56 x 56, B = 8: 0.91 -> 0.42 ms; 224 -> 256: 1.00 -> 0.44; 3-D 160 -> 160
 // at 8 x 28 x 28: 1.41 -> 1.05; small grids keep the tap-stationary kernels on the unpadded width; experiment log 25)
 static bool width_padded(const Geom &g, Geom *gv) {
-  if (g.cm_pad || g.G != 1 || g.DG != 1 || g.in_cl || !use_col2im2()) return false;
+  if (g.cm_pad || g.G != 1 || g.DG != 1 || g.in_cl || !hp_switches().two_pass_gather) return false;
   const int Cp = (g.C + 31) / 32 * 32;
   if (Cp <= 64 || Cp >= 256 || pow2_ceil(Cp) == Cp) return false;
   *gv = g;
@@ -249,73 +286,6 @@ static bool width_padded(const Geom &g, Geom *gv) {
   gv->C_caller = g.C;
   return true;
 }
-static bool hp_plan_geom(const Geom &g, int dtype, bool backward, Geom *ge) {
-  if (hp_supported_as(g, dtype, backward)) {
-    if (backward && width_padded(g, ge) && hp_supported_as(*ge, dtype, true)) {
-      const int bc = chunk_batch(*ge, hp_dims(*ge), true);
-      if (bc > 0) {
-        const Geom gc = chunk_geom(*ge, bc);
-        if (use_bwd3(gc, hp_dims(gc))) return true;
-      }
-    }
-    *ge = g;
-    return true;
-  }
-  return group_padded(g, ge) && hp_supported_as(*ge, dtype, backward);
-}
-bool hp_supported(const Geom &g, int dtype, bool backward) {
-  Geom ge;
-  return hp_plan_geom(g, dtype, backward, &ge);
-}
-
-static bool hp_supported_as(const Geom &g, int dtype, bool backward) {
-  if (!hp_enabled()) return false;
-  if (dtype != MDCONV_F16 && dtype != MDCONV_BF16) return false;
-  if (g.DG > 1 && g.Cdg % 16) return false;
-  const HpDims hd = hp_dims(g);
-  // backward with deformable groups of 16 / 48 / ... channels: the pixel-stationary kernel only (its lanes own 8 channels
-  // of one group each); the tap-stationary kernels reduce the coordinate sums per 32-channel block
-  if (backward && g.DG > 1 && g.Cdg % 32 && !use_bwd3(g, hd)) return false;
-  if (backward) {
-    if (hd.cblks > 8 || hd.MB2 > 8) return false;   // one workgroup covers all input channels
-    if (g.in_sz[g.nd - 1] < 2) return false;        // pair-keyed scatter lists
-  }
-  return chunk_batch(g, hd, backward) > 0;
-}
-
-// Forward of a FEW pixel tiles over MANY K stages: hp_fwd2 runs one workgroup per (128-pixel tile, output-channel row)
-// through every tap and 64-channel stage, so a grid of a dozen workgroups takes one whole tile time on an otherwise empty
-// chip (C = 512, 7 x 7, B = 16: 231 us; 3-D C = 256, 4 x 7 x 7, B = 4: 547 us) -- whereas the fp32 matrix forwards cut such
-// grids into tap ranges (fwd_tail_plan) and take 87 / 109 us for the same shapes.  Such calls run on the fp32 kernels
-// through fp32 copies (the route of every 16-bit shape the native kernels do not take: fp32 accumulation, one rounding of
-// the output).  Not with a channels-last input (only the native kernels read it in place), not when MDCONV_HP_FWD selects a
-// kernel explicitly (the forced-path tests).
-bool hp_forward_preferred(const Geom &gcall, int dtype) {
-  static const bool forced = getenv("MDCONV_HP_FWD") != nullptr;
-  if (forced) return true;
-  Geom g;
-  if (!hp_plan_geom(gcall, dtype, false, &g)) return false;
-  // counted in rows of 8 output blocks whatever rows hp_dims picks: single-block rows (small grids, MB = 1) multiply the
-  // workgroups, not the work one of them finishes per unit time (2048 -> 512 at 7 x 7, B = 8: 64 single-block workgroups
-  // 675 us, the fp32 route 277 us; profiles/r06_experiments.md 15)
-  const int oblks = (g.O + 31) / 32;
-  const long wgs = (long)((g.N + 127) / 128) * ((oblks + 7) / 8);
-  const long stages = (long)g.K * ((g.C + 63) / 64);
-  if (wgs > 16 || stages < 64) return true;
-  return !mfma_supported(gcall, dtype, false);
-}
-
-size_t hp_workspace_bytes(const Geom &gcall, int dtype, bool backward) {
-  Geom g;
-  if (!hp_plan_geom(gcall, dtype, backward, &g)) return 0;
-  HpDims hd = hp_dims(g);
-  const int bc = chunk_batch(g, hd, backward);
-  if (bc <= 0) return 0;
-  const Geom gc = chunk_geom(g, bc);
-  hd = hp_dims(gc);
-  return backward ? bwd_layout(gc, hd, dtype).total : fwd_layout(gc, hd).total;
-}
-
 // hp_fwd2 with deformable groups: every workgroup row's channel range must start on a group
 // boundary (its stages are numbered from there)
 static bool fwd2_rows_align(const Geom &g, const HpDims &hd) {
@@ -330,31 +300,114 @@ static bool fwd2_rows_align(const Geom &g, const HpDims &hd) {
   return true;
 }
 
-int hp_forward(const Geom &gcall, int dtype, const Tensors &t, void *ws, hipStream_t stream) {
-  Geom g;   // the caller's geometry or its group-padded form
-  if (!hp_plan_geom(gcall, dtype, false, &g)) { set_error("hp_forward: no plan"); return MDCONV_EUNSUPPORTED; }
-  const int Bc = chunk_batch(g, hp_dims(g), false);
-  if (Bc <= 0) { set_error("hp_forward: no plan"); return MDCONV_EUNSUPPORTED; }
-  const Geom g0 = chunk_geom(g, Bc);
-  const HpDims hd0 = hp_dims(g0);
-  const FwdLayout L = fwd_layout(g0, hd0);
+// The chunks of `g` run as it stands (no padding decision): chunk size, the dimensions and the kernel of each chunk size.
+// false: the kernels do not take `g`.
+static bool plan_chunks(const Geom &g, int dtype, bool backward, HpPlan *p) {
+  if (!hp_switches().enabled) return false;
+  if (dtype != MDCONV_F16 && dtype != MDCONV_BF16) return false;
+  if (g.DG > 1 && g.Cdg % 16) return false;
+  const HpDims hd = hp_dims(g);
+  // backward with deformable groups of 16 / 48 / ... channels: the pixel-stationary kernel only (its lanes own 8 channels
+  // of one group each); the tap-stationary kernels reduce the coordinate sums per 32-channel block
+  if (backward && g.DG > 1 && g.Cdg % 32 && !use_bwd3(g, hd)) return false;
+  if (backward) {
+    if (hd.cblks > 8 || hd.MB2 > 8) return false;   // one workgroup covers all input channels
+    if (g.in_sz[g.nd - 1] < 2) return false;        // pair-keyed scatter lists
+  }
+  p->g = g;
+  p->Bc = chunk_batch(g, hd, backward);
+  if (p->Bc <= 0) return false;
+  p->full.gc = chunk_geom(g, p->Bc);
+  p->full.hd = p->Bc == g.B ? hd : hp_dims(p->full.gc);
+  p->tail = p->full;
+  if (g.B % p->Bc) {
+    p->tail.gc = chunk_geom(g, g.B % p->Bc);
+    p->tail.hd = hp_dims(p->tail.gc);
+    if (!backward) {
+      // The row width is a decision of the CALL: hp_dims narrows the rows of a small grid (MB = 1), and a shorter last
+      // chunk can be such a grid -- but the weights are packed and the row table is filled once, for the full chunk's
+      // rows, so every chunk runs those (a tail with its own MB read table rows nobody had written and skipped its
+      // output-channel blocks).  The kernel choice below follows the rows.
+      p->tail.hd.MB = p->full.hd.MB;
+      p->tail.hd.oranges = p->full.hd.oranges;
+      p->tail.hd.fwd_nmax = p->full.hd.fwd_nmax;
+    }
+  }
+  for (HpChunk *c : {&p->full, &p->tail}) {
+    // forward: quad-contiguous gathers (hp_fwd2.hip) unless a 64-channel stage would straddle deformable groups
+    c->fwd2 = !backward && hp_switches().fwd == 2 && (g.DG == 1 || (g.Cdg % 64 == 0 && fwd2_rows_align(g, c->hd)));
+    // backward: pixel-stationary or tap-stationary PER CHUNK SIZE -- both kernels read the same packed W^T and block table
+    // and write the same grad_col rows and fp32 partials
+    c->bwd = backward ? bwd_kernel(c->gc, c->hd) : HpChunk::BWD1;
+  }
+  return true;
+}
+
+// Forward of a FEW pixel tiles over MANY K stages: hp_fwd2 runs one workgroup per (128-pixel tile, output-channel row)
+// through every tap and 64-channel stage, so a grid of a dozen workgroups takes one whole tile time on an otherwise empty
+// chip (C = 512, 7 x 7, B = 16: 231 us; 3-D C = 256, 4 x 7 x 7, B = 4: 547 us) -- whereas the fp32 matrix forwards cut such
+// grids into tap ranges (fwd_tail_plan) and take 87 / 109 us for the same shapes.  Such calls run on the fp32 kernels
+// through fp32 copies (the route of every 16-bit shape the native kernels do not take: fp32 accumulation, one rounding of
+// the output).  Not with a channels-last input (only the native kernels read it in place: the caller's business), not
+// when MDCONV_HP_FWD selects a kernel explicitly (the forced-path tests).  `g`: the planned geometry of `gcall`.
+static bool forward_preferred(const Geom &gcall, const Geom &g, int dtype) {
+  if (hp_switches().fwd_set) return true;
+  // counted in rows of 8 output blocks whatever rows hp_dims picks: single-block rows (small grids, MB = 1) multiply the
+  // workgroups, not the work one of them finishes per unit time (2048 -> 512 at 7 x 7, B = 8: 64 single-block workgroups
+  // 675 us, the fp32 route 277 us; profiles/r06_experiments.md 15)
+  const int oblks = (g.O + 31) / 32;
+  const long wgs = (long)((g.N + 127) / 128) * ((oblks + 7) / 8);
+  const long stages = (long)g.K * ((g.C + 63) / 64);
+  if (wgs > 16 || stages < 64) return true;
+  return !mfma_supported(gcall, dtype, false);
+}
+
+bool hp_plan(const Geom &gcall, int dtype, bool backward, HpPlan *p) {
+  // the geometry the kernels run: the caller's -- or, in the backward, its width-padded form where the full chunk of THAT
+  // takes hp_bwd3 --, else the group-padded form
+  Geom gv;
+  if (plan_chunks(gcall, dtype, backward, p)) {
+    HpPlan padded;
+    if (backward && width_padded(gcall, &gv) && plan_chunks(gv, dtype, true, &padded) && padded.full.bwd == HpChunk::BWD3)
+      *p = padded;
+  } else if (!group_padded(gcall, &gv) || !plan_chunks(gv, dtype, backward, p)) {
+    return false;
+  }
+  p->two_pass_gather = hp_switches().two_pass_gather;
+  p->forward_preferred = backward || forward_preferred(gcall, p->g, dtype);
+  p->fwd = HpFwdLayout();
+  p->bwd = HpBwdLayout();
+  if (!backward) {
+    p->fwd = fwd_layout(p->full.gc, p->full.hd);
+    p->total = p->fwd.total;
+    return true;
+  }
+  p->bwd = bwd_layout(p->full, dtype, p->two_pass_gather);
+  p->total = p->bwd.total;
+  for (const HpChunk *c : {&p->full, &p->tail}) {
+    const char *slot = bwd_short_slot(p->bwd, *c, dtype, p->two_pass_gather);
+    if (slot) {
+      set_error("hp_plan: the %s of a chunk of %d images do not fit the slot laid out for chunks of %d", slot, c->gc.B, p->Bc);
+      return false;
+    }
+  }
+  return true;
+}
+
+int hp_forward(int dtype, const HpPlan &p, const Tensors &t, void *ws, hipStream_t stream) {
+  const Geom &g = p.g;
+  const HpFwdLayout &L = p.fwd;
   char *base = (char *)ws;
   const int nc_off = g.DG * g.nd * g.K, nc_m = g.DG * g.K;
   const size_t es_s = samp_bytes(dtype, t);   // offset / mask element: 2, or 4 with fp32 sampling
   int rc;
-  if ((rc = hp_pack_fwd_weights(g0, hd0, dtype, t.weight, base + L.off_w, (int2 *)(base + L.off_tab), stream)))
+  if ((rc = hp_pack_fwd_weights(p.full.gc, p.full.hd, dtype, t.weight, base + L.off_w, (int2 *)(base + L.off_tab), stream)))
     return rc;
-  for (int b0 = 0; b0 < g.B; b0 += Bc) {
-    const int bc = g.B - b0 < Bc ? g.B - b0 : Bc;
-    const Geom gc = chunk_geom(g, bc);
-    // The row width is a decision of the CALL: hp_dims narrows the rows of a small grid (MB = 1), and a shorter last
-    // chunk can be such a grid -- but the weights are packed and the row table is filled once, for the full chunk's
-    // rows, so every chunk runs those (a tail with its own MB read table rows nobody had written and skipped its
-    // output-channel blocks).  The kernel choice below follows the rows.
-    HpDims hd = hp_dims(gc);
-    hd.MB = hd0.MB;
-    hd.oranges = hd0.oranges;
-    hd.fwd_nmax = hd0.fwd_nmax;
+  for (int b0 = 0; b0 < g.B; b0 += p.Bc) {
+    const int bc = g.B - b0 < p.Bc ? g.B - b0 : p.Bc;
+    const HpChunk &c = bc == p.Bc ? p.full : p.tail;
+    const Geom &gc = c.gc;
+    const HpDims &hd = c.hd;
     Tensors tc = t;
     tc.input = (const char *)t.input + (size_t)b0 * caller_channels(g) * g.S_i * 2;
     tc.offset = (const char *)t.offset + (size_t)b0 * nc_off * g.S_o * es_s;
@@ -363,11 +416,8 @@ int hp_forward(const Geom &gcall, int dtype, const Tensors &t, void *ws, hipStre
     const void *xt = base + L.off_xt;
     if (g.in_cl) xt = (const char *)t.input + (size_t)b0 * g.S_i * g.C * 2;   // already channels-last
     else if ((rc = hp_nchw_to_nhwc(gc, hd, tc.input, base + L.off_xt, stream))) return rc;
-    // quad-contiguous gathers (hp_fwd2.hip) unless a 64-channel stage would straddle deformable groups
-    static const int fwd_ver = getenv("MDCONV_HP_FWD") ? atoi(getenv("MDCONV_HP_FWD")) : 2;
-    const bool fwd2 = fwd_ver == 2 && (g.DG == 1 || (g.Cdg % 64 == 0 && fwd2_rows_align(g, hd)));
-    profile_mark(0, true, stream, fwd2 ? "hp_fwd2_kernel" : "hp_fwd_kernel");
-    if (fwd2)
+    profile_mark(0, true, stream, c.fwd2 ? "hp_fwd2_kernel" : "hp_fwd_kernel");
+    if (c.fwd2)
       rc = hp_forward2_launch(gc, hd, dtype, tc, xt, base + L.off_w,
                               (const int2 *)(base + L.off_tab), stream);
     else
@@ -379,26 +429,23 @@ int hp_forward(const Geom &gcall, int dtype, const Tensors &t, void *ws, hipStre
   return MDCONV_OK;
 }
 
-int hp_backward(const Geom &gcall, int dtype, const Tensors &t, void *ws, hipStream_t stream) {
-  Geom g;   // the caller's geometry or its group-padded form
-  if (!hp_plan_geom(gcall, dtype, true, &g)) { set_error("hp_backward: no plan"); return MDCONV_EUNSUPPORTED; }
-  const int Bc = chunk_batch(g, hp_dims(g), true);
-  if (Bc <= 0) { set_error("hp_backward: no plan"); return MDCONV_EUNSUPPORTED; }
-  const Geom g0 = chunk_geom(g, Bc);
-  const HpDims hd0 = hp_dims(g0);
-  const BwdLayout L = bwd_layout(g0, hd0, dtype);
+int hp_backward(int dtype, const HpPlan &p, const Tensors &t, void *ws, hipStream_t stream) {
+  const Geom &g = p.g;
+  const int Bc = p.Bc;
+  const HpBwdLayout &L = p.bwd;
   char *base = (char *)ws;
   const int nc_off = g.DG * g.nd * g.K, nc_m = g.DG * g.K;
   const size_t es_s = samp_bytes(dtype, t);   // offset / mask element: 2, or 4 with fp32 sampling
   int rc;
-  if ((rc = hp_pack_bwd_weights(g0, hd0, dtype, t.weight, base + L.off_w, (int4 *)(base + L.off_tab), stream)))
+  if ((rc = hp_pack_bwd_weights(p.full.gc, p.full.hd, dtype, t.weight, base + L.off_w, (int4 *)(base + L.off_tab), stream)))
     return rc;
   if (g.with_bias && (rc = hp_grad_bias(g, dtype, t.grad_output, t.grad_bias, t.wgrad32 != 0, stream))) return rc;
   for (int b0 = 0; b0 < g.B; b0 += Bc) {
     const int bc = g.B - b0 < Bc ? g.B - b0 : Bc;
-    Geom gc = chunk_geom(g, bc);
+    const HpChunk &c = bc == Bc ? p.full : p.tail;
+    const Geom &gc = c.gc;
+    const HpDims &hd = c.hd;
     const bool multi = Bc < g.B, first = b0 == 0, last = b0 + bc >= g.B;
-    const HpDims hd = hp_dims(gc);
     Tensors tc = t;
     tc.input = (const char *)t.input + (size_t)b0 * caller_channels(g) * g.S_i * 2;
     tc.offset = (const char *)t.offset + (size_t)b0 * nc_off * g.S_o * es_s;
@@ -412,11 +459,7 @@ int hp_backward(const Geom &gcall, int dtype, const Tensors &t, void *ws, hipStr
     if (g.in_cl) xt = (const char *)t.input + (size_t)b0 * g.S_i * g.C * 2;   // already channels-last
     else if ((rc = hp_nchw_to_nhwc(gc, hd, tc.input, base + L.off_xt, stream))) return rc;
     if ((rc = hp_csr_zero(gc, cnt, stream))) return rc;
-    // pixel-stationary or tap-stationary PER CHUNK: both kernels read the same packed W^T and block table, write the same
-    // grad_col rows and fp32 partials sized for either (max_ranges), and use_bwd3 is monotonic in the tile count, so a
-    // chunk that takes hp_bwd3 implies the full chunk did and the layout has the column rows (off_col)
-    const bool bwd3 = use_bwd3(gc, hd);
-    const bool bwd2 = !bwd3 && bwd_version() >= 2 && g.DG <= 4 && hp_bwd2_lds_bytes(gc, hd) <= 160 * 1024;
+    const bool bwd3 = c.bwd == HpChunk::BWD3, bwd2 = c.bwd == HpChunk::BWD2;   // (the plan checked this chunk's slots)
     profile_mark(1, true, stream, bwd3 ? "hp_bwd3_kernel" : (bwd2 ? "hp_bwd2_kernel" : "hp_bwd_kernel"));
     if (bwd3)
       rc = hp_backward3_launch(gc, hd, dtype, tc, xt, base + L.off_w, base + L.off_gcol, base + L.off_col, cnt, stream);
@@ -460,9 +503,9 @@ int hp_backward(const Geom &gcall, int dtype, const Tensors &t, void *ws, hipStr
       rc = csr_sort_rows(rowptr, base + L.off_entries, base + L.off_sort, hp_entry_width(gc, dtype), hp_anchor_space(gc),
                          (int64_t)gc.K * gc.S_o, gc.B * gc.DG, gs);
     if (!rc) {
-      profile_mark(3, true, gs, use_col2im2() ? "hp_col2im_sums_kernel" : "hp_col2im_kernel");
-      rc = use_col2im2() ? hp_col2im2(gc, hd, dtype, tc, base + L.off_gcol, rowptr, base + L.off_entries, base + L.off_sums, gs)
-                         : hp_col2im(gc, hd, dtype, tc, base + L.off_gcol, rowptr, base + L.off_entries, gs);
+      profile_mark(3, true, gs, p.two_pass_gather ? "hp_col2im_sums_kernel" : "hp_col2im_kernel");
+      rc = p.two_pass_gather ? hp_col2im2(gc, hd, dtype, tc, base + L.off_gcol, rowptr, base + L.off_entries, base + L.off_sums, gs)
+                             : hp_col2im(gc, hd, dtype, tc, base + L.off_gcol, rowptr, base + L.off_entries, gs);
       profile_mark(3, false, gs);
     }
     if (forked) {

@@ -1,16 +1,10 @@
-// hp_kernels.hpp -- entry points of the native 16-bit (fp16 / bf16) path (hp_*.hip).
+// hp_kernels.hpp -- dimensions and launchers of the native 16-bit (fp16 / bf16) path (hp_*.hip); its plan: hp_plan.hpp.
 #pragma once
 #include "hp_common.hpp"
 
 namespace mdconv {
 
-bool hp_supported(const Geom &g, int dtype, bool backward);
-size_t hp_workspace_bytes(const Geom &g, int dtype, bool backward);
-// false: a forward of a few pixel tiles over many K stages, faster on the fp32 matrix kernels through fp32 copies (hp_host.hip)
-bool hp_forward_preferred(const Geom &g, int dtype);
-int hp_forward(const Geom &g, int dtype, const Tensors &t, void *ws, hipStream_t stream);
-int hp_backward(const Geom &g, int dtype, const Tensors &t, void *ws, hipStream_t stream);
-
+// hp_host.hip (the planner and the kernel sequences: hp_plan.hpp)
 HpDims hp_dims(const Geom &g);
 
 // hp_prep.hip

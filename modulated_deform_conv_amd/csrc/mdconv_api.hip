@@ -14,7 +14,7 @@
 #include <utility>
 
 #include "mdconv_common.hpp"
-#include "hp_kernels.hpp"
+#include "hp_plan.hpp"
 #include "mfma_plan.hpp"
 
 namespace mdconv {
@@ -250,6 +250,7 @@ struct CallPlan {
   Refusal refused;
   size_t bytes;      // workspace the route needs
   size_t reported;   // what mdconv_workspace_bytes answers: `bytes`, but see the few-tile forwards in plan_call
+  HpPlan hp;         // ROUTE_HP
   MfmaPlan f32;      // ROUTE_F32
   S32Plan s32;       // ROUTE_*_SAMP32
   D16Plan d16;       // ROUTE_DIRECT_16
@@ -261,11 +262,11 @@ static bool route_is_direct(Route r) { return r == ROUTE_DIRECT || r == ROUTE_DI
 // sliced plans hold grad_weight rows in the caller's element size, and size them for it.
 static void plan_call(const Geom &g, int dt, int s32, int wg32, int path, bool backward, CallPlan *cp) {
   const bool half = dt == MDCONV_F16 || dt == MDCONV_BF16;
-  const bool hp = path != MDCONV_PATH_DIRECT && hp_supported(g, dt, backward);
+  const bool hp = path != MDCONV_PATH_DIRECT && hp_plan(g, dt, backward, &cp->hp);
   cp->refused = g.in_cl && !(hp && g.C % 32 == 0) ? REFUSE_CHANNELS_LAST : REFUSE_NONE;
-  const size_t hp_bytes = hp ? hp_workspace_bytes(g, dt, backward) : 0;
-  // 16-bit forwards of a few tiles run faster on the fp32 kernels (hp_forward_preferred)
-  const bool few_tile = hp && !backward && !hp_forward_preferred(g, dt);
+  const size_t hp_bytes = hp ? cp->hp.total : 0;
+  // 16-bit forwards of a few tiles run faster on the fp32 kernels (HpPlan::forward_preferred)
+  const bool few_tile = hp && !cp->hp.forward_preferred;
   if (hp && !few_tile) {
     cp->route = ROUTE_HP;
     cp->bytes = cp->reported = hp_bytes;
@@ -382,7 +383,7 @@ static int run_forward(const mdconv_desc *d, int nd, int modulated, Tensors t, v
       if ((rc = check_ws(ws, ws_bytes, cp.bytes))) return rc;
       g_last_path = MDCONV_PATH_MFMA;
       g_last_kernels = MDCONV_KERNELS_HP;
-      return hp_forward(g, dt, t, ws, s);
+      return hp_forward(dt, cp.hp, t, ws, s);
     case ROUTE_F32:
     case ROUTE_F32_SAMP32:
       g_last_path = MDCONV_PATH_MFMA;
@@ -436,7 +437,7 @@ static int run_backward(const mdconv_desc *d, int nd, int modulated, Tensors t, 
     if ((rc = check_ws(ws, ws_bytes, cp.bytes))) return rc;
     g_last_path = MDCONV_PATH_MFMA;
     g_last_kernels = MDCONV_KERNELS_HP;
-    return hp_backward(g, dt, t, ws, s);
+    return hp_backward(dt, cp.hp, t, ws, s);
   }
   if (cp.route == ROUTE_F32 || cp.route == ROUTE_F32_SAMP32) {
     g_last_path = MDCONV_PATH_MFMA;

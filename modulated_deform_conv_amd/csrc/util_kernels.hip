@@ -146,7 +146,7 @@ int zero_bytes(void *p, size_t bytes, hipStream_t s) {
   return check_launch("zero");
 }
 
-// 16-bit tensors the native kernels do not take (hp_supported) run through fp32 copies: fp16 and bf16
+// 16-bit tensors the native kernels do not take (hp_plan) run through fp32 copies: fp16 and bf16
 int widen(int dtype, const void *src, float *dst, int64_t n, hipStream_t s) {
   if (n == 0) return MDCONV_OK;
   if (dtype == MDCONV_BF16)

@@ -251,6 +251,34 @@ def test_workspace_plan_and_layout_query_without_gpu(capi):
     assert capi.lib().mdconv_profile_name(9) == b""
 
 
+def test_16bit_plan_answers_are_stable_without_gpu(capi):
+    """Host planning only: the native 16-bit family plans a call once (hp_plan.hpp: hp_plan), and the sizing query reads
+    that plan's total.  For shapes its kernels take -- conv groups, 256 -> 256, 3-D, a group-padded one -- the backward
+    query answers the same non-zero size every time it is asked, and covers at least the grad_col rows of the plan.  The
+    3-D shape is a forward of a few pixel tiles over many K stages (7 tiles, 108 stages): it runs on the fp32 kernels from an
+    NCHW input and on the native ones from a channels-last input, and the reported size is enough for either family, so
+    the query answers alike for both layouts."""
+    L = capi.lib()
+    ws = lambda d, bwd: L.mdconv_workspace_bytes(ctypes.byref(d), bwd)
+    descs = {
+        "cfg3_like": (_plan_desc(capi, 2, capi.F16, 2, 256, 256, (14, 14), G=32, DG=4), 2 * 9 * 14 * 14 * 256 * 2),
+        "c256": (_plan_desc(capi, 2, capi.BF16, 2, 256, 256, (14, 14)), 2 * 9 * 14 * 14 * 256 * 2),
+        "3d_few_tile": (_plan_desc(capi, 3, capi.F16, 4, 256, 256, (4, 7, 7)), 4 * 27 * 4 * 7 * 7 * 256 * 2),
+        "group_padded": (_plan_desc(capi, 2, capi.F16, 2, 96, 64, (8, 8), DG=4), 2 * 9 * 8 * 8 * 128 * 2),
+    }
+    for name, (d, gcol_rows) in descs.items():
+        first = ws(d, 1)
+        assert first >= gcol_rows, name
+        assert ws(d, 0) > 0 and ws(d, 1) == first, name
+        if name != "group_padded":   # (a padded call needs the library's own input copy: channels-last is refused)
+            assert L.mdconv_input_layout_supported(ctypes.byref(d), 1, 0) == 1, name
+            assert L.mdconv_input_layout_supported(ctypes.byref(d), 1, 1) == 1, name
+    few = descs["3d_few_tile"][0]
+    nchw = ws(few, 0)
+    few.input_layout = 1   # MDCONV_LAYOUT_CHANNELS_LAST
+    assert ws(few, 0) == nchw > 0
+
+
 C_CALLER = r"""
 #include "mdconv.h"
 #include <stdio.h>

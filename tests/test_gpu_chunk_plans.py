@@ -1,7 +1,7 @@
 """Batch-chunked calls whose LAST chunk takes a different plan than the full chunks of the same call.
 
 Both kernel families cut a call into batch chunks when a tensor would pass the 32-bit buffer range (hp_host.hip:
-chunk_batch / hp_forward / hp_backward; mfma_kernels.hip: make_plan / native_forward / native_backward), and many plan
+chunk_batch / hp_plan, run by hp_forward / hp_backward; mfma_kernels.hip: make_plan / native_forward / native_backward), and many plan
 decisions follow the pixel count of the chunk being launched: the forward row width of the 16-bit kernels (hp_dims: MB),
 hp_fwd2 or hp_fwd, hp_bwd3 or hp_bwd2 (use_bwd3), the channels-last fp32 forward and GEMM-2 (fwd_channels_last /
 bwd_channels_last), the N % 32 instance and split-K count of GEMM-2 (bwd_dims).  Weights, tables and the workspace layout
@@ -24,7 +24,7 @@ Modes: "zeros" accumulates into zeroed gradient buffers; "prefill" accumulates i
 "nan" runs in overwrite mode into NaN-filled buffers and must write every element.
 
 Regressions covered: fwd_mb and fwd_k2 for a tail that took narrower forward rows than the row table was filled for
-(hp_forward now takes the row width once per call; the numbers, the NaN-filled output and the pattern-filled table are
+(hp_plan now takes the row width once per call; the numbers, the NaN-filled output and the pattern-filled table are
 the evidence -- both chunk sizes run the same kernel, so there is no proof by name); f32_bwd_cl and f32_padn_3+2 for a
 tail whose fp32 backward workspace is larger than a full chunk's (make_plan now sizes it for the larger need).
 
@@ -74,7 +74,7 @@ def _geo(case):
 
 def hp_width(case):
     """Channels the 16-bit BACKWARD runs on: one deformable group of 96 / 160 / 192 / 224 padded channels is widened to
-    128 / 256 where the full chunk takes hp_bwd3 (hp_host.hip: width_padded).  A partial mirror: it does not test that
+    128 / 256 where the full chunk takes hp_bwd3 (hp_host.hip: width_padded, a step of hp_plan).  A partial mirror: it does not test that
     the full chunk takes hp_bwd3; a case where it does not fails the kernel-name check of slot 1."""
     Cp = _ceil(case["C"], 32)
     if case["groups"] == 1 and case["dgroups"] == 1 and 64 < Cp < 256 and _pow2_ceil(Cp) != Cp:
@@ -93,7 +93,7 @@ def hp_chunk_batch(case, C, limit, backward):
 
 
 def hp_fwd_plan(case, images, cus):
-    """hp_host.hip: hp_dims (MB, oranges) and hp_forward (hp_fwd2 unless a 64-channel stage would straddle deformable groups
+    """hp_host.hip: hp_dims (MB, oranges) and hp_plan's forward kernel choice (hp_fwd2 unless a 64-channel stage would straddle deformable groups
     or, with deformable groups, a second workgroup row exists), one conv group."""
     nd, K, S_i, S_o = _geo(case)
     oblks = _ceil(case["O"], 32) // 32
@@ -108,7 +108,7 @@ def hp_fwd_plan(case, images, cus):
 
 
 def hp_bwd_plan(case, C, images, cus):
-    """hp_host.hip: use_bwd3 -- the pixel-stationary hp_bwd3 beyond one 128-pixel tile per CU (earlier for the instances of
+    """hp_host.hip: use_bwd3, asked by hp_plan for each chunk size -- the pixel-stationary hp_bwd3 beyond one 128-pixel tile per CU (earlier for the instances of
     hp_bwd2 that spill), the tap-stationary hp_bwd2 below; one conv group.  A partial mirror: the library's further
     conditions (hp_bwd3_supported, the LDS and deformable-group limits of hp_bwd2) are left to the kernel-name and
     launch-count checks, which fail where they bite."""

@@ -81,7 +81,7 @@ HP_CASES = [
 
 CASE_BY_HP = {c["name"]: c for c in HP_CASES}
 
-# 16-bit shapes the native kernels reject in at least one direction (hp_supported): more than 256
+# 16-bit shapes the native kernels reject in at least one direction (hp_plan fails): more than 256
 # input channels / a block's output range above 256 in the backward, deformable groups whose padded
 # form (group_padded, hp_host.hip) exceeds 256 channels.  fp16 AND bf16 must still work (fp32 copies through the fp32 kernels, else the
 # shape-generic kernels) -- ADVICE round 2: bf16 used to end in "unknown dtype 3".
@@ -196,7 +196,7 @@ def test_channels_last_input_on_a_shape_the_native_backward_rejects():
         out.backward(t["grad_output"])
         res.append((out, x.grad, off.grad, m.grad, w.grad))
     # (round 5: this few-tile, 72-stage forward runs on the fp32 kernels for the contiguous input and on the native kernels
-    # for the channels-last one -- hp_forward_preferred -- so the two outputs agree to fp16 rounding, not bit for bit)
+    # for the channels-last one -- HpPlan::forward_preferred -- so the two outputs agree to fp16 rounding, not bit for bit)
     assert_close("output", res[1][0].float(), res[0][0].float(), 2e-3, 1e-2)
     for a, b, name in zip(res[0][1:], res[1][1:], ("grad_input", "grad_offset", "grad_mask", "grad_weight")):
         assert_close(name, b.float(), a.float(), 2e-3, 1e-2)
@@ -322,7 +322,7 @@ def test_channels_last_input_is_consumed_in_place(name):
 def test_few_tile_many_stage_forward_runs_on_the_fp32_kernels(dtype):
     """A 16-bit forward of a few 128-pixel tiles over many K stages (C_in = 512 at 7 x 7: one tile, 72 stages) takes one whole
     tile time on the native kernel; the library runs it on the fp32 matrix kernels through fp32 copies instead
-    (hp_forward_preferred, hp_host.hip) -- same oracle tolerance -- while the backward and a channels-last input (which only
+    (HpPlan::forward_preferred, hp_host.hip) -- same oracle tolerance -- while the backward and a channels-last input (which only
     the native kernels read in place) stay on the native kernels."""
     from modulated_deform_conv_amd import MDCONV_CUDA as M, _capi
     case = _c("hp_route_c512_7x7", M2, 2, 512, 64, (7, 7), 3, seed=131)

@@ -1,5 +1,5 @@
 """The lane = pixel predecessors of the native 16-bit kernels (hp_fwd.hip, hp_bwd.hip) are still live
-product code: hp_host.hip selects hp_bwd when a shape has more than 4 deformable groups or needs
+product code: hp_host.hip (hp_plan: bwd_kernel) selects hp_bwd when a shape has more than 4 deformable groups or needs
 more than 160 KB of LDS in hp_bwd2, and hp_fwd when a 64-channel K stage would straddle
 deformable groups.  Only a few shapes reach them on their own, so the whole 16-bit case list runs
 again in a child process with MDCONV_HP_FWD=1 / MDCONV_HP_BWD=1 (read once per process) and is
