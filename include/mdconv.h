@@ -127,6 +127,27 @@ typedef struct mdconv_desc {
  * that would run on them returns MDCONV_EUNSUPPORTED before anything is launched (the message names the shape rule);
  * mdconv_deterministic_supported() tells beforehand.  The forward is always deterministic and ignores the flag. */
 #define MDCONV_FLAG_DETERMINISTIC 1
+/* MDCONV_FLAG_NO_GRAD_INPUT, MDCONV_FLAG_NO_GRAD_WEIGHT -- selective backward (what `output_mask` is to
+ * aten::convolution_backward).  NO_GRAD_INPUT: grad_input is not wanted.  NO_GRAD_WEIGHT: grad_weight and grad_bias are not
+ * wanted.  Both together are valid: only grad_offset (and grad_mask) are computed.
+ *  - Pointer rule: the pointers of a skipped gradient (grad_input; grad_weight and grad_bias) may be NULL.  They are never
+ *    read or written, NULL or not, in accumulate and in overwrite mode.
+ *  - The routing of a flagged call is that of the same call without the flags (kernel family, plan, batch chunks, kernel
+ *    per chunk); only the stages that produce the skipped gradients are left out.  On the matrix-core kernels
+ *    (mdconv_last_kernels() = MDCONV_KERNELS_F32 / MDCONV_KERNELS_HP) every requested gradient holds exactly what the call
+ *    without the flags stores: grad_offset, grad_mask, grad_weight and grad_bias bit for bit, grad_input bit for bit under
+ *    MDCONV_FLAG_DETERMINISTIC and to rounding otherwise, as between any two calls.  On the shape-generic kernels
+ *    (floating-point atomics) the requested gradients agree to rounding.
+ *  - mdconv_workspace_bytes honours the flags and is exact for the flagged call: never larger than without them on the
+ *    matrix-core kernels; on the shape-generic kernels NO_GRAD_INPUT adds scratch the fused data kernel scatters into.
+ *  - With NO_GRAD_WEIGHT there is nothing to wait for: the weights-ready event is recorded on the caller's stream before
+ *    the call's first kernel, so mdconv_stream_wait_weight_ready* after such a call succeeds at once and never refers to
+ *    an older backward.
+ *  - Forward entry points accept and ignore both flags, so one descriptor serves both directions.
+ * (The values skip 2: callers and tests written against earlier releases rely on flags words 2 and 3 being
+ * MDCONV_EINVAL, like every other value that was invalid before these flags existed; they still are.) */
+#define MDCONV_FLAG_NO_GRAD_INPUT 4
+#define MDCONV_FLAG_NO_GRAD_WEIGHT 8
 #define MDCONV_DESC_FLAGS(d) ((d)->reserved[4])
 
 /* Initialiser of a v2 descriptor: `mdconv_desc d = MDCONV_DESC_INIT(2);` then fill in the shape.

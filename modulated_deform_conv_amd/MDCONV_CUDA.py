@@ -35,6 +35,8 @@ def _is_channels_last(t):
 
 def _check_contig(**tensors):
     for name, t in tensors.items():
+        if t is None:   # a gradient the call leaves out (_capi.skip_grads)
+            continue
         # extension of the reference's check (mdeformable_conv.cu:127-131): a channels-last `input`
         # is accepted where the kernels consume that layout anyway
         if not t.is_contiguous() and not (name == "input" and _is_channels_last(t)):
@@ -42,7 +44,14 @@ def _check_contig(**tensors):
 
 
 def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr() if t.numel() > 0 else 0)
+    return ctypes.c_void_p(t.data_ptr() if t is not None and t.numel() > 0 else 0)
+
+
+def _skipped(grad_input, grad_weight, grad_bias):
+    """The gradients of a caller-allocated backward with the ones `_capi.skip_grads` leaves out replaced by None: whatever
+    the caller passed there (None, or any tensor) is neither checked nor handed to the library."""
+    skip_input, skip_weight = _capi.skipped_grads()
+    return (None if skip_input else grad_input,) + ((None, None) if skip_weight else (grad_weight, grad_bias))
 
 
 def _desc(nd, modulated, input, weight, ksz, stride, pad, dil, group, deformable_group, in_step,
@@ -66,6 +75,8 @@ def _desc(nd, modulated, input, weight, ksz, stride, pad, dil, group, deformable
     # deterministic mode (include/mdconv.h: MDCONV_FLAG_DETERMINISTIC): the one place the flag enters a descriptor, so
     # workspace sizing and every entry point see it
     d.flags = _capi.FLAG_DETERMINISTIC if _capi.deterministic_mode() else 0
+    # selective backward (_capi.skip_grads; include/mdconv.h: MDCONV_FLAG_NO_GRAD_INPUT / _WEIGHT; forwards ignore the flags)
+    d.flags |= _capi.skip_flags()
     d.batch, d.c_in, d.c_out = input.shape[0], input.shape[1], weight.shape[0]
     fill = lambda v, f: tuple(int(x) for x in v) + (f,) * (3 - nd)
     d.in_sz = (ctypes.c_int * 3)(*fill(input.shape[2:], 1))
@@ -171,7 +182,7 @@ def _check_deterministic(L, d):
             warnings.warn("modulated_deform_conv_amd: " + msg + "; running it non-deterministically "
                           "(torch.use_deterministic_algorithms(True, warn_only=True)). This warning is issued once.",
                           UserWarning, stacklevel=3)
-        d.flags = 0
+        d.flags &= ~_capi.FLAG_DETERMINISTIC
         return
     raise RuntimeError("modulated_deform_conv_amd does not have a deterministic implementation of this backward: " + msg
                        + ". Use torch.use_deterministic_algorithms(True, warn_only=True) or "
@@ -244,6 +255,7 @@ def deform_conv2d_backward_cuda(input, weight, bias, offset, grad_input, grad_we
                                 pad_h, pad_w, dilation_h, dilation_w, group, deformable_group,
                                 in_step, with_bias):
     """reference deformable_conv.cu:327-333; accumulates into the four grad tensors, returns 0."""
+    grad_input, grad_weight, grad_bias = _skipped(grad_input, grad_weight, grad_bias)
     _check_contig(input=input, weight=weight, bias=bias, offset=offset, grad_input=grad_input,
                   grad_weight=grad_weight, grad_bias=grad_bias, grad_offset=grad_offset,
                   grad_output=grad_output)
@@ -262,15 +274,16 @@ def deform_conv2d_backward_cuda(input, weight, bias, offset, grad_input, grad_we
 
 def _backward_checks(input, weight, offset, mask, grad_input, grad_weight, grad_bias, grad_offset,
                      grad_mask, grad_output, d, with_bias):
-    wgrads = {} if _wgrad_f32(d, input, grad_weight, grad_bias, with_bias) else dict(
+    # (None: a gradient the call leaves out, _capi.skip_grads -- nothing to check)
+    wgrads = {} if grad_weight is None or _wgrad_f32(d, input, grad_weight, grad_bias, with_bias) else dict(
         grad_weight=grad_weight, grad_bias=grad_bias if with_bias else None)
     _check_dtypes(d, input, offset, mask, weight=weight, grad_input=grad_input, grad_offset=grad_offset,
                   grad_mask=grad_mask, grad_output=grad_output, **wgrads)
     for name, g, ref in (("grad_input", grad_input, input), ("grad_weight", grad_weight, weight),
                          ("grad_offset", grad_offset, offset), ("grad_mask", grad_mask, mask)):
-        if ref is not None and g.numel() != ref.numel():
+        if ref is not None and g is not None and g.numel() != ref.numel():
             raise RuntimeError("%s has %d elements, expected %d" % (name, g.numel(), ref.numel()))
-    if with_bias and grad_bias.numel() != d.c_out:
+    if with_bias and grad_weight is not None and grad_bias.numel() != d.c_out:
         raise RuntimeError("grad_bias has %d elements, expected %d" % (grad_bias.numel(), d.c_out))
 
 
@@ -307,14 +320,18 @@ def _modulated2d_backward(fused, input, weight, bias, offset, mask, grad_output,
     # the reference allocates zeros here (mdeformable_conv.cu:404-411) and adds into them; this
     # entry point owns its results, so it allocates uninitialised memory and asks the library to
     # WRITE the gradients (mdconv_desc.accumulate = 0: no zero fills, no read-modify-write)
-    grad_input = torch.empty_like(input, memory_format=torch.contiguous_format)
+    skip_input, skip_weight = _capi.skipped_grads()   # (inside _capi.skip_grads: None for what the call leaves out)
+    grad_input = None if skip_input else torch.empty_like(input, memory_format=torch.contiguous_format)
     grad_offset = torch.empty_like(offset)
     grad_mask = torch.empty_like(mask)
     # grad_weight || grad_bias live in ONE flat buffer: the data-parallel exchange is then a single in-place all-reduce
     # (distributed.py: fused_grad_buffers / FusedGradAllReduce)
     # (inside _capi.weight_grads_f32(): fp32 for 16-bit tensors -- the unrounded sums, reduced in place by the exchange)
     wdt = torch.float32 if _capi.weight_grads_f32_mode() and input.dtype in (torch.float16, torch.bfloat16) else None
-    grad_weight, grad_bias = fused_grad_buffers(weight, bias, wdt) if fused else (torch.empty_like(weight), torch.empty_like(bias))
+    if skip_weight:
+        grad_weight = grad_bias = None
+    else:
+        grad_weight, grad_bias = fused_grad_buffers(weight, bias, wdt) if fused else (torch.empty_like(weight), torch.empty_like(bias))
     _backward_checks(input, weight, offset, mask, grad_input, grad_weight, grad_bias, grad_offset,
                      grad_mask, grad_output, d, with_bias)
     d.accumulate = 0
@@ -341,6 +358,7 @@ def deform_conv3d_backward_cuda(input, weight, bias, offset, grad_input, grad_we
                                 stride_w, stride_l, pad_h, pad_w, pad_l, dilation_h, dilation_w,
                                 dilation_l, group, deformable_group, in_step, with_bias):
     """reference deformable_conv3d.cu:434-442; accumulates, returns 0."""
+    grad_input, grad_weight, grad_bias = _skipped(grad_input, grad_weight, grad_bias)
     _check_contig(input=input, weight=weight, bias=bias, offset=offset, grad_input=grad_input,
                   grad_weight=grad_weight, grad_bias=grad_bias, grad_offset=grad_offset,
                   grad_output=grad_output)
@@ -378,6 +396,7 @@ def modulated_deform_conv3d_backward_cuda(input, weight, bias, offset, mask, gra
                                           dilation_w, dilation_l, group, deformable_group, in_step,
                                           with_bias):
     """reference mdeformable_conv3d.cu:443-451; accumulates, returns 0."""
+    grad_input, grad_weight, grad_bias = _skipped(grad_input, grad_weight, grad_bias)
     _check_contig(input=input, weight=weight, bias=bias, offset=offset, mask=mask,
                   grad_input=grad_input, grad_weight=grad_weight, grad_bias=grad_bias,
                   grad_offset=grad_offset, grad_mask=grad_mask, grad_output=grad_output)

@@ -17,6 +17,8 @@ PATH_AUTO, PATH_DIRECT, PATH_MFMA = 0, 1, 2
 ABI_VERSION = 2
 DESC_V2 = 0x100   # MDCONV_DESC_V2: the descriptor carries accumulate / input_layout / path
 FLAG_DETERMINISTIC = 1   # MDCONV_FLAG_DETERMINISTIC, in the flags word (MdconvDesc.flags = reserved[4])
+FLAG_NO_GRAD_INPUT = 4   # MDCONV_FLAG_NO_GRAD_INPUT: the backward leaves grad_input out (value 2 stays invalid)
+FLAG_NO_GRAD_WEIGHT = 8  # MDCONV_FLAG_NO_GRAD_WEIGHT: the backward leaves grad_weight and grad_bias out
 
 EXPORTS = (
     "mdconv_abi_version", "mdconv_last_error", "mdconv_out_size", "mdconv_workspace_bytes",
@@ -203,6 +205,40 @@ class weight_grads_f32:
 
     def __exit__(self, *exc):
         _modes.weight_grads_f32 = self._prev
+        return False
+
+
+def skipped_grads():
+    """``(input, weight)``: the gradients a backward issued now by this thread leaves out -- the innermost ``skip_grads``
+    context manager, ``(False, False)`` outside one."""
+    return getattr(_modes, "skip_grads", (False, False))
+
+
+def skip_flags():
+    """``skipped_grads()`` as bits of the descriptor's flags word."""
+    skip_input, skip_weight = skipped_grads()
+    return (FLAG_NO_GRAD_INPUT if skip_input else 0) | (FLAG_NO_GRAD_WEIGHT if skip_weight else 0)
+
+
+class skip_grads:
+    """Context manager: backward entry points of MDCONV_CUDA called inside by this thread leave out ``grad_input``
+    (``input=True``) and / or ``grad_weight`` and ``grad_bias`` (``weight=True``): ``MDCONV_FLAG_NO_GRAD_INPUT`` /
+    ``MDCONV_FLAG_NO_GRAD_WEIGHT`` (include/mdconv.h).  The stages that produce them are not run; the other gradients are
+    what the full call stores.  The caller-allocated entry points accept ``None`` (or any tensor, which stays untouched) for
+    a skipped gradient; ``modulated_deform_conv2d_backward_cuda`` returns ``None`` there.  The autograd Functions enter it
+    by themselves from ``ctx.needs_input_grad``.  Thread-local, nests (the innermost block decides both switches), and
+    travels in each call's descriptor like ``overwrite_grads``."""
+
+    def __init__(self, input=False, weight=False):
+        self._skip = (bool(input), bool(weight))
+
+    def __enter__(self):
+        self._prev = skipped_grads()
+        _modes.skip_grads = self._skip
+        return self
+
+    def __exit__(self, *exc):
+        _modes.skip_grads = self._prev
         return False
 
 

@@ -1,7 +1,8 @@
 // hp_bwd3.hip -- host side of the pixel-stationary backward kernel of the native 16-bit path (hp_bwd3_kernel.hpp):
 // which shapes it takes, its LDS size, and the dispatch over the four translation units that instantiate it
 // (hp_bwd3_{f16,bf16}_{2d,3d}.hip -- the template has 11 (lanes per pixel, channel blocks) x 4 (k-steps) x 2 variants per
-// tensor type and rank; split so that they compile side by side).
+// tensor type and rank; split so that they compile side by side) and over their *_nocol siblings, the variant without column
+// rows that a backward without weight gradients runs.
 #include "hp_bwd3_kernel.hpp"
 
 namespace mdconv {
@@ -13,6 +14,11 @@ int hp_bwd3_bf16_3d(const Geom &, const HpDims &, const Tensors &, const void *,
 // fp32 offsets / masks (MDCONV_SAMPLING_F32): hp_bwd3_s32_{f16,bf16}.hip, both ranks
 int hp_bwd3_s32_f16(const Geom &, const HpDims &, const Tensors &, const void *, const void *, void *, void *, int *, hipStream_t);
 int hp_bwd3_s32_bf16(const Geom &, const HpDims &, const Tensors &, const void *, const void *, void *, void *, int *, hipStream_t);
+
+// the variant without column rows (COLS = false): hp_bwd3_*_nocol.hip
+using NoColFn = int(const Geom &, const HpDims &, const Tensors &, const void *, const void *, void *, int *, hipStream_t);
+NoColFn hp_bwd3_f16_2d_nocol, hp_bwd3_f16_3d_nocol, hp_bwd3_bf16_2d_nocol, hp_bwd3_bf16_3d_nocol, hp_bwd3_s32_f16_nocol,
+    hp_bwd3_s32_bf16_nocol;
 
 size_t hp_bwd3_lds_bytes(const Geom &g, const HpDims &hd) {
   const size_t region = (size_t)32 * (hd.Cp + 8) * 2 > (size_t)kB3ChunkRows * kPP * 2 ? (size_t)32 * (hd.Cp + 8) * 2
@@ -37,6 +43,16 @@ bool hp_bwd3_supported(const Geom &g, const HpDims &hd) {
 
 int hp_backward3_launch(const Geom &g, const HpDims &hd, int dtype, const Tensors &t, const void *xt,
                         const void *wpb, void *gcol, void *colbuf, int *cnt, hipStream_t stream) {
+  if (!colbuf) {   // no column rows: the plan of a call without weight gradients has no slot for them (hp_host.hip)
+    if (t.samp32)
+      return dtype == MDCONV_F16 ? hp_bwd3_s32_f16_nocol(g, hd, t, xt, wpb, gcol, cnt, stream)
+                                 : hp_bwd3_s32_bf16_nocol(g, hd, t, xt, wpb, gcol, cnt, stream);
+    if (dtype == MDCONV_F16)
+      return g.nd == 2 ? hp_bwd3_f16_2d_nocol(g, hd, t, xt, wpb, gcol, cnt, stream)
+                       : hp_bwd3_f16_3d_nocol(g, hd, t, xt, wpb, gcol, cnt, stream);
+    return g.nd == 2 ? hp_bwd3_bf16_2d_nocol(g, hd, t, xt, wpb, gcol, cnt, stream)
+                     : hp_bwd3_bf16_3d_nocol(g, hd, t, xt, wpb, gcol, cnt, stream);
+  }
   if (t.samp32)
     return dtype == MDCONV_F16 ? hp_bwd3_s32_f16(g, hd, t, xt, wpb, gcol, colbuf, cnt, stream)
                                : hp_bwd3_s32_bf16(g, hd, t, xt, wpb, gcol, colbuf, cnt, stream);

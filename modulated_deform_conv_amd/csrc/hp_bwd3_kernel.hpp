@@ -1,6 +1,7 @@
 // hp_bwd3_kernel.hpp -- pixel-stationary backward kernel of the native 16-bit path (gfx950): the kernel template and
 // its launch / dispatch templates.  Instantiated per (tensor type, rank) in hp_bwd3_{f16,bf16}_{2d,3d}.hip (four
-// translation units that compile side by side); the host side is hp_bwd3.hip.
+// translation units that compile side by side) and, without the column rows (COLS = false: a backward that wants no weight
+// gradients, MDCONV_FLAG_NO_GRAD_WEIGHT), in their *_nocol siblings; the host side is hp_bwd3.hip.
 //
 // Reference: mdeformable_conv.cu:412-444, 202-318; 3-D mdeformable_conv3d.cu:515-560, 265-395.
 // Per (tap, deformable group, pixel)
@@ -61,7 +62,11 @@ constexpr int kB3WRing2 = 8, kB3WRing3 = 4;   // kWG instances: A fragments in f
 
 // LPP: lanes per pixel of a deformable group (C_dg / 8); CBT: 32-channel blocks of ALL channels (Cp / 32)
 // SE: element type of offset / mask / grad_offset / grad_mask (T::Raw, or float for MDCONV_SAMPLING_F32)
-template <int ND, bool MOD, typename T, int LPP, int NKS, int CBT, typename SE = typename T::Raw>
+// COLS: build and store the column rows GEMM-2 reads.  false (no GEMM-2 follows): the column arithmetic of the gather
+// phase -- one multiply-add per corner and channel -- and one of the two 16-byte stores per lane are gone, `colbuf` is not
+// used; GEMM-1, the S sums and their reduction, the grad_col store, the counting atomics and the finish are the same
+// instructions on the same values, so grad_offset, grad_mask and the grad_col rows are those of the full kernel bit for bit.
+template <int ND, bool MOD, typename T, int LPP, int NKS, int CBT, typename SE = typename T::Raw, bool COLS = true>
 __global__ __launch_bounds__(256, 2) void hp_bwd3_kernel(
     Geom g, HpDims hd, const typename T::Raw *__restrict__ xt, const U4 *__restrict__ wpb,
     const typename T::Raw *__restrict__ gout, const SE *__restrict__ offset,
@@ -115,7 +120,7 @@ __global__ __launch_bounds__(256, 2) void hp_bwd3_kernel(
   const rsrc_t r_xt = make_rsrc(xt, (size_t)g.B * g.S_i * Cp * 2);
   const size_t gcol_img = (size_t)g.K * g.S_o * Cp;   // grad_col / column elements per image
   const rsrc_t r_gcol = make_rsrc(gcol + (size_t)b0 * gcol_img, gcol_img * 2);
-  const rsrc_t r_col = make_rsrc(colbuf + (size_t)b0 * gcol_img, gcol_img * 2);
+  const rsrc_t r_col = make_rsrc(COLS ? colbuf + (size_t)b0 * gcol_img : gcol, COLS ? gcol_img * 2 : 0);   // (!COLS: never used)
   const int S_e = hp_anchor_space(g);
 
   // ---- W^T slab of tap 0 -> LDS (whole workgroup) ----
@@ -333,7 +338,10 @@ __global__ __launch_bounds__(256, 2) void hp_bwd3_kernel(
     const U4 gq = *reinterpret_cast<const U4 *>(Gc + p * pitch + cho);
     float S[NC];
     U4 cq = {0, 0, 0, 0};
-    if constexpr (T::kPackedCol) {
+    if constexpr (!COLS) {
+#pragma unroll
+      for (int ci = 0; ci < NC; ++ci) S[ci] = dot8<T>(0.f, s.x[ci], gq);
+    } else if constexpr (T::kPackedCol) {
 #pragma unroll
       for (int ci = 0; ci < NC; ++ci) {
         S[ci] = dot8<T>(0.f, s.x[ci], gq);
@@ -352,11 +360,11 @@ __global__ __launch_bounds__(256, 2) void hp_bwd3_kernel(
     }
     if (one_img) {   // scalar row base, dead pixels out of range (dropped)
       buf_store4u_nt(r_gcol, tail.x + cho * 2, 0, gq);
-      buf_store4u_nt(r_col, tail.x + cho * 2, 0, cq);
+      if constexpr (COLS) buf_store4u_nt(r_col, tail.x + cho * 2, 0, cq);
     } else if (tail.x != kHpOob) {
       const size_t e = (size_t)tail.y * gcol_img + (tail.x >> 1) + cho;
       *reinterpret_cast<U4 *>(gcol + e) = gq;
-      *reinterpret_cast<U4 *>(colbuf + e) = cq;
+      if constexpr (COLS) *reinterpret_cast<U4 *>(colbuf + e) = cq;
     }
     // S summed over the pixel's LPP lanes: DPP adds inside a row of 16, ds_bpermute beyond
     hp_dpp_sum<NC>(S, LPP < 16 ? LPP : 16);
@@ -467,28 +475,29 @@ __global__ __launch_bounds__(256, 2) void hp_bwd3_kernel(
 
 size_t hp_bwd3_lds_bytes(const Geom &g, const HpDims &hd);   // hp_bwd3.hip
 
-template <int ND, bool MOD, typename T, int LPP, int NKS, int CBT, typename SE>
+template <int ND, bool MOD, typename T, int LPP, int NKS, int CBT, typename SE, bool COLS>
 int launch_bwd3(const Geom &g, const HpDims &hd, const Tensors &t, const void *xt, const void *wpb,
                 void *gcol, void *colbuf, int *cnt, hipStream_t stream) {
   using Raw = typename T::Raw;
   const size_t lds = hp_bwd3_lds_bytes(g, hd);
   if (lds > 64 * 1024) {
-    hipError_t ea = hipFuncSetAttribute((const void *)hp_bwd3_kernel<ND, MOD, T, LPP, NKS, CBT, SE>,
+    hipError_t ea = hipFuncSetAttribute((const void *)hp_bwd3_kernel<ND, MOD, T, LPP, NKS, CBT, SE, COLS>,
                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (ea != hipSuccess) { set_error("hipFuncSetAttribute: %s", hipGetErrorString(ea)); return MDCONV_ELAUNCH; }
   }
-  hp_debug_plan("hp_bwd3", hp_bwd3_kernel<ND, MOD, T, LPP, NKS, CBT, SE>, 256, lds, (g.N + 127) / 128);
-  hipLaunchKernelGGL((hp_bwd3_kernel<ND, MOD, T, LPP, NKS, CBT, SE>), dim3((g.N + 127) / 128), dim3(256), lds, stream, g, hd,
+  hp_debug_plan("hp_bwd3", hp_bwd3_kernel<ND, MOD, T, LPP, NKS, CBT, SE, COLS>, 256, lds, (g.N + 127) / 128);
+  hipLaunchKernelGGL((hp_bwd3_kernel<ND, MOD, T, LPP, NKS, CBT, SE, COLS>), dim3((g.N + 127) / 128), dim3(256), lds, stream, g, hd,
                      (const Raw *)xt, (const U4 *)wpb, (const Raw *)t.grad_output, (const SE *)t.offset,
                      (const SE *)t.mask, (Raw *)gcol, (Raw *)colbuf, (SE *)t.grad_offset, (SE *)t.grad_mask, cnt);
   return check_launch("hp_bwd3");
 }
 
 // (Cp, deformable groups) -> (LPP, CBT): LPP = C_dg / 8 lanes per pixel of a group, CBT = Cp / 32
-template <int ND, bool MOD, typename T, typename SE = typename T::Raw>
+// COLS = false: the variant without column rows (`colbuf` is not used)
+template <int ND, bool MOD, typename T, typename SE = typename T::Raw, bool COLS = true>
 int dispatch_bwd3(const Geom &g, const HpDims &hd, const Tensors &t, const void *xt, const void *wpb,
                   void *gcol, void *colbuf, int *cnt, hipStream_t stream) {
-#define HP_B3(L, N, C) return launch_bwd3<ND, MOD, T, L, N, C, SE>(g, hd, t, xt, wpb, gcol, colbuf, cnt, stream)
+#define HP_B3(L, N, C) return launch_bwd3<ND, MOD, T, L, N, C, SE, COLS>(g, hd, t, xt, wpb, gcol, colbuf, cnt, stream)
 #define HP_B3_L(L, C)                                                              \
   switch (hd.nks) {                                                                \
     case 2: HP_B3(L, 2, C);                                                        \

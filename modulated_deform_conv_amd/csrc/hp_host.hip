@@ -132,12 +132,20 @@ BwdNeed bwd_need(const HpChunk &c, int ranges, int dtype, bool two_pass_gather) 
 }
 
 // the layout of a call, made for its full chunk
-HpBwdLayout bwd_layout(const HpChunk &c, int dtype, bool two_pass_gather) {
+// `skip`: without weight gradients no column rows (hp_bwd3 runs its variant without them), no running grad_weight, and
+// no partials unless a chunk runs a kernel with GEMM-2 fused in (`fused_partials`: hp_bwd2 / hp_bwd write and discard them);
+// without grad_input no row pointers, entries, partial sums or sort scratch -- the counters stay, the kernels count into them
+HpBwdLayout bwd_layout(const HpChunk &c, int dtype, bool two_pass_gather, Skip skip = Skip(), bool fused_partials = true) {
   const Geom &gc = c.gc;
   const HpDims &hd = c.hd;
   // a shorter last chunk can have MORE ranges than a full one (ranges is not monotonic in the tile
   // count), so the partials are sized for the bound; gw32 = running fp32 grad_weight over chunks
-  const BwdNeed n = bwd_need(c, hd.max_ranges, dtype, two_pass_gather);
+  BwdNeed n = bwd_need(c, hd.max_ranges, dtype, two_pass_gather);
+  if (skip.weight) {
+    n.col = 0;
+    if (!fused_partials) n.part = 0;
+  }
+  if (skip.input) n.rowptr = n.entries = n.sums = n.sort = 0;
   HpBwdLayout L;
   Bump b;
   L.off_xt = b.take(n.xt);
@@ -146,7 +154,7 @@ HpBwdLayout bwd_layout(const HpChunk &c, int dtype, bool two_pass_gather) {
   L.off_gcol = b.take(n.gcol);
   L.off_col = b.take(n.col);
   L.off_part = b.take(n.part);
-  L.off_gw32 = b.take((size_t)gc.O * gc.Cg * gc.K * sizeof(float));
+  L.off_gw32 = b.take(skip.weight ? 0 : (size_t)gc.O * gc.Cg * gc.K * sizeof(float));
   L.off_cnt = b.take(n.cnt);
   L.off_rowptr = b.take(n.rowptr);
   L.off_entries = b.take(n.entries);
@@ -362,7 +370,7 @@ static bool forward_preferred(const Geom &gcall, const Geom &g, int dtype) {
   return !mfma_supported(gcall, dtype, false);
 }
 
-bool hp_plan(const Geom &gcall, int dtype, bool backward, HpPlan *p) {
+bool hp_plan(const Geom &gcall, int dtype, bool backward, HpPlan *p, Skip skip) {
   // the geometry the kernels run: the caller's -- or, in the backward, its width-padded form where the full chunk of THAT
   // takes hp_bwd3 --, else the group-padded form
   Geom gv;
@@ -377,6 +385,7 @@ bool hp_plan(const Geom &gcall, int dtype, bool backward, HpPlan *p) {
   p->forward_preferred = backward || forward_preferred(gcall, p->g, dtype);
   p->fwd = HpFwdLayout();
   p->bwd = HpBwdLayout();
+  p->skip = Skip();
   if (!backward) {
     p->fwd = fwd_layout(p->full.gc, p->full.hd);
     p->total = p->fwd.total;
@@ -390,6 +399,14 @@ bool hp_plan(const Geom &gcall, int dtype, bool backward, HpPlan *p) {
       set_error("hp_plan: the %s of a chunk of %d images do not fit the slot laid out for chunks of %d", slot, c->gc.B, p->Bc);
       return false;
     }
+  }
+  // a selective backward: decided and checked as the full call above (same answer, same chunks, same kernels), then laid out
+  // again without the slots of the stages it leaves out -- every slot that stays keeps the size just checked
+  p->skip = skip;
+  if (skip.input || skip.weight) {
+    const bool fused = p->full.bwd != HpChunk::BWD3 || p->tail.bwd != HpChunk::BWD3;   // a chunk writes fp32 partials itself
+    p->bwd = bwd_layout(p->full, dtype, p->two_pass_gather, skip, fused);
+    p->total = p->bwd.total;
   }
   return true;
 }
@@ -436,10 +453,11 @@ int hp_backward(int dtype, const HpPlan &p, const Tensors &t, void *ws, hipStrea
   char *base = (char *)ws;
   const int nc_off = g.DG * g.nd * g.K, nc_m = g.DG * g.K;
   const size_t es_s = samp_bytes(dtype, t);   // offset / mask element: 2, or 4 with fp32 sampling
+  const Skip skip = p.skip;
   int rc;
   if ((rc = hp_pack_bwd_weights(p.full.gc, p.full.hd, dtype, t.weight, base + L.off_w, (int4 *)(base + L.off_tab), stream)))
     return rc;
-  if (g.with_bias && (rc = hp_grad_bias(g, dtype, t.grad_output, t.grad_bias, t.wgrad32 != 0, stream))) return rc;
+  if (g.with_bias && !skip.weight && (rc = hp_grad_bias(g, dtype, t.grad_output, t.grad_bias, t.wgrad32 != 0, stream))) return rc;
   for (int b0 = 0; b0 < g.B; b0 += Bc) {
     const int bc = g.B - b0 < Bc ? g.B - b0 : Bc;
     const HpChunk &c = bc == Bc ? p.full : p.tail;
@@ -451,7 +469,7 @@ int hp_backward(int dtype, const HpPlan &p, const Tensors &t, void *ws, hipStrea
     tc.offset = (const char *)t.offset + (size_t)b0 * nc_off * g.S_o * es_s;
     tc.mask = t.mask ? (const char *)t.mask + (size_t)b0 * nc_m * g.S_o * es_s : nullptr;
     tc.grad_output = (const char *)t.grad_output + (size_t)b0 * g.O * g.S_o * 2;
-    tc.grad_input = (char *)t.grad_input + (size_t)b0 * caller_channels(g) * g.S_i * 2;
+    tc.grad_input = skip.input ? nullptr : (char *)t.grad_input + (size_t)b0 * caller_channels(g) * g.S_i * 2;
     tc.grad_offset = (char *)t.grad_offset + (size_t)b0 * nc_off * g.S_o * es_s;
     tc.grad_mask = t.grad_mask ? (char *)t.grad_mask + (size_t)b0 * nc_m * g.S_o * es_s : nullptr;
     int *cnt = (int *)(base + L.off_cnt), *rowptr = (int *)(base + L.off_rowptr);
@@ -461,8 +479,9 @@ int hp_backward(int dtype, const HpPlan &p, const Tensors &t, void *ws, hipStrea
     if ((rc = hp_csr_zero(gc, cnt, stream))) return rc;
     const bool bwd3 = c.bwd == HpChunk::BWD3, bwd2 = c.bwd == HpChunk::BWD2;   // (the plan checked this chunk's slots)
     profile_mark(1, true, stream, bwd3 ? "hp_bwd3_kernel" : (bwd2 ? "hp_bwd2_kernel" : "hp_bwd_kernel"));
-    if (bwd3)
-      rc = hp_backward3_launch(gc, hd, dtype, tc, xt, base + L.off_w, base + L.off_gcol, base + L.off_col, cnt, stream);
+    if (bwd3)   // (without weight gradients: the variant that neither builds nor stores the column rows)
+      rc = hp_backward3_launch(gc, hd, dtype, tc, xt, base + L.off_w, base + L.off_gcol, skip.weight ? nullptr : base + L.off_col,
+                               cnt, stream);
     else if (bwd2)
       rc = hp_backward2_launch(gc, hd, dtype, tc, xt, base + L.off_w,
                                (const int4 *)(base + L.off_tab), base + L.off_gcol,
@@ -478,7 +497,9 @@ int hp_backward(int dtype, const HpPlan &p, const Tensors &t, void *ws, hipStrea
     // alone streams at ~3.6 TB/s; forked (mfma_kernels.hpp) they share the chip: cfg5 backward 5.94 -> 5.85 ms
     // (GEMM-2 1.0 -> 1.5 ms beside the gather).  Only where GEMM-2 is its own kernel: with the fused backward
     // the weight tail is one 27 us reduction and the fork's two cross-stream waits cost as much (cfg3).
-    hipStream_t gs = bwd3 ? fork_side_stream(stream) : nullptr;
+    // A selective backward has one tail, or none: nothing to fork.  (hp_bwd2 / hp_bwd chunks of a call without weight
+    // gradients have GEMM-2 fused in: their partials stay in the workspace, unreduced.)
+    hipStream_t gs = bwd3 && !skip.input && !skip.weight ? fork_side_stream(stream) : nullptr;
     const bool forked = gs != nullptr;
     if (!forked) gs = stream;
     auto weight_tail = [&]() -> int {
@@ -496,7 +517,8 @@ int hp_backward(int dtype, const HpPlan &p, const Tensors &t, void *ws, hipStrea
         return r;
       return last ? record_weight_ready(stream) : MDCONV_OK;
     };
-    if (!forked && (rc = weight_tail())) return rc;
+    if (!forked && !skip.weight && (rc = weight_tail())) return rc;
+    if (skip.input) continue;
     rc = hp_csr_build(gc, dtype, tc, cnt, rowptr, base + L.off_entries, gs);
     // deterministic mode: the lists in canonical order before the gather sums them (on the gather's stream)
     if (!rc && gc.det)

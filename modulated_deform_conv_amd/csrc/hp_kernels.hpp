@@ -49,7 +49,8 @@ int hp_backward2_launch_s32(const Geom &g, const HpDims &hd, int dtype, const Te
                             hipStream_t stream);   // hp_bwd2_s32.hip
 
 // hp_bwd3.hip: pixel-stationary GEMM-1 + coordinate gradients + grad_col rows + column rows (GEMM-2 is
-// hp_gemm2.hip); one conv group, 1 / 2 / 4 deformable groups, Cp a power of two
+// hp_gemm2.hip); one conv group, 1 / 2 / 4 deformable groups, Cp a power of two.  colbuf == nullptr (no GEMM-2 follows:
+// MDCONV_FLAG_NO_GRAD_WEIGHT) launches the variant of the kernel that neither builds nor stores the column rows.
 bool hp_bwd3_supported(const Geom &g, const HpDims &hd);
 size_t hp_bwd3_lds_bytes(const Geom &g, const HpDims &hd);
 int hp_backward3_launch(const Geom &g, const HpDims &hd, int dtype, const Tensors &t, const void *xt,

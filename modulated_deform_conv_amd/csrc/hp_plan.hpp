@@ -29,9 +29,13 @@ struct HpPlan {
   bool two_pass_gather;    // grad_input gather in two passes (MDCONV_HP_C2I, default) or one
   bool forward_preferred;  // forward only: false = a few pixel tiles over many K stages, the fp32 matrix kernels are faster
   size_t total;            // workspace bytes
+  // backward: gradients the call leaves out (MDCONV_FLAG_NO_GRAD_INPUT / _WEIGHT).  Their stages are not run -- GEMM-2, the
+  // split-K reduce and grad_bias; the list build, the sort and the gather -- and the slots only those stages use take no
+  // bytes; hp_bwd3 chunks of a call without weight gradients run the kernel's variant without column rows.
+  Skip skip;
 };
-// false: the family does not take the call
-bool hp_plan(const Geom &g, int dtype, bool backward, HpPlan *p);
+// false: the family does not take the call.  `skip` never changes the answer, the geometry, the chunks or their kernels.
+bool hp_plan(const Geom &g, int dtype, bool backward, HpPlan *p, Skip skip = Skip());
 int hp_forward(int dtype, const HpPlan &p, const Tensors &t, void *ws, hipStream_t stream);
 int hp_backward(int dtype, const HpPlan &p, const Tensors &t, void *ws, hipStream_t stream);
 

@@ -69,9 +69,10 @@ static int current_path() {
 static int desc_ndim(const mdconv_desc *d) { return d->ndim & ~MDCONV_DESC_V2; }
 
 // Call modes of one call: from the descriptor (ABI v2) or from the v1 setters of the calling thread / process.
-struct Modes { int accumulate, input_layout, path, deterministic; };
+struct Modes { int accumulate, input_layout, path, deterministic; Skip skip; };
 static int call_modes(const mdconv_desc *d, Modes *m) {
-  m->deterministic = 0;   // v1 descriptors end before the flag word: they never request the mode
+  m->deterministic = 0;   // v1 descriptors end before the flag word: they never request a flag
+  m->skip = Skip();
   if (!(d->ndim & MDCONV_DESC_V2)) {
     m->accumulate = g_accumulate;
     m->input_layout = g_input_layout;
@@ -90,12 +91,16 @@ static int call_modes(const mdconv_desc *d, Modes *m) {
       set_error("mdconv_desc.reserved must be 0");
       return MDCONV_EINVAL;
     }
-  if (d->reserved[4] & ~MDCONV_FLAG_DETERMINISTIC) {
-    set_error("unknown bits 0x%x in the flags word of the descriptor (mdconv_desc.reserved[4]); MDCONV_FLAG_DETERMINISTIC is the only flag",
-              (unsigned)(d->reserved[4] & ~MDCONV_FLAG_DETERMINISTIC));
+  const int known = MDCONV_FLAG_DETERMINISTIC | MDCONV_FLAG_NO_GRAD_INPUT | MDCONV_FLAG_NO_GRAD_WEIGHT;
+  if (d->reserved[4] & ~known) {
+    set_error("unknown bits 0x%x in the flags word of the descriptor (mdconv_desc.reserved[4]); the flags are "
+              "MDCONV_FLAG_DETERMINISTIC (1), MDCONV_FLAG_NO_GRAD_INPUT (4) and MDCONV_FLAG_NO_GRAD_WEIGHT (8)",
+              (unsigned)(d->reserved[4] & ~known));
     return MDCONV_EINVAL;
   }
   m->deterministic = (d->reserved[4] & MDCONV_FLAG_DETERMINISTIC) ? 1 : 0;
+  m->skip.input = (d->reserved[4] & MDCONV_FLAG_NO_GRAD_INPUT) != 0;
+  m->skip.weight = (d->reserved[4] & MDCONV_FLAG_NO_GRAD_WEIGHT) != 0;
   m->accumulate = d->accumulate;
   m->input_layout = d->input_layout;
   m->path = d->path == MDCONV_PATH_AUTO ? current_path() : d->path;
@@ -254,15 +259,23 @@ struct CallPlan {
   MfmaPlan f32;      // ROUTE_F32
   S32Plan s32;       // ROUTE_*_SAMP32
   D16Plan d16;       // ROUTE_DIRECT_16
+  Skip skip;         // backward: gradients the call leaves out
+  size_t scratch_gi; // ROUTE_DIRECT with skip.input: bytes of the grad_input scratch (the route's whole workspace)
 };
 static bool route_is_direct(Route r) { return r == ROUTE_DIRECT || r == ROUTE_DIRECT_16 || r == ROUTE_DIRECT_SAMP32; }
 
 // `g` with in_cl and det set; `dt` the tensors' element type, `s32` fp32 offsets / masks, `path` the caller's MDCONV_PATH_*.
 // `wg32` (fp32 grad_weight / grad_bias of a 16-bit backward) never changes the route: only the fp32 matrix family's padded /
 // sliced plans hold grad_weight rows in the caller's element size, and size them for it.
-static void plan_call(const Geom &g, int dt, int s32, int wg32, int path, bool backward, CallPlan *cp) {
+// `skip` (a backward without grad_input / without the weight gradients) never changes the route either: the plans drop the
+// stages and workspace slots of the skipped gradients, and the shape-generic data kernel scatters an unwanted grad_input
+// into scratch (CallPlan::scratch_gi, appended to the route's workspace).
+static void plan_call(const Geom &g, int dt, int s32, int wg32, int path, bool backward, CallPlan *cp, Skip skip = Skip()) {
   const bool half = dt == MDCONV_F16 || dt == MDCONV_BF16;
-  const bool hp = path != MDCONV_PATH_DIRECT && hp_plan(g, dt, backward, &cp->hp);
+  if (!backward) skip = Skip();
+  cp->skip = skip;
+  cp->scratch_gi = 0;
+  const bool hp = path != MDCONV_PATH_DIRECT && hp_plan(g, dt, backward, &cp->hp, skip);
   cp->refused = g.in_cl && !(hp && g.C % 32 == 0) ? REFUSE_CHANNELS_LAST : REFUSE_NONE;
   const size_t hp_bytes = hp ? cp->hp.total : 0;
   // 16-bit forwards of a few tiles run faster on the fp32 kernels (HpPlan::forward_preferred)
@@ -277,9 +290,9 @@ static void plan_call(const Geom &g, int dt, int s32, int wg32, int path, bool b
   bool mfma = false;
   if (path != MDCONV_PATH_DIRECT) {
     if (s32) {
-      if (mfma_supported(g, dt, backward)) samp32_plan(g, backward, true, &cp->s32), mfma = cp->s32.mfma;
+      if (mfma_supported(g, dt, backward)) samp32_plan(g, backward, true, &cp->s32, skip), mfma = cp->s32.mfma;
     } else {
-      mfma = mfma_plan(g, dt, backward, &cp->f32, wg32 != 0);
+      mfma = mfma_plan(g, dt, backward, &cp->f32, wg32 != 0, skip);
     }
   }
   if (mfma) {
@@ -287,7 +300,7 @@ static void plan_call(const Geom &g, int dt, int s32, int wg32, int path, bool b
     cp->bytes = s32 ? cp->s32.total : cp->f32.total;
   } else if (s32) {
     cp->route = ROUTE_DIRECT_SAMP32;
-    samp32_plan(g, backward, false, &cp->s32);
+    samp32_plan(g, backward, false, &cp->s32, skip);
     cp->bytes = cp->s32.total;
   } else if (backward && half) {   // 16-bit atomics round at every add: fp32 copies for the scatter kernels
     cp->route = ROUTE_DIRECT_16;
@@ -295,7 +308,9 @@ static void plan_call(const Geom &g, int dt, int s32, int wg32, int path, bool b
     cp->bytes = cp->d16.total;
   } else {
     cp->route = ROUTE_DIRECT;
-    cp->bytes = 0;
+    // the fused data kernel scatters grad_input whether it is wanted or not: scratch of the tensor's size for it
+    if (skip.input) cp->scratch_gi = (size_t)g.B * g.C * g.S_i * (dt == MDCONV_F64 ? 8 : (dt == MDCONV_F32 ? 4 : 2));
+    cp->bytes = cp->scratch_gi;
   }
   cp->reported = cp->bytes;
   if (few_tile) {
@@ -414,14 +429,19 @@ static int run_backward(const mdconv_desc *d, int nd, int modulated, Tensors t, 
   }
   Modes md;
   if ((rc = call_modes(d, &md))) return rc;
+  const Skip skip = md.skip;
+  // a skipped gradient's pointers are neither required nor used: the call goes on as if they were NULL
+  if (skip.input) t.grad_input = nullptr;
+  if (skip.weight) t.grad_weight = t.grad_bias = nullptr;
   if ((rc = require(t.input, "input")) || (rc = require(t.weight, "weight")) ||
       (rc = require(t.offset, "offset")) || (rc = require(t.grad_output, "grad_output")) ||
-      (rc = require(t.grad_input, "grad_input")) || (rc = require(t.grad_weight, "grad_weight")) ||
+      (!skip.input && (rc = require(t.grad_input, "grad_input"))) ||
+      (!skip.weight && (rc = require(t.grad_weight, "grad_weight"))) ||
       (rc = require(t.grad_offset, "grad_offset")))
     return rc;
   if (modulated && ((rc = require(t.mask, "mask")) || (rc = require(t.grad_mask, "grad_mask"))))
     return rc;
-  if (g.with_bias && (rc = require(t.grad_bias, "grad_bias"))) return rc;
+  if (g.with_bias && !skip.weight && (rc = require(t.grad_bias, "grad_bias"))) return rc;
   hipStream_t s = (hipStream_t)stream;
   g.acc_data = g.acc_w = md.accumulate;
   const int path = md.path;
@@ -431,10 +451,16 @@ static int run_backward(const mdconv_desc *d, int nd, int modulated, Tensors t, 
   g.in_cl = md.input_layout == MDCONV_LAYOUT_CHANNELS_LAST ? 1 : 0;
   g.det = md.deterministic;
   CallPlan cp;
-  plan_call(g, dt, s32, t.wgrad32, path, true, &cp);
+  plan_call(g, dt, s32, t.wgrad32, path, true, &cp, skip);
   if (cp.refused) return refuse(cp, g, dt, path);
+  // the workspace check; without weight gradients there is nothing to wait for, so the weights-ready event goes in front
+  // of the call's first kernel
+  auto ready = [&]() -> int {
+    const int r = check_ws(ws, ws_bytes, cp.bytes);
+    return r || !skip.weight ? r : record_weight_ready(s);
+  };
   if (cp.route == ROUTE_HP) {
-    if ((rc = check_ws(ws, ws_bytes, cp.bytes))) return rc;
+    if ((rc = ready())) return rc;
     g_last_path = MDCONV_PATH_MFMA;
     g_last_kernels = MDCONV_KERNELS_HP;
     return hp_backward(dt, cp.hp, t, ws, s);
@@ -442,35 +468,32 @@ static int run_backward(const mdconv_desc *d, int nd, int modulated, Tensors t, 
   if (cp.route == ROUTE_F32 || cp.route == ROUTE_F32_SAMP32) {
     g_last_path = MDCONV_PATH_MFMA;
     g_last_kernels = MDCONV_KERNELS_F32;
-    if ((rc = check_ws(ws, ws_bytes, cp.bytes))) return rc;
+    if ((rc = ready())) return rc;
     if (cp.route == ROUTE_F32_SAMP32) return samp32_backward(g, dt, cp.s32, t, ws, s);
     return mfma_backward(g, dt, cp.f32, t, ws, s);
   }
   g_last_path = MDCONV_PATH_DIRECT;
   g_last_kernels = MDCONV_KERNELS_DIRECT;
   note_direct_fallback(g, dt, true, path);
-  if (cp.route == ROUTE_DIRECT_SAMP32) {
-    if ((rc = check_ws(ws, ws_bytes, cp.bytes))) return rc;
-    return samp32_backward(g, dt, cp.s32, t, ws, s);
-  }
+  if ((rc = ready())) return rc;
+  if (cp.route == ROUTE_DIRECT_SAMP32) return samp32_backward(g, dt, cp.s32, t, ws, s);
   if (cp.route == ROUTE_DIRECT_16) {
-    if ((rc = check_ws(ws, ws_bytes, cp.bytes))) return rc;
-    if ((rc = direct16_backward(g, dt, cp.d16, t, ws, s))) return rc;
-    return record_weight_ready(s);
+    if ((rc = direct16_backward(g, dt, cp.d16, t, ws, s, skip))) return rc;
+    return skip.weight ? MDCONV_OK : record_weight_ready(s);
   }
+  if (skip.input) t.grad_input = ws;   // scratch: scattered into, never read (CallPlan::scratch_gi)
   if (!md.accumulate) {
     // the direct kernels scatter with atomics, so "overwrite" means: clear first
     const size_t es = dt == MDCONV_F64 ? 8 : (dt == MDCONV_F32 ? 4 : 2);
     const size_t n_off = (size_t)g.B * g.DG * g.nd * g.K * g.S_o, n_m = (size_t)g.B * g.DG * g.K * g.S_o;
-    if ((rc = zero_bytes(t.grad_input, (size_t)g.B * g.C * g.S_i * es, s)) ||
-        (rc = zero_bytes(t.grad_offset, n_off * es, s)) ||
-        (rc = zero_bytes(t.grad_weight, (size_t)g.O * g.Cg * g.K * es, s)))
-      return rc;
+    if (!skip.input && (rc = zero_bytes(t.grad_input, (size_t)g.B * g.C * g.S_i * es, s))) return rc;
+    if ((rc = zero_bytes(t.grad_offset, n_off * es, s))) return rc;
+    if (!skip.weight && (rc = zero_bytes(t.grad_weight, (size_t)g.O * g.Cg * g.K * es, s))) return rc;
     if (modulated && (rc = zero_bytes(t.grad_mask, n_m * es, s))) return rc;
-    if (g.with_bias && (rc = zero_bytes(t.grad_bias, (size_t)g.O * es, s))) return rc;
+    if (g.with_bias && !skip.weight && (rc = zero_bytes(t.grad_bias, (size_t)g.O * es, s))) return rc;
   }
-  if ((rc = direct_backward(g, dt, t, s))) return rc;
-  return record_weight_ready(s);
+  if ((rc = direct_backward(g, dt, t, s, skip.weight ? 1 : 3))) return rc;
+  return skip.weight ? MDCONV_OK : record_weight_ready(s);
 }
 
 int record_weight_ready(hipStream_t stream) {
@@ -554,7 +577,7 @@ size_t mdconv_workspace_bytes(const mdconv_desc *d, int backward) {
   g.in_cl = md.input_layout == MDCONV_LAYOUT_CHANNELS_LAST ? 1 : 0;   // (the plan of a channels-last call, where the caller says so)
   g.det = backward ? md.deterministic : 0;   // the list sort's scratch (backward on the matrix-core kernels only)
   CallPlan cp;
-  plan_call(g, base_dtype(d), sampling_f32(d), wgrad_f32(d, backward != 0), md.path, backward != 0, &cp);
+  plan_call(g, base_dtype(d), sampling_f32(d), wgrad_f32(d, backward != 0), md.path, backward != 0, &cp, md.skip);
   return cp.reported;
 }
 

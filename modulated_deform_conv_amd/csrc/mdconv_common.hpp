@@ -441,6 +441,13 @@ inline size_t wgrad_bytes(int dtype, const Tensors &t) {
   return t.wgrad32 ? 4 : (dtype == MDCONV_F64 ? 8 : (dtype == MDCONV_F32 ? 4 : 2));
 }
 
+// Gradients a backward call leaves out (MDCONV_FLAG_NO_GRAD_INPUT / MDCONV_FLAG_NO_GRAD_WEIGHT): host-side state of the
+// plans (never in Geom, which is a kernel argument).  The matching pointers of `Tensors` may be NULL and are not touched.
+struct Skip {
+  bool input = false;    // no grad_input
+  bool weight = false;   // no grad_weight, no grad_bias
+};
+
 // direct (VALU) path, any shape / dtype
 int direct_forward(const Geom &g, int dtype, const Tensors &t, hipStream_t stream);
 // parts: bit 0 = grad_input/grad_offset/grad_mask kernel, bit 1 = grad_weight/grad_bias kernel

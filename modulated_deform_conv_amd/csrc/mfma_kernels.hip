@@ -68,7 +68,10 @@ int pack_weights_f32(const Geom &g, const PackDims &pd, const float *weight, flo
   return check_launch("pack_weights");
 }
 
-BwdDims bwd_dims(const Geom &g) {
+// `skip`: a backward without grad_input / without the weight gradients -- the slots only the skipped stages write take no
+// bytes; everything GEMM-1 and the requested stages use (tiling, split-K count, the slots GEMM-1 itself writes) is unchanged,
+// so the requested gradients are the same sums in the same order
+BwdDims bwd_dims(const Geom &g, Skip skip) {
   BwdDims bd;
   bd.Np = (g.N + 31) / 32 * 32;
   // 64 x 64 tiles (all four waves busy when C_out <= 64) were measured SLOWER than 256 x 32 tiles
@@ -152,26 +155,27 @@ BwdDims bwd_dims(const Geom &g) {
   bd.off_wq = off;   off += align_up((size_t)g.K * bd.ochunks * bd.cblks_q * 2 * 64 * 16);
   bd.off_ga = off;   off += align_up((size_t)bd.Np * bd.OgpB * sizeof(float));
   bd.off_table = off; off += align_up((size_t)g.DG * g.K * bd.Np * 2 * (1 << g.nd) * sizeof(int));
-  bd.off_part = off; off += align_up((size_t)bd.splits * g.K * bd.OgpB * bd.Cp * sizeof(float));
+  bd.off_part = off; off += skip.weight ? 0 : align_up((size_t)bd.splits * g.K * bd.OgpB * bd.Cp * sizeof(float));
   bd.off_gcol = off; off += align_up((size_t)g.B * g.C * g.K * g.S_o * sizeof(float));
   // scatter lists: 2-D one entry per corner pair keyed by the pair's first pixel; 3-D one entry per
   // sample keyed by its low corner in the extended anchor space (4x fewer entries and atomics)
   bd.sample_keyed = g.nd == 3 ? 1 : 0;
   bd.S_e = bd.sample_keyed ? hp_anchor_space(g) : g.S_i;
   bd.off_cnt = off;  off += align_up((size_t)g.B * g.DG * bd.S_e * sizeof(int));
-  bd.off_rowptr = off; off += align_up((size_t)g.B * g.DG * (bd.S_e + 1) * sizeof(int));
-  bd.off_entries = off; off += align_up((size_t)g.B * g.DG * g.K * g.S_o * (bd.sample_keyed ? 32 : (nc / 2) * 16));
+  // (the counters stay with NO_GRAD_INPUT: GEMM-1's counting pass writes them)
+  bd.off_rowptr = off; off += skip.input ? 0 : align_up((size_t)g.B * g.DG * (bd.S_e + 1) * sizeof(int));
+  bd.off_entries = off; off += skip.input ? 0 : align_up((size_t)g.B * g.DG * g.K * g.S_o * (bd.sample_keyed ? 32 : (nc / 2) * 16));
   bd.bias_tiles = (g.N + 32 * (4 / bd.waves_c) - 1) / (32 * (4 / bd.waves_c));
   bd.off_bias = off; off += align_up((size_t)bd.bias_tiles * g.O * sizeof(float));
   bd.off_xt = off;   off += bd.cl ? align_up((size_t)g.B * g.S_i * g.C * sizeof(float)) : 0;
   static const int c2i_env = getenv("MDCONV_C2I3D") ? atoi(getenv("MDCONV_C2I3D")) : 2;
   bd.two_pass = bd.sample_keyed && c2i_env >= 2 ? 1 : 0;
-  bd.off_sums = off; off += bd.two_pass ? align_up(col2im3d_sums_bytes(g)) : 0;
-  bd.off_bstage = off; off += g.with_bias ? align_up(grad_bias_stage_bytes(g)) : 0;
+  bd.off_sums = off; off += bd.two_pass && !skip.input ? align_up(col2im3d_sums_bytes(g)) : 0;
+  bd.off_bstage = off; off += g.with_bias && !skip.weight ? align_up(grad_bias_stage_bytes(g)) : 0;
   // deterministic mode: scratch of the list sort, shaped like the entries (csr_sort.hip); after everything else, so the
   // default layout is untouched
   bd.off_sort = off;
-  off += g.det ? align_up(csr_sort_scratch_bytes(bd.sample_keyed ? 2 : 1, (int64_t)g.K * g.S_o * (bd.sample_keyed ? 1 : nc / 2),
+  off += g.det && !skip.input ? align_up(csr_sort_scratch_bytes(bd.sample_keyed ? 2 : 1, (int64_t)g.K * g.S_o * (bd.sample_keyed ? 1 : nc / 2),
                                                  g.B * g.DG)) : 0;
   bd.off_end = off;
   return bd;
@@ -201,7 +205,7 @@ size_t fwd_core_bytes(const Geom &gc) {
 }
 
 // chunking and workspace layout of a shape the kernels tile (native_plan)
-bool make_plan(const Geom &g, int dtype, bool backward, Plan *p) {
+bool make_plan(const Geom &g, int dtype, bool backward, Skip skip, Plan *p) {
   const size_t per_in = (size_t)g.C * g.S_i * 4, per_out = (size_t)g.O * g.S_o * 4;
   const size_t per_col = (size_t)g.C * g.K * g.S_o * 4;
   size_t per = per_in > per_out ? per_in : per_out;
@@ -224,8 +228,9 @@ bool make_plan(const Geom &g, int dtype, bool backward, Plan *p) {
   if (bc > g.B) bc = g.B;
   p->Bc = bc;
   p->half_io = dtype == MDCONV_F16 || dtype == MDCONV_BF16;
+  p->skip = backward ? skip : Skip();
   p->gc = chunk_geom(g, bc);
-  if (backward) p->bd = bwd_dims(p->gc);
+  if (backward) p->bd = bwd_dims(p->gc, skip);
   p->core_bytes = backward ? p->bd.off_end : fwd_core_bytes(p->gc);
   // A shorter last chunk lays its workspace out anew (bwd_dims per chunk) and can need MORE than a full one: below the
   // channels-last threshold GEMM-2 pads its rows to 256 output channels and its split-K partials grow (C = O = 64 at
@@ -235,7 +240,7 @@ bool make_plan(const Geom &g, int dtype, bool backward, Plan *p) {
   // here -- one image, the full chunk, the tail; the chunks that are launched run with these layouts.)
   if (g.B % bc) {
     const Geom gt = chunk_geom(g, g.B % bc);
-    if (backward) p->bd_tail = bwd_dims(gt);
+    if (backward) p->bd_tail = bwd_dims(gt, skip);
     const size_t tail_bytes = backward ? p->bd_tail.off_end : fwd_core_bytes(gt);
     if (tail_bytes > p->core_bytes) p->core_bytes = tail_bytes;
   }
@@ -254,11 +259,11 @@ bool make_plan(const Geom &g, int dtype, bool backward, Plan *p) {
       p->off_out = ws.take(n_o);
     } else {
       p->off_go = ws.take(n_o);
-      p->off_gi = ws.take(n_x);
+      p->off_gi = ws.take(skip.input ? 0 : n_x);
       p->off_goff = ws.take(n_off);
       p->off_gm = ws.take(n_m);
-      p->off_gw = ws.take(n_w);
-      p->off_gb = ws.take((size_t)g.O * 4);
+      p->off_gw = ws.take(skip.weight ? 0 : n_w);
+      p->off_gb = ws.take(skip.weight ? 0 : (size_t)g.O * 4);
     }
   }
   p->total = ws.off;
@@ -318,8 +323,11 @@ bool bwd_fork_enabled() { return bwd_fork_mode() != 0; }
 // The grad_input gather (CSR scan + fill -> col2im, HBM-bound) shares nothing with GEMM-2 (matrix-bound)
 // and runs beside it on a forked stream that re-joins before this function returns (get_fork).
 // `bd`: the layout the plan sized the workspace with for this chunk size (Plan::bd / bd_tail).
+// `skip`: the tail of a gradient the call leaves out is not enqueued (and with one tail, or none, nothing is forked);
+// GEMM-1 runs as it is -- its side products for the skipped tail (packed grad_out, tap table and grad_bias partials for
+// GEMM-2; grad_col rows and counters for the gather) go to the workspace and are left there.
 int backward_chunk_f32(const Geom &g, const BwdDims &bd, const Tensors &t, char *base, hipStream_t stream,
-                       bool weights_final) {
+                       bool weights_final, Skip skip) {
   float *wq = (float *)(base + bd.off_wq);
   float *ga = (float *)(base + bd.off_ga);
   int *table = (int *)(base + bd.off_table);
@@ -339,7 +347,7 @@ int backward_chunk_f32(const Geom &g, const BwdDims &bd, const Tensors &t, char 
   profile_mark(1, false, stream);
   if (rc) return rc;
   Fork fk;
-  const bool fork = bwd_fork_enabled() && get_fork(stream, &fk);
+  const bool fork = !skip.input && !skip.weight && bwd_fork_enabled() && get_fork(stream, &fk);
   hipStream_t gs = stream;   // stream of the grad_input gather
   // GEMM-2 + split-K reduction; grad_bias behind them unless the forked stream already took it
   auto gemm2 = [&](bool bias_here) {
@@ -358,9 +366,10 @@ int backward_chunk_f32(const Geom &g, const BwdDims &bd, const Tensors &t, char 
       return MDCONV_ELAUNCH;
     }
     gs = fk.side;
-  } else {
+  } else if (!skip.weight) {
     if ((rc = gemm2(true))) return rc;
   }
+  if (skip.input) return MDCONV_OK;
   const bool gemm2_first = fork && bwd_fork_mode() == 2;   // (experiment: GEMM-2 enqueued before the gather)
   rc = MDCONV_OK;
   // forked: grad_bias first on the side stream (beside GEMM-2, off the critical path), its event for the caller's stream
@@ -410,7 +419,7 @@ int join_side_stream(hipStream_t stream) {
   return MDCONV_OK;
 }
 
-bool native_plan(const Geom &g, int dtype, bool backward, Plan *p) {
+bool native_plan(const Geom &g, int dtype, bool backward, Plan *p, Skip skip) {
   if (dtype != MDCONV_F32 && dtype != MDCONV_F16 && dtype != MDCONV_BF16) return false;
   if (g.in_sz[g.nd - 1] < 2) return false;   // paired-corner gathers need 2 columns
   if (!backward) {
@@ -422,7 +431,7 @@ bool native_plan(const Geom &g, int dtype, bool backward, Plan *p) {
     if (g.C < 16 || g.O < 16 || g.C % 8) return false;
     if (!(g.DG == 1 || g.Cdg == 64 || g.Cdg == 128 || g.Cdg % 256 == 0)) return false;
   }
-  if (!make_plan(g, dtype, backward, p)) return false;   // one image must fit 32-bit buffer offsets
+  if (!make_plan(g, dtype, backward, skip, p)) return false;   // one image must fit 32-bit buffer offsets
   // the grad_out tile of GEMM-1 lives in LDS: sized for the whole call's pixel count (a single chunk: its own layout)
   return !backward || bwd_data_lds_bytes(g, p->Bc == g.B ? p->bd : bwd_dims(g)) <= kBwdDataLdsCap;
 }
@@ -482,6 +491,7 @@ int native_forward(const Geom &g, int dtype, const Plan &p, const Tensors &t, vo
 
 int native_backward(const Geom &g, int dtype, const Plan &p, const Tensors &t, void *ws, hipStream_t stream) {
   char *base = (char *)ws;
+  const Skip skip = p.skip;
   const size_t es = p.half_io ? 2 : 4;
   const int nc_off = g.DG * g.nd * g.K, nc_m = g.DG * g.K;
   const int64_t n_w = (int64_t)g.O * g.Cg * g.K;
@@ -510,11 +520,13 @@ int native_backward(const Geom &g, int dtype, const Plan &p, const Tensors &t, v
       if ((rc = widen(dtype, (const char *)t.grad_output + o_go * es, (float *)(base + p.off_go), n_go, stream))) return rc;
       tc.input = base + p.off_x; tc.offset = base + p.off_off; tc.mask = t.mask ? base + p.off_m : nullptr;
       tc.weight = base + p.off_w; tc.grad_output = base + p.off_go;
-      tc.grad_input = base + p.off_gi; tc.grad_offset = base + p.off_goff;
+      tc.grad_input = skip.input ? nullptr : base + p.off_gi; tc.grad_offset = base + p.off_goff;
       tc.grad_mask = t.grad_mask ? base + p.off_gm : nullptr;
-      tc.grad_weight = base + p.off_gw; tc.grad_bias = base + p.off_gb;
-      if ((rc = backward_chunk_f32(gc, bd, tc, base, stream, false))) return rc;
-      if ((rc = narrow(dtype, (const float *)tc.grad_input, (char *)t.grad_input + o_x * es, n_x, g.acc_data != 0, stream))) return rc;
+      tc.grad_weight = skip.weight ? nullptr : base + p.off_gw; tc.grad_bias = skip.weight ? nullptr : base + p.off_gb;
+      if ((rc = backward_chunk_f32(gc, bd, tc, base, stream, false, skip))) return rc;
+      if (!skip.input &&
+          (rc = narrow(dtype, (const float *)tc.grad_input, (char *)t.grad_input + o_x * es, n_x, g.acc_data != 0, stream)))
+        return rc;
       if ((rc = narrow(dtype, (const float *)tc.grad_offset, (char *)t.grad_offset + o_off * es, n_off, g.acc_data != 0, stream))) return rc;
       if (t.grad_mask &&
           (rc = narrow(dtype, (const float *)tc.grad_mask, (char *)t.grad_mask + o_m * es, n_m, g.acc_data != 0, stream)))
@@ -524,13 +536,13 @@ int native_backward(const Geom &g, int dtype, const Plan &p, const Tensors &t, v
       tc.offset = (const char *)t.offset + o_off * es;
       tc.mask = t.mask ? (const char *)t.mask + o_m * es : nullptr;
       tc.grad_output = (const char *)t.grad_output + o_go * es;
-      tc.grad_input = (char *)t.grad_input + o_x * es;
+      tc.grad_input = skip.input ? nullptr : (char *)t.grad_input + o_x * es;
       tc.grad_offset = (char *)t.grad_offset + o_off * es;
       tc.grad_mask = t.grad_mask ? (char *)t.grad_mask + o_m * es : nullptr;
-      if ((rc = backward_chunk_f32(gc, bd, tc, base, stream, b0 + bc >= g.B))) return rc;
+      if ((rc = backward_chunk_f32(gc, bd, tc, base, stream, b0 + bc >= g.B, skip))) return rc;
     }
   }
-  if (p.half_io) {
+  if (p.half_io && !skip.weight) {
     // (fp32 grad_weight / grad_bias, t.wgrad32: the sums as they are, copied or added)
     if ((rc = narrow_wgrad(dtype, t, (const float *)(base + p.off_gw), t.grad_weight, n_w, g.acc_w != 0, stream))) return rc;
     if (g.with_bias && (rc = narrow_wgrad(dtype, t, (const float *)(base + p.off_gb), t.grad_bias, g.O, g.acc_w != 0, stream)))

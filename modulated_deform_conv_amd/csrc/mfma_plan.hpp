@@ -18,9 +18,11 @@ struct Plan {
   size_t core_bytes;  // workspace of the fp32 kernels for one chunk: the larger need of the two chunk sizes
   size_t off_w, off_b, off_x, off_off, off_m, off_go, off_out, off_gi, off_goff, off_gm, off_gw, off_gb;
   size_t total;
+  Skip skip;          // backward: gradients the call leaves out -- their stages are not run, their slots take no bytes
 };
-// false: the kernels do not tile `g` (or one image exceeds 32-bit buffer offsets)
-bool native_plan(const Geom &g, int dtype, bool backward, Plan *p);
+// false: the kernels do not tile `g` (or one image exceeds 32-bit buffer offsets).  `skip` never changes the answer,
+// the chunks or the tiling.
+bool native_plan(const Geom &g, int dtype, bool backward, Plan *p, Skip skip = Skip());
 // `g` is the geometry `p` was made for; with_bias alone may differ from it where the caller sized for the larger need
 // (split plans: the slices of a conv group after the first run without bias)
 int native_forward(const Geom &g, int dtype, const Plan &p, const Tensors &t, void *ws, hipStream_t stream);
@@ -58,6 +60,7 @@ struct MfmaPlan {
   enum Kind { NATIVE, PADDED, SPLIT_FWD, SPLIT_BWD } kind;
   bool backward;
   size_t total;       // workspace bytes
+  Skip skip;          // backward: gradients the call leaves out
   Plan native;
   PadPlan pad;
   SplitFwdPlan split_fwd;
@@ -66,7 +69,9 @@ struct MfmaPlan {
 // Priority: padded where the padded problem is the faster one (pad_channels_preferred), native, padded, split.
 // false: the family does not run this shape / dtype.  `wgrad32` (a 16-bit backward with fp32 grad_weight / grad_bias,
 // MDCONV_WGRAD_F32) sizes the padded / sliced plans' grad_weight rows for 4-byte elements; it never changes the kind.
-bool mfma_plan(const Geom &g, int dtype, bool backward, MfmaPlan *p, bool wgrad32 = false);
+// `skip` (a backward without grad_input / without the weight gradients) never changes the kind either: the plans drop the
+// skipped gradients' stages, copies and workspace slots (MfmaPlan::skip).
+bool mfma_plan(const Geom &g, int dtype, bool backward, MfmaPlan *p, bool wgrad32 = false, Skip skip = Skip());
 int mfma_forward(const Geom &g, int dtype, const MfmaPlan &p, const Tensors &t, void *ws, hipStream_t stream);
 int mfma_backward(const Geom &g, int dtype, const MfmaPlan &p, const Tensors &t, void *ws, hipStream_t stream);
 
@@ -74,7 +79,8 @@ int mfma_backward(const Geom &g, int dtype, const MfmaPlan &p, const Tensors &t,
 // ... on the shape-generic backward kernels: one rounding per gradient instead of one per atomic add
 struct D16Plan { size_t off_x, off_off, off_m, off_w, off_go, off_gi, off_goff, off_gm, off_gw, off_gb, total; };
 D16Plan direct16_plan(const Geom &g);
-int direct16_backward(const Geom &g, int dtype, const D16Plan &p, const Tensors &t, void *ws, hipStream_t stream);
+// (`skip`: the weight kernel is not run / the narrowing copies of the skipped gradients are left out; the layout stays)
+int direct16_backward(const Geom &g, int dtype, const D16Plan &p, const Tensors &t, void *ws, hipStream_t stream, Skip skip = Skip());
 
 // ... with fp32 offsets / masks (MDCONV_SAMPLING_F32) on the fp32 kernels: fp32 copies of the 16-bit tensors, the caller's
 // fp32 offsets / masks / grad_offset / grad_mask as they are; on the matrix kernels (`mfma`: their fp32 plan is `inner`,
@@ -83,9 +89,10 @@ struct S32Plan {
   size_t off_x, off_w, off_b, off_o, off_gi, off_gw, off_inner, total;   // off_o: output / grad_output
   bool mfma;
   MfmaPlan inner;
+  Skip skip;   // backward: gradients the call leaves out (no fp32 buffer, no copies for them on the matrix kernels)
 };
 // want_mfma: take the matrix kernels where they have an fp32 plan for `g` (p->mfma tells)
-void samp32_plan(const Geom &g, bool backward, bool want_mfma, S32Plan *p);
+void samp32_plan(const Geom &g, bool backward, bool want_mfma, S32Plan *p, Skip skip = Skip());
 int samp32_forward(const Geom &g, int dtype, const S32Plan &p, const Tensors &t, void *ws, hipStream_t stream);
 int samp32_backward(const Geom &g, int dtype, const S32Plan &p, const Tensors &t, void *ws, hipStream_t stream);
 

@@ -35,16 +35,16 @@ bool split_slice_geom(const Geom &g, Geom *out, bool *copy_w, bool *copy_go) {
   *out = s;
   return true;
 }
-bool split_plan(const Geom &g, int dtype, bool wgrad32, SplitPlan *p) {
+bool split_plan(const Geom &g, int dtype, bool wgrad32, Skip skip, SplitPlan *p) {
   if (!split_slice_geom(g, &p->gs, &p->copy_w, &p->copy_go)) return false;
   // The slices' workspace is sized from the geometry the FIRST slice of a conv group runs with (split_backward): that
   // slice carries grad_bias and has the grad_bias stage buffer at the end of its layout -- sized without it, it wrote
   // 32 * C_out * 4 bytes past the workspace (found by tools/fuzz_more.py in round 5; tests/test_gpu_workspace_guard.py)
   Geom first = p->gs;
   first.with_bias = g.with_bias;
-  if (!native_plan(first, dtype, true, &p->first)) return false;
+  if (!native_plan(first, dtype, true, &p->first, skip)) return false;
   p->rest = p->first;
-  if (first.with_bias && !native_plan(p->gs, dtype, true, &p->rest)) return false;
+  if (first.with_bias && !native_plan(p->gs, dtype, true, &p->rest, skip)) return false;
   const size_t es = dtype == MDCONV_F32 ? 4 : 2;
   const size_t es_w = wgrad32 ? 4 : es;   // grad_weight rows (fp32 with MDCONV_WGRAD_F32)
   const Geom &s = p->gs;
@@ -54,10 +54,10 @@ bool split_plan(const Geom &g, int dtype, bool wgrad32, SplitPlan *p) {
   p->off_m = ws.take(g.modulated ? (size_t)g.B * g.K * g.S_o * es : 0);
   p->off_go = ws.take(p->copy_go ? (size_t)g.B * s.O * g.S_o * es : 0);
   p->off_w = ws.take(p->copy_w ? (size_t)s.O * s.Cg * g.K * es : 0);
-  p->off_gi = ws.take((size_t)g.B * s.C * g.S_i * es);
+  p->off_gi = ws.take(skip.input ? 0 : (size_t)g.B * s.C * g.S_i * es);   // (a selective backward: no slice of a skipped gradient)
   p->off_goff = ws.take((size_t)g.B * g.nd * g.K * g.S_o * es);
   p->off_gm = ws.take(g.modulated ? (size_t)g.B * g.K * g.S_o * es : 0);
-  p->off_gw = ws.take(p->copy_w ? (size_t)s.O * s.Cg * g.K * es_w : 0);
+  p->off_gw = ws.take(p->copy_w && !skip.weight ? (size_t)s.O * s.Cg * g.K * es_w : 0);
   p->off_sub = ws.off;
   p->total = ws.off + p->first.total;
   return true;
@@ -74,6 +74,7 @@ int split_backward(const Geom &g, int dtype, const SplitPlan &p, const Tensors &
   const size_t w_go = (size_t)s.O * g.S_o * es, p_go = (size_t)g.O * g.S_o * es;
   const size_t w_w = (size_t)s.Cg * g.K * es, p_w = (size_t)g.Cg * g.K * es;
   const size_t w_gw = (size_t)s.Cg * g.K * es_w, p_gw = (size_t)g.Cg * g.K * es_w;
+  const Skip skip = p.first.skip;   // skipped gradients: no slice buffer, no copies in or out, NULL for the slices
   int rc;
   for (int dg = 0; dg < g.DG; ++dg) {
     const int c0 = dg * g.Cdg;            // first input channel of the slice
@@ -83,13 +84,13 @@ int split_backward(const Geom &g, int dtype, const SplitPlan &p, const Tensors &
     Tensors ts = t;
     const char *src_x = (const char *)t.input + (size_t)c0 * g.S_i * es;
     const char *src_off = (const char *)t.offset + (size_t)dg * w_off;
-    char *dst_gi = (char *)t.grad_input + (size_t)c0 * g.S_i * es;
+    char *dst_gi = skip.input ? nullptr : (char *)t.grad_input + (size_t)c0 * g.S_i * es;
     char *dst_goff = (char *)t.grad_offset + (size_t)dg * w_off;
-    char *dst_gw = (char *)t.grad_weight + ((size_t)o0 * g.Cg + cw) * g.K * es_w;
+    char *dst_gw = skip.weight ? nullptr : (char *)t.grad_weight + ((size_t)o0 * g.Cg + cw) * g.K * es_w;
     if ((rc = copy_rows(base + p.off_x, w_x, src_x, p_x, w_x, g.B, stream))) return rc;
     if ((rc = copy_rows(base + p.off_off, w_off, src_off, p_off, w_off, g.B, stream))) return rc;
     ts.input = base + p.off_x; ts.offset = base + p.off_off;
-    ts.grad_input = base + p.off_gi; ts.grad_offset = base + p.off_goff;
+    ts.grad_input = skip.input ? nullptr : base + p.off_gi; ts.grad_offset = base + p.off_goff;
     if (g.modulated) {
       if ((rc = copy_rows(base + p.off_m, w_m, (const char *)t.mask + (size_t)dg * w_m, p_m, w_m, g.B, stream))) return rc;
       ts.mask = base + p.off_m; ts.grad_mask = base + p.off_gm;
@@ -103,30 +104,30 @@ int split_backward(const Geom &g, int dtype, const SplitPlan &p, const Tensors &
     ts.grad_weight = dst_gw;
     if (p.copy_w) {
       if ((rc = copy_rows(base + p.off_w, w_w, ts.weight, p_w, w_w, s.O, stream))) return rc;
-      ts.weight = base + p.off_w; ts.grad_weight = base + p.off_gw;
+      ts.weight = base + p.off_w; ts.grad_weight = skip.weight ? nullptr : base + p.off_gw;
     }
     Geom gs = s;
     // grad_bias belongs to the output channels: once per conv group, with the first slice that touches it
     gs.with_bias = g.with_bias && cw == 0 ? 1 : 0;
     ts.bias = nullptr;
-    ts.grad_bias = gs.with_bias ? (char *)t.grad_bias + (size_t)o0 * es_w : nullptr;
+    ts.grad_bias = gs.with_bias && !skip.weight ? (char *)t.grad_bias + (size_t)o0 * es_w : nullptr;
     if (g.acc_data) {   // accumulate mode: the slice starts from the caller's values
-      if ((rc = copy_rows(base + p.off_gi, w_x, dst_gi, p_x, w_x, g.B, stream))) return rc;
+      if (!skip.input && (rc = copy_rows(base + p.off_gi, w_x, dst_gi, p_x, w_x, g.B, stream))) return rc;
       if ((rc = copy_rows(base + p.off_goff, w_off, dst_goff, p_off, w_off, g.B, stream))) return rc;
       if (g.modulated &&
           (rc = copy_rows(base + p.off_gm, w_m, (const char *)t.grad_mask + (size_t)dg * w_m, p_m, w_m, g.B, stream)))
         return rc;
     }
-    if (g.acc_w && p.copy_w && (rc = copy_rows(base + p.off_gw, w_gw, dst_gw, p_gw, w_gw, s.O, stream))) return rc;
+    if (g.acc_w && p.copy_w && !skip.weight && (rc = copy_rows(base + p.off_gw, w_gw, dst_gw, p_gw, w_gw, s.O, stream))) return rc;
     if ((rc = native_backward(gs, dtype, gs.with_bias ? p.first : p.rest, ts, base + p.off_sub, stream))) return rc;
-    if ((rc = copy_rows(dst_gi, p_x, base + p.off_gi, w_x, w_x, g.B, stream))) return rc;
+    if (!skip.input && (rc = copy_rows(dst_gi, p_x, base + p.off_gi, w_x, w_x, g.B, stream))) return rc;
     if ((rc = copy_rows(dst_goff, p_off, base + p.off_goff, w_off, w_off, g.B, stream))) return rc;
     if (g.modulated &&
         (rc = copy_rows((char *)t.grad_mask + (size_t)dg * w_m, p_m, base + p.off_gm, w_m, w_m, g.B, stream)))
       return rc;
-    if (p.copy_w && (rc = copy_rows(dst_gw, p_gw, base + p.off_gw, w_gw, w_gw, s.O, stream))) return rc;
+    if (p.copy_w && !skip.weight && (rc = copy_rows(dst_gw, p_gw, base + p.off_gw, w_gw, w_gw, s.O, stream))) return rc;
   }
-  return record_weight_ready(stream);   // after the last slice's copies
+  return skip.weight ? MDCONV_OK : record_weight_ready(stream);   // after the last slice's copies
 }
 }  // namespace
 
@@ -276,7 +277,7 @@ int pad_group_channels(const Geom &g, bool backward, bool native_ok) {
   return backward ? cdp_b : cdp_f;
 }
 // native_ok: the kernels tile `g` itself
-bool pad_plan(const Geom &g, int dtype, bool backward, bool native_ok, bool wgrad32, PadPlan *p) {
+bool pad_plan(const Geom &g, int dtype, bool backward, bool native_ok, bool wgrad32, Skip skip, PadPlan *p) {
   if (dg_plan_env() == 2) return false;
   Geom gp = g;
   if (g.G == 1) {
@@ -331,18 +332,19 @@ bool pad_plan(const Geom &g, int dtype, bool backward, bool native_ok, bool wgra
   p->pad_c = p->cinp != p->cin;
   p->pad_o = p->ogp != p->og;
   if (!p->pad_c && !p->pad_o) return false;
-  if (!native_plan(gp, dtype, backward, &p->sub)) return false;
+  if (!native_plan(gp, dtype, backward, &p->sub, skip)) return false;
   p->gp = gp;
   const size_t es = dtype == MDCONV_F32 ? 4 : 2;
   const size_t es_w = wgrad32 ? 4 : es;   // grad_weight / grad_bias (fp32 with MDCONV_WGRAD_F32)
   Bump ws;
   p->off_x = ws.take(p->pad_c ? (size_t)g.B * gp.C * g.S_i * es : 0);
   p->off_w = ws.take((size_t)gp.O * gp.Cg * g.K * es);
-  p->off_gi = ws.take(backward && p->pad_c ? (size_t)g.B * gp.C * g.S_i * es : 0);
-  p->off_gw = ws.take(backward ? (size_t)gp.O * gp.Cg * g.K * es_w : 0);
+  // (a selective backward: no padded buffer of a skipped gradient)
+  p->off_gi = ws.take(backward && p->pad_c && !skip.input ? (size_t)g.B * gp.C * g.S_i * es : 0);
+  p->off_gw = ws.take(backward && !skip.weight ? (size_t)gp.O * gp.Cg * g.K * es_w : 0);
   p->off_o = ws.take(p->pad_o ? (size_t)g.B * gp.O * g.S_o * es : 0);
   p->off_b = ws.take(p->pad_o && g.with_bias && !backward ? (size_t)gp.O * es : 0);
-  p->off_gb = ws.take(p->pad_o && g.with_bias && backward ? (size_t)gp.O * es_w : 0);
+  p->off_gb = ws.take(p->pad_o && g.with_bias && backward && !skip.weight ? (size_t)gp.O * es_w : 0);
   p->off_sub = ws.off;
   p->total = ws.off + p->sub.total;
   return true;
@@ -389,26 +391,30 @@ int pad_backward(const Geom &g, int dtype, const PadPlan &p, const Tensors &t, v
   const size_t es_w = wgrad_bytes(dtype, t);   // grad_weight / grad_bias elements
   const size_t w_gw = (size_t)p.cin * g.K * es_w, p_gw = (size_t)p.cinp * g.K * es_w;
   const size_t wi = (size_t)p.og * p.wsub, wip = (size_t)p.ogp * p.wsub;   // weight rows of one output group (caller's / padded)
+  const Skip skip = p.sub.skip;   // skipped gradients: no padded buffer, no copies in or out (the caller's pointers are NULL)
   int rc;
   Tensors tp = t;   // grad_offset / grad_mask have no channel axis: written in place, in the caller's mode
   if ((rc = pad_inputs(g, dtype, p, t, base, &tp, stream))) return rc;
   // accumulate modes: the padded gradient buffers start from the caller's values (like the slices above)
-  if (p.pad_c) {
+  if (p.pad_c && !skip.input) {
     if (g.acc_data && (rc = pad_rows(base + p.off_gi, p_x, t.grad_input, w_x, (size_t)g.B * p.ng, stream))) return rc;
     tp.grad_input = base + p.off_gi;
   }
-  if (g.acc_w && (rc = pad_rows_grouped(base + p.off_gw, p_gw, t.grad_weight, w_gw, wi, wip, p.nog, stream))) return rc;
-  tp.grad_weight = base + p.off_gw;
+  if (!skip.weight) {
+    if (g.acc_w && (rc = pad_rows_grouped(base + p.off_gw, p_gw, t.grad_weight, w_gw, wi, wip, p.nog, stream))) return rc;
+    tp.grad_weight = base + p.off_gw;
+  }
   if (p.pad_o) {
     if ((rc = pad_rows(base + p.off_o, p_o, t.grad_output, w_o, (size_t)g.B * p.nog, stream))) return rc;   // zero planes for the padding channels
     tp.grad_output = base + p.off_o;
-    if (g.with_bias) {
+    if (g.with_bias && !skip.weight) {
       if (g.acc_w && (rc = pad_rows(base + p.off_gb, (size_t)p.ogp * es_w, t.grad_bias, (size_t)p.og * es_w, p.nog, stream))) return rc;
       tp.grad_bias = base + p.off_gb;
     }
   }
   if ((rc = native_backward(p.gp, dtype, p.sub, tp, base + p.off_sub, stream))) return rc;
-  if (p.pad_c && (rc = copy_rows(t.grad_input, w_x, base + p.off_gi, p_x, w_x, (size_t)g.B * p.ng, stream))) return rc;
+  if (p.pad_c && !skip.input && (rc = copy_rows(t.grad_input, w_x, base + p.off_gi, p_x, w_x, (size_t)g.B * p.ng, stream))) return rc;
+  if (skip.weight) return MDCONV_OK;
   if ((rc = unpad_rows_grouped(t.grad_weight, w_gw, base + p.off_gw, p_gw, wi, wip, p.nog, stream))) return rc;
   if (p.pad_o && g.with_bias &&
       (rc = copy_rows(t.grad_bias, (size_t)p.og * es_w, base + p.off_gb, (size_t)p.ogp * es_w, (size_t)p.og * es_w, p.nog, stream)))
@@ -417,18 +423,20 @@ int pad_backward(const Geom &g, int dtype, const PadPlan &p, const Tensors &t, v
 }
 }  // namespace
 
-bool mfma_plan(const Geom &g, int dtype, bool backward, MfmaPlan *p, bool wgrad32) {
+bool mfma_plan(const Geom &g, int dtype, bool backward, MfmaPlan *p, bool wgrad32, Skip skip) {
   p->backward = backward;
-  const bool native_ok = native_plan(g, dtype, backward, &p->native);
+  if (!backward) skip = Skip();
+  p->skip = skip;
+  const bool native_ok = native_plan(g, dtype, backward, &p->native, skip);
   // the padded problem where it is the faster one (pad_channels_preferred), else native tiling, else padded, else slices
-  if ((pad_channels_preferred(g) || !native_ok) && pad_plan(g, dtype, backward, native_ok, wgrad32, &p->pad)) {
+  if ((pad_channels_preferred(g) || !native_ok) && pad_plan(g, dtype, backward, native_ok, wgrad32, skip, &p->pad)) {
     p->kind = MfmaPlan::PADDED;
     p->total = p->pad.total;
   } else if (native_ok) {
     p->kind = MfmaPlan::NATIVE;
     p->total = p->native.total;
   } else if (backward) {
-    if (!split_plan(g, dtype, wgrad32, &p->split_bwd)) return false;
+    if (!split_plan(g, dtype, wgrad32, skip, &p->split_bwd)) return false;
     p->kind = MfmaPlan::SPLIT_BWD;
     p->total = p->split_bwd.total;
   } else {

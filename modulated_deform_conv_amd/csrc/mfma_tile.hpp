@@ -91,7 +91,7 @@ struct BwdDims {
   // off_sort: scratch of the list sort in deterministic mode (Geom::det; 0 bytes otherwise)
   int two_pass;         // 3-D grad_input gather: 1 = per-anchor partial sums + stencil (mfma_csr3d.hip), 0 = block walk
 };
-BwdDims bwd_dims(const Geom &g);
+BwdDims bwd_dims(const Geom &g, Skip skip = Skip());   // skip: slots of the stages a selective backward leaves out take no bytes
 
 #ifdef __HIPCC__
 // xt[b][q0 + r][c0 + tx] = x[b][c0 + r][q0 + tx] for one 32 x 32 tile through LDS (256 threads; C is a multiple of 32)

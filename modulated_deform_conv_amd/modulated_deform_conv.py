@@ -113,20 +113,28 @@ def _make_function(nd, modulated, name):
             mask = None
         geo = _geometry(ctx, weight)
         wdt = torch.float32 if ctx.wgrad32 else None
+        # selective backward (_capi.skip_grads): what autograd does not ask for is neither computed nor allocated, and None
+        # is returned there -- grad_input when `input` needs no gradient, the weight gradients when neither `weight` nor
+        # (with a bias) `bias` does.  (forward's arguments: input, offset, [mask,] weight, bias, ...)
+        need = ctx.needs_input_grad
+        iw = 3 if modulated else 2
+        skip_input = not need[0]
+        skip_weight = not (need[iw] or (ctx.with_bias and need[iw + 1]))
+        skip = _capi.skip_grads(input=skip_input, weight=skip_weight)
         if returns_tensors:
-            # (autograd runs this on its own thread: the mode recorded in forward is entered here)
-            with _capi.weight_grads_f32(ctx.wgrad32):
+            # (autograd runs this on its own thread: the modes recorded in forward are entered here)
+            with _capi.weight_grads_f32(ctx.wgrad32), skip:
                 grad_input, grad_offset, grad_mask, grad_weight, grad_bias = bwd(
                     input, weight, bias, offset, mask, grad_output, *geo)
         else:
             # the reference wrapper zero-fills and the entry points add (:53-56); here the buffers
             # are fresh, so the library is asked to write them instead (mdconv_set_accumulate)
-            grad_input = torch.empty_like(input, memory_format=torch.contiguous_format)
+            grad_input = None if skip_input else torch.empty_like(input, memory_format=torch.contiguous_format)
             grad_offset = torch.empty_like(offset)
             # one flat buffer: one in-place all-reduce (distributed.py); fp32 for fp32 weight gradients -- the entry points
             # take the mode from the buffers' dtype
-            grad_weight, grad_bias = fused_grad_buffers(weight, bias, wdt)
-            with _capi.overwrite_grads(), _capi.weight_grads_f32(ctx.wgrad32):
+            grad_weight, grad_bias = (None, None) if skip_weight else fused_grad_buffers(weight, bias, wdt)
+            with _capi.overwrite_grads(), _capi.weight_grads_f32(ctx.wgrad32), skip:
                 if modulated:
                     grad_mask = torch.empty_like(mask)
                     bwd(input, weight, bias, offset, mask, grad_input, grad_weight, grad_bias,

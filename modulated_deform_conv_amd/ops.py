@@ -7,6 +7,9 @@ Two dispatcher-visible operators, written once for 2-D / 3-D and plain / modulat
     mdconv::deform_conv_backward(grad_output, input, offset, mask?, weight, bias?, ...)
         -> (grad_input, grad_offset, grad_mask, grad_weight, grad_bias)
 
+    mdconv::deform_conv_backward_masked(grad_output, input, offset, mask?, weight, bias?, ..., need_input, need_weight)
+        -> the same five; 0-element tensors where a gradient is not needed (the backward leaves it out)
+
 with fake (meta) kernels, so FakeTensor / ``torch.compile`` / ``torch.export`` can trace through
 them without running a kernel, and an autograd formula that links the two.  The CUDA(=HIP)
 implementations call the same eight ``MDCONV_CUDA`` entry points as the legacy
@@ -26,7 +29,7 @@ import torch
 
 from . import MDCONV_CUDA, _capi
 
-__all__ = ["deform_conv", "deform_conv_backward", "output_size"]
+__all__ = ["deform_conv", "deform_conv_backward", "deform_conv_backward_masked", "output_size"]
 
 
 def output_size(in_size, kernel, stride, padding, dilation):
@@ -137,6 +140,49 @@ def _(input, offset, mask, weight, bias, stride, padding, dilation, groups, defo
     return input.new_empty([input.shape[0], weight.shape[0]] + osz)
 
 
+def _backward_impl(grad_output, input, offset, mask, weight, bias, stride, padding, dilation, groups, deformable_groups,
+                   in_step, need_input=True, need_weight=True):
+    """The five gradients as the operators return them: 0-element tensors for grad_mask / grad_bias of an op without
+    mask / bias (the reference's "fake tensor" convention, modulated_deform_conv.py:19-21) and for the gradients a masked
+    call leaves out (`need_input` / `need_weight` False: _capi.skip_grads)."""
+    nd, _ = _validate(input, offset, mask, weight, bias, stride, padding, dilation, groups,
+                      deformable_groups, in_step, grad_output)
+    grad_output = grad_output.contiguous()
+    input, offset, weight = _input_layout(input), offset.contiguous(), weight.contiguous()
+    mask = None if mask is None else mask.contiguous()
+    b = input.new_empty(0) if bias is None else bias.contiguous()
+    geo = _geometry(weight, stride, padding, dilation, groups, deformable_groups, in_step,
+                    bias is not None)
+    fn = _entry(nd, mask is not None, True)
+    fake = lambda g: input.new_empty(0) if g is None else g
+    with _capi.skip_grads(input=not need_input, weight=not need_weight):
+        if mask is not None and nd == 2:
+            # (the export itself returns grad_weight / grad_bias as two views of one buffer; an operator's returns may not alias)
+            return tuple(fake(g) for g in MDCONV_CUDA._modulated2d_backward(False, input, weight, b, offset, mask, grad_output, *geo))
+        gi = torch.empty_like(input, memory_format=torch.contiguous_format) if need_input else None
+        goff = torch.empty_like(offset)
+        gw, gb = (torch.empty_like(weight), torch.empty_like(b)) if need_weight else (None, None)
+        with _capi.overwrite_grads():   # fresh buffers: written, not added to
+            if mask is not None:
+                gm = torch.empty_like(mask)
+                fn(input, weight, b, offset, mask, gi, gw, gb, goff, gm, grad_output, *geo)
+            else:
+                gm = input.new_empty(0)
+                fn(input, weight, b, offset, gi, gw, gb, goff, grad_output, *geo)
+    return fake(gi), goff, gm, fake(gw), fake(gb)
+
+
+def _backward_fake(grad_output, input, offset, mask, weight, bias, stride, padding, dilation, groups, deformable_groups,
+                   in_step, need_input=True, need_weight=True):
+    _validate(input, offset, mask, weight, bias, stride, padding, dilation, groups,
+              deformable_groups, in_step, grad_output)
+    gi = torch.empty_like(input, memory_format=torch.contiguous_format) if need_input else input.new_empty(0)
+    gm = input.new_empty(0) if mask is None else torch.empty_like(mask)
+    gw = torch.empty_like(weight) if need_weight else input.new_empty(0)
+    gb = input.new_empty(0) if bias is None or not need_weight else torch.empty_like(bias)
+    return gi, torch.empty_like(offset), gm, gw, gb
+
+
 @torch.library.custom_op("mdconv::deform_conv_backward", mutates_args=(), device_types="cuda")
 def deform_conv_backward(grad_output: torch.Tensor, input: torch.Tensor, offset: torch.Tensor,
                          mask: Optional[torch.Tensor], weight: torch.Tensor,
@@ -147,39 +193,37 @@ def deform_conv_backward(grad_output: torch.Tensor, input: torch.Tensor, offset:
     """-> (grad_input, grad_offset, grad_mask, grad_weight, grad_bias); grad_mask / grad_bias are
     0-element tensors when the op has no mask / bias (the reference's "fake tensor" convention,
     modulated_deform_conv.py:19-21)."""
-    nd, _ = _validate(input, offset, mask, weight, bias, stride, padding, dilation, groups,
-                      deformable_groups, in_step, grad_output)
-    grad_output = grad_output.contiguous()
-    input, offset, weight = _input_layout(input), offset.contiguous(), weight.contiguous()
-    mask = None if mask is None else mask.contiguous()
-    b = input.new_empty(0) if bias is None else bias.contiguous()
-    geo = _geometry(weight, stride, padding, dilation, groups, deformable_groups, in_step,
-                    bias is not None)
-    fn = _entry(nd, mask is not None, True)
-    if mask is not None and nd == 2:
-        # (the export itself returns grad_weight / grad_bias as two views of one buffer; an operator's returns may not alias)
-        return MDCONV_CUDA._modulated2d_backward(False, input, weight, b, offset, mask, grad_output, *geo)
-    gi, goff = torch.empty_like(input, memory_format=torch.contiguous_format), torch.empty_like(offset)
-    gw, gb = torch.empty_like(weight), torch.empty_like(b)
-    with _capi.overwrite_grads():   # fresh buffers: written, not added to
-        if mask is not None:
-            gm = torch.empty_like(mask)
-            fn(input, weight, b, offset, mask, gi, gw, gb, goff, gm, grad_output, *geo)
-        else:
-            gm = input.new_empty(0)
-            fn(input, weight, b, offset, gi, gw, gb, goff, grad_output, *geo)
-    return gi, goff, gm, gw, gb
+    return _backward_impl(grad_output, input, offset, mask, weight, bias, stride, padding, dilation, groups,
+                          deformable_groups, in_step)
 
 
 @deform_conv_backward.register_fake
 def _(grad_output, input, offset, mask, weight, bias, stride, padding, dilation, groups,
       deformable_groups, in_step):
-    _validate(input, offset, mask, weight, bias, stride, padding, dilation, groups,
-              deformable_groups, in_step, grad_output)
-    gm = input.new_empty(0) if mask is None else torch.empty_like(mask)
-    gb = input.new_empty(0) if bias is None else torch.empty_like(bias)
-    return (torch.empty_like(input, memory_format=torch.contiguous_format), torch.empty_like(offset), gm,
-            torch.empty_like(weight), gb)
+    return _backward_fake(grad_output, input, offset, mask, weight, bias, stride, padding, dilation, groups,
+                          deformable_groups, in_step)
+
+
+@torch.library.custom_op("mdconv::deform_conv_backward_masked", mutates_args=(), device_types="cuda")
+def deform_conv_backward_masked(grad_output: torch.Tensor, input: torch.Tensor, offset: torch.Tensor,
+                                mask: Optional[torch.Tensor], weight: torch.Tensor,
+                                bias: Optional[torch.Tensor], stride: List[int], padding: List[int],
+                                dilation: List[int], groups: int, deformable_groups: int,
+                                in_step: int, need_input: bool, need_weight: bool) -> Tuple[
+                                    torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """``deform_conv_backward`` with an output mask (what ``output_mask`` is to ``aten::convolution_backward``):
+    ``need_input`` False leaves grad_input out, ``need_weight`` False grad_weight and grad_bias -- the stages that produce
+    them are not run (include/mdconv.h: MDCONV_FLAG_NO_GRAD_INPUT / MDCONV_FLAG_NO_GRAD_WEIGHT) and 0-element tensors are
+    returned in their places.  The other gradients are what ``deform_conv_backward`` returns."""
+    return _backward_impl(grad_output, input, offset, mask, weight, bias, stride, padding, dilation, groups,
+                          deformable_groups, in_step, need_input, need_weight)
+
+
+@deform_conv_backward_masked.register_fake
+def _(grad_output, input, offset, mask, weight, bias, stride, padding, dilation, groups,
+      deformable_groups, in_step, need_input, need_weight):
+    return _backward_fake(grad_output, input, offset, mask, weight, bias, stride, padding, dilation, groups,
+                          deformable_groups, in_step, need_input, need_weight)
 
 
 def _setup_context(ctx, inputs, output):
@@ -191,10 +235,13 @@ def _setup_context(ctx, inputs, output):
 
 def _autograd(ctx, grad_output):
     input, offset, mask, weight, bias = ctx.saved_tensors
-    gi, goff, gm, gw, gb = deform_conv_backward(grad_output, input, offset, mask, weight, bias,
-                                                *ctx.conf)
-    return (gi, goff, gm if mask is not None else None, gw, gb if bias is not None else None,
-            None, None, None, None, None, None)
+    # only what autograd asks for (inputs: input, offset, mask, weight, bias, ...)
+    need = ctx.needs_input_grad
+    need_input, need_weight = bool(need[0]), bool(need[3] or (bias is not None and need[4]))
+    gi, goff, gm, gw, gb = deform_conv_backward_masked(grad_output, input, offset, mask, weight, bias,
+                                                       *ctx.conf, need_input, need_weight)
+    return (gi if need_input else None, goff, gm if mask is not None else None, gw if need_weight else None,
+            gb if bias is not None and need_weight else None, None, None, None, None, None, None)
 
 
 deform_conv.register_autograd(_autograd, setup_context=_setup_context)
