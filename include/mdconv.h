@@ -148,6 +148,21 @@ typedef struct mdconv_desc {
  * MDCONV_EINVAL, like every other value that was invalid before these flags existed; they still are.) */
 #define MDCONV_FLAG_NO_GRAD_INPUT 4
 #define MDCONV_FLAG_NO_GRAD_WEIGHT 8
+/* MDCONV_FLAG_MATH_BF16 -- fp32 tensors, bf16 matrix math (what torch.set_float32_matmul_precision("medium") is to the
+ * reference's addmm_ calls).  A PERMISSION for MDCONV_F32 calls, like allow_tf32: a forward / backward whose bf16 form the
+ * native 16-bit kernels take (the forward: and prefer; at least 16 input and 16 output channels) runs on those kernels; any other flagged call runs exactly as
+ * without the flag -- same route, same bits, same workspace -- and none is refused over it.  mdconv_math_bf16_used() tells
+ * beforehand; the two directions of one layer can differ.  Where the mode is taken:
+ *  - input, weight and grad_output are rounded to bf16 (to nearest even) as matrix operands, inside the layout passes;
+ *  - offset, mask, grad_offset and grad_mask stay fp32 end to end (as with MDCONV_SAMPLING_F32);
+ *  - grad_weight and grad_bias are the unrounded fp32 sums (as with MDCONV_WGRAD_F32); bias is added in fp32;
+ *  - output and grad_input are fp32, stored from fp32 accumulators; accumulate mode adds to the caller's buffers in fp32;
+ *  - MDCONV_FLAG_DETERMINISTIC, _NO_GRAD_INPUT and _NO_GRAD_WEIGHT act as on a bf16 call;
+ *  - mdconv_workspace_bytes, mdconv_deterministic_supported and mdconv_last_kernels() (MDCONV_KERNELS_HP) answer for the
+ *    route the flagged call takes.  An fp32 channels-last input stays refused.
+ * With MDCONV_F16, MDCONV_BF16 or MDCONV_F64 tensors the flag is MDCONV_EINVAL; v1 descriptors never request it.
+ * (The value skips 16, which stays MDCONV_EINVAL like 2 above.) */
+#define MDCONV_FLAG_MATH_BF16 32
 #define MDCONV_DESC_FLAGS(d) ((d)->reserved[4])
 
 /* Initialiser of a v2 descriptor: `mdconv_desc d = MDCONV_DESC_INIT(2);` then fill in the shape.
@@ -215,6 +230,12 @@ int mdconv_input_layout_supported(const mdconv_desc *d, int layout, int backward
  * shape-generic kernels: narrow channel counts, MDCONV_PATH_DIRECT, every fp64 call -- mdconv_last_error() then names
  * the shape rule.  0 for an invalid descriptor. */
 int mdconv_deterministic_supported(const mdconv_desc *d, int backward);
+
+/* 1 if the forward (backward = 0) / backward (backward = 1) of `d` -- an MDCONV_F32 descriptor WITH MDCONV_FLAG_MATH_BF16 --
+ * would run on the bf16 kernels, else 0: an unflagged or invalid descriptor, MDCONV_PATH_DIRECT, a channels-last input,
+ * forwards of a few pixel tiles (which the fp32 kernels run faster), layers of fewer than 16 input or 16 output channels
+ * (measured: no gain, profiles/math_bf16.md) and shapes outside the native 16-bit kernels. */
+int mdconv_math_bf16_used(const mdconv_desc *d, int backward);
 
 /* Multi-GPU overlap: every backward records an event on its stream as soon
  * as grad_weight and grad_bias are final -- before the grad_input gather is enqueued.

@@ -77,6 +77,10 @@ def _desc(nd, modulated, input, weight, ksz, stride, pad, dil, group, deformable
     d.flags = _capi.FLAG_DETERMINISTIC if _capi.deterministic_mode() else 0
     # selective backward (_capi.skip_grads; include/mdconv.h: MDCONV_FLAG_NO_GRAD_INPUT / _WEIGHT; forwards ignore the flags)
     d.flags |= _capi.skip_flags()
+    # fp32 tensors, bf16 matrix math (_capi.fp32_math / torch.set_float32_matmul_precision("medium"); include/mdconv.h:
+    # MDCONV_FLAG_MATH_BF16): a permission for fp32 calls only -- the library refuses the flag on any other dtype
+    if input.dtype == torch.float32 and _capi.fp32_math_mode() == "bf16":
+        d.flags |= _capi.FLAG_MATH_BF16
     d.batch, d.c_in, d.c_out = input.shape[0], input.shape[1], weight.shape[0]
     fill = lambda v, f: tuple(int(x) for x in v) + (f,) * (3 - nd)
     d.in_sz = (ctypes.c_int * 3)(*fill(input.shape[2:], 1))

@@ -19,13 +19,14 @@ DESC_V2 = 0x100   # MDCONV_DESC_V2: the descriptor carries accumulate / input_la
 FLAG_DETERMINISTIC = 1   # MDCONV_FLAG_DETERMINISTIC, in the flags word (MdconvDesc.flags = reserved[4])
 FLAG_NO_GRAD_INPUT = 4   # MDCONV_FLAG_NO_GRAD_INPUT: the backward leaves grad_input out (value 2 stays invalid)
 FLAG_NO_GRAD_WEIGHT = 8  # MDCONV_FLAG_NO_GRAD_WEIGHT: the backward leaves grad_weight and grad_bias out
+FLAG_MATH_BF16 = 32      # MDCONV_FLAG_MATH_BF16: fp32 tensors may run on the bf16 matrix kernels (value 16 stays invalid)
 
 EXPORTS = (
     "mdconv_abi_version", "mdconv_last_error", "mdconv_out_size", "mdconv_workspace_bytes",
     "mdconv_set_path", "mdconv_last_path", "mdconv_last_kernels",
     "mdconv_profile_enable", "mdconv_profile_read", "mdconv_profile_reset", "mdconv_profile_name",
     "mdconv_stream_wait_weight_ready", "mdconv_stream_wait_weight_ready_on", "mdconv_set_accumulate", "mdconv_set_input_layout",
-    "mdconv_input_layout_supported", "mdconv_deterministic_supported",
+    "mdconv_input_layout_supported", "mdconv_deterministic_supported", "mdconv_math_bf16_used",
     "mdconv_deform_conv2d_forward", "mdconv_deform_conv2d_backward",
     "mdconv_modulated_deform_conv2d_forward", "mdconv_modulated_deform_conv2d_backward",
     "mdconv_deform_conv3d_forward", "mdconv_deform_conv3d_backward",
@@ -90,8 +91,13 @@ def lib():
         L.mdconv_input_layout_supported.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int]
         L.mdconv_deterministic_supported.restype = ctypes.c_int
         L.mdconv_deterministic_supported.argtypes = [ctypes.c_void_p, ctypes.c_int]
+        # (MDCONV_LIB may name a build from before the query existed -- the A/B tools measure such builds' exact calls)
+        has_math_query = hasattr(L, "mdconv_math_bf16_used")
+        if has_math_query:
+            L.mdconv_math_bf16_used.argtypes = [ctypes.c_void_p, ctypes.c_int]
         for name in EXPORTS[11:]:
-            getattr(L, name).restype = ctypes.c_int
+            if name != "mdconv_math_bf16_used" or has_math_query:
+                getattr(L, name).restype = ctypes.c_int
         if L.mdconv_abi_version() != ABI_VERSION:
             raise ImportError("libmdconv_hip.so ABI version mismatch")
         _lib = L
@@ -205,6 +211,46 @@ class weight_grads_f32:
 
     def __exit__(self, *exc):
         _modes.weight_grads_f32 = self._prev
+        return False
+
+
+def fp32_math_override():
+    """``"bf16"`` / ``"fp32"`` inside an ``fp32_math`` context manager of this thread, None outside."""
+    return getattr(_modes, "fp32_math", None)
+
+
+def fp32_math_mode():
+    """The matrix arithmetic of an fp32 call issued now: ``"bf16"`` (its descriptor carries ``MDCONV_FLAG_MATH_BF16``,
+    include/mdconv.h) or ``"fp32"``.  The innermost ``fp32_math`` context manager of this thread when one is active, otherwise
+    ``"bf16"`` exactly when ``torch.get_float32_matmul_precision() == "medium"`` ("bfloat16 for internal computations, if a
+    fast algorithm is available") -- read at the call.  "high" and "highest" stay exact: there is no TF32-class kernel."""
+    over = fp32_math_override()
+    if over is not None:
+        return over
+    import torch
+    return "bf16" if torch.get_float32_matmul_precision() == "medium" else "fp32"
+
+
+class fp32_math:
+    """Context manager: fp32 calls of MDCONV_CUDA issued inside by this thread may run their matrix products in bf16
+    (``"bf16"``: ``MDCONV_FLAG_MATH_BF16`` -- fp32 tensors in and out, bf16 operands, fp32 sampling, accumulation and weight
+    gradients, wherever the native 16-bit kernels take the shape; other shapes run exactly as without it) or run exact
+    (``"fp32"``), whatever ``torch.set_float32_matmul_precision`` says.  No effect on fp16 / bf16 / fp64 tensors.
+    Thread-local, nests, and travels in each call's descriptor like ``overwrite_grads``; the autograd Functions record the
+    mode in forward and enter it in backward themselves."""
+
+    def __init__(self, mode="bf16"):
+        if mode not in ("bf16", "fp32"):
+            raise ValueError('fp32_math mode must be "bf16" or "fp32", got %r' % (mode,))
+        self._mode = mode
+
+    def __enter__(self):
+        self._prev = fp32_math_override()
+        _modes.fp32_math = self._mode
+        return self
+
+    def __exit__(self, *exc):
+        _modes.fp32_math = self._prev
         return False
 
 

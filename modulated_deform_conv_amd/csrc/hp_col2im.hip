@@ -94,12 +94,13 @@ constexpr int kRun = 8;   // targets per run
 // LPD lanes (8 channels each) follow one list; a wave walks 64 / LPD runs of kRun consecutive
 // targets side by side; workgroup tile = 4 * (64 / LPD) runs.  Channel units of LPD * 8 channels
 // (one deformable group each when DG > 1) are processed one after the other.
-template <int ND, typename T, int LPD>
+// OT: the type grad_input is stored in (F32IO: fp32 tensors on the bf16 kernels)
+template <int ND, typename T, int LPD, typename OT = T>
 __global__ __launch_bounds__(256) void hp_col2im_kernel(Geom g, HpDims hd, int S_e,
                                                         const typename T::Raw *__restrict__ gcol,
                                                         const int *__restrict__ rowptr,
                                                         const int4 *__restrict__ entries,
-                                                        typename T::Raw *__restrict__ grad_input) {
+                                                        typename OT::Raw *__restrict__ grad_input) {
   using Raw = typename T::Raw;
   constexpr int L = ND - 1, NR = 1 << L;   // anchor rows that reach a target
   constexpr int NQ = 64 / LPD, RUNS = 4 * NQ, QT = RUNS * kRun;
@@ -213,9 +214,9 @@ __global__ __launch_bounds__(256) void hp_col2im_kernel(Geom g, HpDims hd, int S
       const int cl = x / QT, ql = x - cl * QT;
       const int c = c_lo + cl, q = q0 + ql;
       if (c < min(c_end, g.C) && q < g.S_i) {
-        Raw *dst = grad_input + ((int64_t)b * g.C + c) * g.S_i + q;
+        typename OT::Raw *dst = grad_input + ((int64_t)b * g.C + c) * g.S_i + q;
         const float v = tile[cl * TP + ql];
-        T::stf(dst, g.acc_data ? T::ldf(dst) + v : v);
+        OT::stf(dst, g.acc_data ? OT::ldf(dst) + v : v);
       }
     }
     __syncthreads();
@@ -564,11 +565,10 @@ __global__ __launch_bounds__(256, NB <= 2 ? 4 : (NB == 4 ? 3 : 1)) void hp_col2i
 
 // pass 2: grad_input[b][c][t] (+)= sum_s A[segment(b, c)][anchor row t + s][x][s][c]; workgroup = 64
 // consecutive targets x 64 channels, lanes = (target, channel octet), LDS transpose to [B, C, S_i]
-template <int ND, typename T>
+template <int ND, typename T, typename OT = T>
 __global__ __launch_bounds__(256) void hp_col2im_combine_kernel(Geom g, HpDims hd, int S_e,
                                                                 const typename SumStore<T>::type *__restrict__ sums,
-                                                                typename T::Raw *__restrict__ grad_input) {
-  using Raw = typename T::Raw;
+                                                                typename OT::Raw *__restrict__ grad_input) {
   using Sum = typename SumStore<T>::type;
   constexpr bool WIDE = sizeof(Sum) == 4;
   constexpr int L = ND - 1, NS = 1 << L;
@@ -619,16 +619,16 @@ __global__ __launch_bounds__(256) void hp_col2im_combine_kernel(Geom g, HpDims h
       const int cl = x / QT, ql = x - cl * QT;
       const int c = caller_channel(g, c0 + cl), q = q0 + ql;
       if (c >= 0 && q < g.S_i) {
-        Raw *dst = grad_input + ((int64_t)b * caller_channels(g) + c) * g.S_i + q;
+        typename OT::Raw *dst = grad_input + ((int64_t)b * caller_channels(g) + c) * g.S_i + q;
         const float v = (float)tile[cl * TP + ql];
-        T::stf(dst, g.acc_data ? T::ldf(dst) + v : v);
+        OT::stf(dst, g.acc_data ? OT::ldf(dst) + v : v);
       }
     }
     __syncthreads();
   }
 }
 
-template <int ND, typename T>
+template <int ND, typename T, typename OT = T>
 int launch_col2im(const Geom &g, const HpDims &hd, const Tensors &t, const void *gcol,
                   const int *rowptr, const void *entries, hipStream_t stream) {
   using Raw = typename T::Raw;
@@ -638,9 +638,9 @@ int launch_col2im(const Geom &g, const HpDims &hd, const Tensors &t, const void 
 #define HP_C2I(LPD)                                                                              \
   do {                                                                                           \
     const int qt = 4 * (64 / LPD) * kRun;                                                        \
-    hipLaunchKernelGGL((hp_col2im_kernel<ND, T, LPD>), dim3(g.B * ((g.S_i + qt - 1) / qt)),      \
+    hipLaunchKernelGGL((hp_col2im_kernel<ND, T, LPD, OT>), dim3(g.B * ((g.S_i + qt - 1) / qt)),  \
                        dim3(256), 0, stream, g, hd, S_e, (const Raw *)gcol, rowptr,              \
-                       (const int4 *)entries, (Raw *)t.grad_input);                              \
+                       (const int4 *)entries, (typename OT::Raw *)t.grad_input);                 \
   } while (0)
   if (lanes <= 4) HP_C2I(4);
   else if (lanes <= 8) HP_C2I(8);
@@ -685,7 +685,7 @@ int hp_csr_build(const Geom &g, int dtype, const Tensors &t, int *cnt, int *rowp
   return check_launch("hp_csr_fill");
 }
 
-template <int ND, typename T>
+template <int ND, typename T, typename OT = T>
 static int launch_col2im2(const Geom &g, const HpDims &hd, const Tensors &t, const void *gcol, const int *rowptr,
                    const void *entries, void *sums, hipStream_t stream) {
   using Raw = typename T::Raw;
@@ -730,8 +730,8 @@ static int launch_col2im2(const Geom &g, const HpDims &hd, const Tensors &t, con
 #undef HP_C2S
   int rc = check_launch("hp_col2im_sums");
   if (rc) return rc;
-  hipLaunchKernelGGL((hp_col2im_combine_kernel<ND, T>), dim3(g.B * ((g.S_i + 63) / 64)), dim3(256), 0, stream, g, hd,
-                     S_e, (const typename SumStore<T>::type *)sums, (Raw *)t.grad_input);
+  hipLaunchKernelGGL((hp_col2im_combine_kernel<ND, T, OT>), dim3(g.B * ((g.S_i + 63) / 64)), dim3(256), 0, stream, g, hd,
+                     S_e, (const typename SumStore<T>::type *)sums, (typename OT::Raw *)t.grad_input);
   return check_launch("hp_col2im_combine");
 }
 
@@ -742,6 +742,9 @@ size_t hp_col2im_sums_bytes(const Geom &g, const HpDims &hd, int dtype) {
 
 int hp_col2im2(const Geom &g, const HpDims &hd, int dtype, const Tensors &t, const void *gcol,
                const int *rowptr, const void *entries, void *sums, hipStream_t stream) {
+  if (t.io32)   // fp32 grad_input
+    return g.nd == 2 ? launch_col2im2<2, BF16, F32IO>(g, hd, t, gcol, rowptr, entries, sums, stream)
+                     : launch_col2im2<3, BF16, F32IO>(g, hd, t, gcol, rowptr, entries, sums, stream);
   if (dtype == MDCONV_F16)
     return g.nd == 2 ? launch_col2im2<2, F16>(g, hd, t, gcol, rowptr, entries, sums, stream)
                      : launch_col2im2<3, F16>(g, hd, t, gcol, rowptr, entries, sums, stream);
@@ -751,6 +754,9 @@ int hp_col2im2(const Geom &g, const HpDims &hd, int dtype, const Tensors &t, con
 
 int hp_col2im(const Geom &g, const HpDims &hd, int dtype, const Tensors &t, const void *gcol,
               const int *rowptr, const void *entries, hipStream_t stream) {
+  if (t.io32)   // fp32 grad_input
+    return g.nd == 2 ? launch_col2im<2, BF16, F32IO>(g, hd, t, gcol, rowptr, entries, stream)
+                     : launch_col2im<3, BF16, F32IO>(g, hd, t, gcol, rowptr, entries, stream);
   if (dtype == MDCONV_F16)
     return g.nd == 2 ? launch_col2im<2, F16>(g, hd, t, gcol, rowptr, entries, stream)
                      : launch_col2im<3, F16>(g, hd, t, gcol, rowptr, entries, stream);

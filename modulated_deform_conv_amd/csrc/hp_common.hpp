@@ -109,6 +109,17 @@ struct BF16 {
   }
 };
 
+// fp32 tensors on the bf16 kernels (MDCONV_FLAG_MATH_BF16, Tensors::io32): the type `output` (with `bias`) and `grad_input`
+// are stored in -- the kernels' output policy OT, by default the tensors' own 16-bit type T.  The fp32 the epilogue already
+// holds (accumulators, the gather's LDS tile) is stored as it is, and accumulate mode adds in fp32.
+struct F32IO {
+  using Raw = float;
+  static __device__ __forceinline__ float ldf(const Raw *p) { return *p; }
+  static __device__ __forceinline__ void stf(Raw *p, float v) { *p = v; }
+};
+// one fp32 value as the bf16 matrix operand it becomes: the rounding of BF16::stf / BF16::pack (to nearest even)
+__device__ __forceinline__ unsigned short bf16_operand_bits(float v) { return __builtin_bit_cast(unsigned short, (__bf16)v); }
+
 // Sampling elements -- offset, mask, grad_offset, grad_mask: the tensors' own 16-bit type (the kernels' default
 // template argument SE = T::Raw) or fp32 (MDCONV_SAMPLING_F32: loaded as dwords straight into the fp32 sampling state)
 __device__ __forceinline__ float samp_ld(const _Float16 *p) { return (float)*p; }

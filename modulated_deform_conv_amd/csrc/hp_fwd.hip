@@ -25,11 +25,12 @@ namespace {
 
 constexpr int kStage = 4;   // 16-channel chunks per LDS stage of the weights
 
-template <int ND, bool MOD, typename T, int MB, typename SE = typename T::Raw>
+// OT: the type `bias` and `output` are stored in (F32IO: fp32 tensors on the bf16 kernels)
+template <int ND, bool MOD, typename T, int MB, typename SE = typename T::Raw, typename OT = T>
 __global__ __launch_bounds__(256, 2) void hp_fwd_kernel(
     Geom g, HpDims hd, const typename T::Raw *__restrict__ xt, const U4 *__restrict__ wpf,
-    const typename T::Raw *__restrict__ bias, const SE *__restrict__ offset,
-    const SE *__restrict__ mask, typename T::Raw *__restrict__ output,
+    const typename OT::Raw *__restrict__ bias, const SE *__restrict__ offset,
+    const SE *__restrict__ mask, typename OT::Raw *__restrict__ output,
     const int2 *__restrict__ ctab) {
   constexpr int NC = 1 << ND;
   __shared__ U4 As[2][kStage][MB][64];
@@ -210,7 +211,7 @@ __global__ __launch_bounds__(256, 2) void hp_fwd_kernel(
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           const int o = (orange * MB + ob) * 32 + (r & 3) + 8 * (r >> 2) + 4 * kh;
-          acc[ob][r] += T::ldf(bias + (o < g.O ? o : 0));
+          acc[ob][r] += OT::ldf(bias + (o < g.O ? o : 0));
         }
     }
 #pragma unroll
@@ -218,22 +219,23 @@ __global__ __launch_bounds__(256, 2) void hp_fwd_kernel(
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const int o = (orange * MB + ob) * 32 + (r & 3) + 8 * (r >> 2) + 4 * kh;
-        if (o < g.O) T::stf(output + ((int64_t)b * g.O + o) * g.S_o + pix, acc[ob][r]);
+        if (o < g.O) OT::stf(output + ((int64_t)b * g.O + o) * g.S_o + pix, acc[ob][r]);
       }
   }
 }
 
 }  // namespace
 
-template <int ND, bool MOD, typename T, typename SE>
+template <int ND, bool MOD, typename T, typename SE, typename OT = T>
 static int launch_fwd_hp(const Geom &g, const HpDims &hd, const Tensors &t, const void *xt,
                          const void *wpf, const int2 *ctab, hipStream_t stream) {
   using Raw = typename T::Raw;
+  using Out = typename OT::Raw;
   const dim3 grid((g.N + 127) / 128, hd.oranges);
 #define HP_FWD(MBV)                                                                              \
-  hipLaunchKernelGGL((hp_fwd_kernel<ND, MOD, T, MBV, SE>), grid, dim3(256), 0, stream, g, hd,       \
-                     (const Raw *)xt, (const U4 *)wpf, (const Raw *)t.bias, (const SE *)t.offset,   \
-                     (const SE *)t.mask, (Raw *)t.output, ctab)
+  hipLaunchKernelGGL((hp_fwd_kernel<ND, MOD, T, MBV, SE, OT>), grid, dim3(256), 0, stream, g, hd,   \
+                     (const Raw *)xt, (const U4 *)wpf, (const Out *)t.bias, (const SE *)t.offset,   \
+                     (const SE *)t.mask, (Out *)t.output, ctab)
   switch (hd.MB) {
     case 1: HP_FWD(1); break;
     case 2: HP_FWD(2); break;
@@ -245,14 +247,15 @@ static int launch_fwd_hp(const Geom &g, const HpDims &hd, const Tensors &t, cons
 
 int hp_forward_launch(const Geom &g, const HpDims &hd, int dtype, const Tensors &t, const void *xt,
                       const void *wpf, const int2 *ctab, hipStream_t stream) {
-#define HP_DISPATCH(T, SE)                                                                    \
-  do {                                                                                       \
-    if (g.nd == 2)                                                                           \
-      return g.modulated ? launch_fwd_hp<2, true, T, SE>(g, hd, t, xt, wpf, ctab, stream)      \
-                         : launch_fwd_hp<2, false, T, SE>(g, hd, t, xt, wpf, ctab, stream);    \
-    return g.modulated ? launch_fwd_hp<3, true, T, SE>(g, hd, t, xt, wpf, ctab, stream)        \
-                       : launch_fwd_hp<3, false, T, SE>(g, hd, t, xt, wpf, ctab, stream);      \
+#define HP_DISPATCH(...)                                                                              \
+  do {                                                                                               \
+    if (g.nd == 2)                                                                                   \
+      return g.modulated ? launch_fwd_hp<2, true, __VA_ARGS__>(g, hd, t, xt, wpf, ctab, stream)        \
+                         : launch_fwd_hp<2, false, __VA_ARGS__>(g, hd, t, xt, wpf, ctab, stream);      \
+    return g.modulated ? launch_fwd_hp<3, true, __VA_ARGS__>(g, hd, t, xt, wpf, ctab, stream)          \
+                       : launch_fwd_hp<3, false, __VA_ARGS__>(g, hd, t, xt, wpf, ctab, stream);        \
   } while (0)
+  if (t.io32) HP_DISPATCH(BF16, float, F32IO);   // fp32 bias and output (and fp32 offsets / masks)
   if (t.samp32) {
     if (dtype == MDCONV_F16) HP_DISPATCH(F16, float);
     HP_DISPATCH(BF16, float);

@@ -30,11 +30,12 @@ constexpr int kStSlots = 3;
 constexpr int kBtP = 72;     // LDS pitch (16-bit elements) of a pixel row of the B tile: 64 + 8
 
 // GRP = false: one conv group -- every chunk feeds every output-channel block, no table lookups.
-template <int ND, bool MOD, typename T, int MB, bool GRP, typename SE = typename T::Raw>
+// OT: the type `bias` and `output` are stored in (F32IO: fp32 tensors on the bf16 kernels)
+template <int ND, bool MOD, typename T, int MB, bool GRP, typename SE = typename T::Raw, typename OT = T>
 __global__ __launch_bounds__(256, 2) void hp_fwd2_kernel(
     Geom g, HpDims hd, const typename T::Raw *__restrict__ xt, const U4 *__restrict__ wpf,
-    const typename T::Raw *__restrict__ bias, const SE *__restrict__ offset,
-    const SE *__restrict__ mask, typename T::Raw *__restrict__ output,
+    const typename OT::Raw *__restrict__ bias, const SE *__restrict__ offset,
+    const SE *__restrict__ mask, typename OT::Raw *__restrict__ output,
     const int2 *__restrict__ ctab) {
   using Raw = typename T::Raw;
   constexpr int NC = 1 << ND;
@@ -310,7 +311,7 @@ __global__ __launch_bounds__(256, 2) void hp_fwd2_kernel(
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           const int o = (orange * MB + ob) * 32 + (r & 3) + 8 * (r >> 2) + 4 * kh;
-          acc[ob][r] += T::ldf(bias + (o < g.O ? o : 0));
+          acc[ob][r] += OT::ldf(bias + (o < g.O ? o : 0));
         }
     }
 #pragma unroll
@@ -318,7 +319,7 @@ __global__ __launch_bounds__(256, 2) void hp_fwd2_kernel(
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const int o = (orange * MB + ob) * 32 + (r & 3) + 8 * (r >> 2) + 4 * kh;
-        if (o < g.O) T::stf(output + ((int64_t)b * g.O + o) * g.S_o + pix, acc[ob][r]);
+        if (o < g.O) OT::stf(output + ((int64_t)b * g.O + o) * g.S_o + pix, acc[ob][r]);
       }
   }
 }
@@ -332,10 +333,11 @@ size_t hp_fwd2_lds_bytes(const Geom &g, const HpDims &hd) {
   return (size_t)2 * kStage * (g.G == 1 ? hd.MB : hd.fwd_nmax) * 1024 + (size_t)4 * 32 * kBtP * 2 + (size_t)4 * kStSlots * 32 * 2 * nc * 4 + win;
 }
 
-template <int ND, bool MOD, typename T, typename SE>
+template <int ND, bool MOD, typename T, typename SE, typename OT = T>
 static int launch_fwd2_hp(const Geom &g, const HpDims &hd, const Tensors &t, const void *xt,
                           const void *wpf, const int2 *ctab, hipStream_t stream) {
   using Raw = typename T::Raw;
+  using Out = typename OT::Raw;
   const dim3 grid((g.N + 127) / 128, hd.oranges);
   const size_t lds = hp_fwd2_lds_bytes(g, hd);
 #define HP_FWD2(MBV)                                                                             \
@@ -345,14 +347,14 @@ static int launch_fwd2_hp(const Geom &g, const HpDims &hd, const Tensors &t, con
 #define HP_FWD2_(MBV, GRPV)                                                                      \
   do {                                                                                           \
     if (lds > 64 * 1024) {                                                                       \
-      hipError_t ea = hipFuncSetAttribute((const void *)hp_fwd2_kernel<ND, MOD, T, MBV, GRPV, SE>,    \
+      hipError_t ea = hipFuncSetAttribute((const void *)hp_fwd2_kernel<ND, MOD, T, MBV, GRPV, SE, OT>,    \
                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
       if (ea != hipSuccess) { set_error("hipFuncSetAttribute: %s", hipGetErrorString(ea)); return MDCONV_ELAUNCH; } \
     }                                                                                            \
-    hp_debug_plan("hp_fwd2", hp_fwd2_kernel<ND, MOD, T, MBV, GRPV, SE>, 256, lds, (long)grid.x * grid.y);   \
-    hipLaunchKernelGGL((hp_fwd2_kernel<ND, MOD, T, MBV, GRPV, SE>), grid, dim3(256), lds, stream, g, hd, \
-                       (const Raw *)xt, (const U4 *)wpf, (const Raw *)t.bias, (const SE *)t.offset, \
-                       (const SE *)t.mask, (Raw *)t.output, ctab);                              \
+    hp_debug_plan("hp_fwd2", hp_fwd2_kernel<ND, MOD, T, MBV, GRPV, SE, OT>, 256, lds, (long)grid.x * grid.y);   \
+    hipLaunchKernelGGL((hp_fwd2_kernel<ND, MOD, T, MBV, GRPV, SE, OT>), grid, dim3(256), lds, stream, g, hd, \
+                       (const Raw *)xt, (const U4 *)wpf, (const Out *)t.bias, (const SE *)t.offset, \
+                       (const SE *)t.mask, (Out *)t.output, ctab);                              \
   } while (0)
   switch (hd.MB) {
     case 1: HP_FWD2(1); break;
@@ -366,14 +368,15 @@ static int launch_fwd2_hp(const Geom &g, const HpDims &hd, const Tensors &t, con
 
 int hp_forward2_launch(const Geom &g, const HpDims &hd, int dtype, const Tensors &t, const void *xt,
                        const void *wpf, const int2 *ctab, hipStream_t stream) {
-#define HP_DISPATCH(T, SE)                                                                    \
-  do {                                                                                       \
-    if (g.nd == 2)                                                                           \
-      return g.modulated ? launch_fwd2_hp<2, true, T, SE>(g, hd, t, xt, wpf, ctab, stream)     \
-                         : launch_fwd2_hp<2, false, T, SE>(g, hd, t, xt, wpf, ctab, stream);   \
-    return g.modulated ? launch_fwd2_hp<3, true, T, SE>(g, hd, t, xt, wpf, ctab, stream)       \
-                       : launch_fwd2_hp<3, false, T, SE>(g, hd, t, xt, wpf, ctab, stream);     \
+#define HP_DISPATCH(...)                                                                              \
+  do {                                                                                               \
+    if (g.nd == 2)                                                                                   \
+      return g.modulated ? launch_fwd2_hp<2, true, __VA_ARGS__>(g, hd, t, xt, wpf, ctab, stream)       \
+                         : launch_fwd2_hp<2, false, __VA_ARGS__>(g, hd, t, xt, wpf, ctab, stream);     \
+    return g.modulated ? launch_fwd2_hp<3, true, __VA_ARGS__>(g, hd, t, xt, wpf, ctab, stream)         \
+                       : launch_fwd2_hp<3, false, __VA_ARGS__>(g, hd, t, xt, wpf, ctab, stream);       \
   } while (0)
+  if (t.io32) HP_DISPATCH(BF16, float, F32IO);   // fp32 bias and output (and fp32 offsets / masks)
   if (t.samp32) {
     if (dtype == MDCONV_F16) HP_DISPATCH(F16, float);
     HP_DISPATCH(BF16, float);

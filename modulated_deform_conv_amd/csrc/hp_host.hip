@@ -110,7 +110,7 @@ int hp_entry_width(const Geom &g, int dtype) { return g.nd == 2 && dtype == MDCO
 
 // Bytes one chunk needs in every slot of the backward layout whose size depends on the chunk (the packed W^T, the block
 // table and the running fp32 grad_weight depend on the call alone); `ranges`: pixel ranges per tap in the fp32 partials
-struct BwdNeed { size_t xt, gcol, col, part, cnt, rowptr, entries, sums, sort; };
+struct BwdNeed { size_t xt, gcol, col, part, cnt, rowptr, entries, sums, sort, go16; };
 BwdNeed bwd_need(const HpChunk &c, int ranges, int dtype, bool two_pass_gather) {
   const Geom &gc = c.gc;
   const HpDims &hd = c.hd;
@@ -128,6 +128,7 @@ BwdNeed bwd_need(const HpChunk &c, int ranges, int dtype, bool two_pass_gather) 
   n.sums = two_pass_gather ? hp_col2im_sums_bytes(gc, hd, dtype) : 0;
   // deterministic mode (Geom::det): scratch of the list sort, shaped like the entries (csr_sort.hip)
   n.sort = gc.det ? csr_sort_scratch_bytes(hp_entry_width(gc, dtype), (int64_t)gc.K * gc.S_o, gc.B * gc.DG) : 0;
+  n.go16 = (size_t)gc.B * gc.O * gc.S_o * 2;   // (laid out for fp32 tensors on the bf16 kernels only)
   return n;
 }
 
@@ -135,7 +136,8 @@ BwdNeed bwd_need(const HpChunk &c, int ranges, int dtype, bool two_pass_gather) 
 // `skip`: without weight gradients no column rows (hp_bwd3 runs its variant without them), no running grad_weight, and
 // no partials unless a chunk runs a kernel with GEMM-2 fused in (`fused_partials`: hp_bwd2 / hp_bwd write and discard them);
 // without grad_input no row pointers, entries, partial sums or sort scratch -- the counters stay, the kernels count into them
-HpBwdLayout bwd_layout(const HpChunk &c, int dtype, bool two_pass_gather, Skip skip = Skip(), bool fused_partials = true) {
+// `io32`: the bf16 copy of a chunk's fp32 grad_output, last, so that every other slot sits where the bf16 call has it
+HpBwdLayout bwd_layout(const HpChunk &c, int dtype, bool two_pass_gather, bool io32, Skip skip = Skip(), bool fused_partials = true) {
   const Geom &gc = c.gc;
   const HpDims &hd = c.hd;
   // a shorter last chunk can have MORE ranges than a full one (ranges is not monotonic in the tile
@@ -160,6 +162,7 @@ HpBwdLayout bwd_layout(const HpChunk &c, int dtype, bool two_pass_gather, Skip s
   L.off_entries = b.take(n.entries);
   L.off_sums = b.take(n.sums);
   L.off_sort = b.take(n.sort);
+  L.off_go16 = b.take(io32 ? n.go16 : 0);
   L.total = b.off;
   return L;
 }
@@ -167,14 +170,14 @@ HpBwdLayout bwd_layout(const HpChunk &c, int dtype, bool two_pass_gather, Skip s
 // The layout is made for the full chunk; a tail chunk has its own dimensions and picks its own kernel (it may take hp_bwd3
 // where the full chunk did not, or have more pixel ranges), so what it needs is compared with every slot it uses.
 // Returns the name of a slot that is too small for chunk `c`, or null.
-const char *bwd_short_slot(const HpBwdLayout &L, const HpChunk &c, int dtype, bool two_pass_gather) {
+const char *bwd_short_slot(const HpBwdLayout &L, const HpChunk &c, int dtype, bool two_pass_gather, bool io32) {
   const BwdNeed n = bwd_need(c, c.bwd == HpChunk::BWD3 ? c.hd.ranges_w : c.hd.ranges, dtype, two_pass_gather);
   const struct { const char *name; size_t need, have; } slots[] = {
       {"channels-last input copy", n.xt, L.off_w - L.off_xt},   {"grad_col rows", n.gcol, L.off_col - L.off_gcol},
       {"column rows", n.col, L.off_part - L.off_col},           {"grad_weight partials", n.part, L.off_gw32 - L.off_part},
       {"list counters", n.cnt, L.off_rowptr - L.off_cnt},       {"list row pointers", n.rowptr, L.off_entries - L.off_rowptr},
       {"list entries", n.entries, L.off_sums - L.off_entries},  {"partial sums", n.sums, L.off_sort - L.off_sums},
-      {"sort scratch", n.sort, L.total - L.off_sort}};
+      {"sort scratch", n.sort, L.off_go16 - L.off_sort},        {"grad_output copy", io32 ? n.go16 : 0, L.total - L.off_go16}};
   for (const auto &s : slots)
     if (s.need > s.have) return s.name;
   return nullptr;
@@ -370,7 +373,7 @@ static bool forward_preferred(const Geom &gcall, const Geom &g, int dtype) {
   return !mfma_supported(gcall, dtype, false);
 }
 
-bool hp_plan(const Geom &gcall, int dtype, bool backward, HpPlan *p, Skip skip) {
+bool hp_plan(const Geom &gcall, int dtype, bool backward, HpPlan *p, Skip skip, bool io32) {
   // the geometry the kernels run: the caller's -- or, in the backward, its width-padded form where the full chunk of THAT
   // takes hp_bwd3 --, else the group-padded form
   Geom gv;
@@ -386,15 +389,16 @@ bool hp_plan(const Geom &gcall, int dtype, bool backward, HpPlan *p, Skip skip) 
   p->fwd = HpFwdLayout();
   p->bwd = HpBwdLayout();
   p->skip = Skip();
+  p->io32 = io32;
   if (!backward) {
     p->fwd = fwd_layout(p->full.gc, p->full.hd);
     p->total = p->fwd.total;
     return true;
   }
-  p->bwd = bwd_layout(p->full, dtype, p->two_pass_gather);
+  p->bwd = bwd_layout(p->full, dtype, p->two_pass_gather, io32);
   p->total = p->bwd.total;
   for (const HpChunk *c : {&p->full, &p->tail}) {
-    const char *slot = bwd_short_slot(p->bwd, *c, dtype, p->two_pass_gather);
+    const char *slot = bwd_short_slot(p->bwd, *c, dtype, p->two_pass_gather, io32);
     if (slot) {
       set_error("hp_plan: the %s of a chunk of %d images do not fit the slot laid out for chunks of %d", slot, c->gc.B, p->Bc);
       return false;
@@ -405,20 +409,30 @@ bool hp_plan(const Geom &gcall, int dtype, bool backward, HpPlan *p, Skip skip) 
   p->skip = skip;
   if (skip.input || skip.weight) {
     const bool fused = p->full.bwd != HpChunk::BWD3 || p->tail.bwd != HpChunk::BWD3;   // a chunk writes fp32 partials itself
-    p->bwd = bwd_layout(p->full, dtype, p->two_pass_gather, skip, fused);
+    p->bwd = bwd_layout(p->full, dtype, p->two_pass_gather, io32, skip, fused);
     p->total = p->bwd.total;
   }
   return true;
 }
 
-int hp_forward(int dtype, const HpPlan &p, const Tensors &t, void *ws, hipStream_t stream) {
+// the tensor modes of a plan for fp32 tensors follow from the plan alone: fp32 offsets / masks, fp32 weight gradients, fp32 in and out
+static Tensors plan_tensors(const HpPlan &p, Tensors t) {
+  t.io32 = p.io32 ? 1 : 0;
+  if (p.io32) t.samp32 = t.wgrad32 = 1;
+  return t;
+}
+
+int hp_forward(int dtype, const HpPlan &p, const Tensors &t_call, void *ws, hipStream_t stream) {
+  const Tensors t = plan_tensors(p, t_call);
   const Geom &g = p.g;
   const HpFwdLayout &L = p.fwd;
   char *base = (char *)ws;
   const int nc_off = g.DG * g.nd * g.K, nc_m = g.DG * g.K;
   const size_t es_s = samp_bytes(dtype, t);   // offset / mask element: 2, or 4 with fp32 sampling
+  const bool io32 = p.io32;                   // fp32 tensors: the layout passes round to bf16, the kernel stores fp32
+  const size_t es = io32 ? 4 : 2;             // input / output element
   int rc;
-  if ((rc = hp_pack_fwd_weights(p.full.gc, p.full.hd, dtype, t.weight, base + L.off_w, (int2 *)(base + L.off_tab), stream)))
+  if ((rc = hp_pack_fwd_weights(p.full.gc, p.full.hd, dtype, t.weight, io32, base + L.off_w, (int2 *)(base + L.off_tab), stream)))
     return rc;
   for (int b0 = 0; b0 < g.B; b0 += p.Bc) {
     const int bc = g.B - b0 < p.Bc ? g.B - b0 : p.Bc;
@@ -426,13 +440,13 @@ int hp_forward(int dtype, const HpPlan &p, const Tensors &t, void *ws, hipStream
     const Geom &gc = c.gc;
     const HpDims &hd = c.hd;
     Tensors tc = t;
-    tc.input = (const char *)t.input + (size_t)b0 * caller_channels(g) * g.S_i * 2;
+    tc.input = (const char *)t.input + (size_t)b0 * caller_channels(g) * g.S_i * es;
     tc.offset = (const char *)t.offset + (size_t)b0 * nc_off * g.S_o * es_s;
     tc.mask = t.mask ? (const char *)t.mask + (size_t)b0 * nc_m * g.S_o * es_s : nullptr;
-    tc.output = (char *)t.output + (size_t)b0 * g.O * g.S_o * 2;
+    tc.output = (char *)t.output + (size_t)b0 * g.O * g.S_o * es;
     const void *xt = base + L.off_xt;
-    if (g.in_cl) xt = (const char *)t.input + (size_t)b0 * g.S_i * g.C * 2;   // already channels-last
-    else if ((rc = hp_nchw_to_nhwc(gc, hd, tc.input, base + L.off_xt, stream))) return rc;
+    if (g.in_cl) xt = (const char *)t.input + (size_t)b0 * g.S_i * g.C * 2;   // already channels-last (16-bit tensors only)
+    else if ((rc = hp_nchw_to_nhwc(gc, hd, tc.input, base + L.off_xt, io32, stream))) return rc;
     profile_mark(0, true, stream, c.fwd2 ? "hp_fwd2_kernel" : "hp_fwd_kernel");
     if (c.fwd2)
       rc = hp_forward2_launch(gc, hd, dtype, tc, xt, base + L.off_w,
@@ -446,7 +460,8 @@ int hp_forward(int dtype, const HpPlan &p, const Tensors &t, void *ws, hipStream
   return MDCONV_OK;
 }
 
-int hp_backward(int dtype, const HpPlan &p, const Tensors &t, void *ws, hipStream_t stream) {
+int hp_backward(int dtype, const HpPlan &p, const Tensors &t_call, void *ws, hipStream_t stream) {
+  const Tensors t = plan_tensors(p, t_call);
   const Geom &g = p.g;
   const int Bc = p.Bc;
   const HpBwdLayout &L = p.bwd;
@@ -454,10 +469,15 @@ int hp_backward(int dtype, const HpPlan &p, const Tensors &t, void *ws, hipStrea
   const int nc_off = g.DG * g.nd * g.K, nc_m = g.DG * g.K;
   const size_t es_s = samp_bytes(dtype, t);   // offset / mask element: 2, or 4 with fp32 sampling
   const Skip skip = p.skip;
+  // fp32 tensors: the layout passes round input and weights to bf16, grad_output gets a bf16 copy per chunk (off_go16),
+  // the gather stores fp32 grad_input
+  const bool io32 = p.io32;
+  const size_t es = io32 ? 4 : 2;   // input / grad_output / grad_input element
   int rc;
-  if ((rc = hp_pack_bwd_weights(p.full.gc, p.full.hd, dtype, t.weight, base + L.off_w, (int4 *)(base + L.off_tab), stream)))
+  if ((rc = hp_pack_bwd_weights(p.full.gc, p.full.hd, dtype, t.weight, io32, base + L.off_w, (int4 *)(base + L.off_tab), stream)))
     return rc;
-  if (g.with_bias && !skip.weight && (rc = hp_grad_bias(g, dtype, t.grad_output, t.grad_bias, t.wgrad32 != 0, stream))) return rc;
+  if (g.with_bias && !skip.weight && !io32 && (rc = hp_grad_bias(g, dtype, t.grad_output, t.grad_bias, t.wgrad32 != 0, stream)))
+    return rc;
   for (int b0 = 0; b0 < g.B; b0 += Bc) {
     const int bc = g.B - b0 < Bc ? g.B - b0 : Bc;
     const HpChunk &c = bc == Bc ? p.full : p.tail;
@@ -465,17 +485,28 @@ int hp_backward(int dtype, const HpPlan &p, const Tensors &t, void *ws, hipStrea
     const HpDims &hd = c.hd;
     const bool multi = Bc < g.B, first = b0 == 0, last = b0 + bc >= g.B;
     Tensors tc = t;
-    tc.input = (const char *)t.input + (size_t)b0 * caller_channels(g) * g.S_i * 2;
+    tc.input = (const char *)t.input + (size_t)b0 * caller_channels(g) * g.S_i * es;
     tc.offset = (const char *)t.offset + (size_t)b0 * nc_off * g.S_o * es_s;
     tc.mask = t.mask ? (const char *)t.mask + (size_t)b0 * nc_m * g.S_o * es_s : nullptr;
-    tc.grad_output = (const char *)t.grad_output + (size_t)b0 * g.O * g.S_o * 2;
-    tc.grad_input = skip.input ? nullptr : (char *)t.grad_input + (size_t)b0 * caller_channels(g) * g.S_i * 2;
+    tc.grad_output = (const char *)t.grad_output + (size_t)b0 * g.O * g.S_o * es;
+    tc.grad_input = skip.input ? nullptr : (char *)t.grad_input + (size_t)b0 * caller_channels(g) * g.S_i * es;
     tc.grad_offset = (char *)t.grad_offset + (size_t)b0 * nc_off * g.S_o * es_s;
     tc.grad_mask = t.grad_mask ? (char *)t.grad_mask + (size_t)b0 * nc_m * g.S_o * es_s : nullptr;
     int *cnt = (int *)(base + L.off_cnt), *rowptr = (int *)(base + L.off_rowptr);
     const void *xt = base + L.off_xt;
-    if (g.in_cl) xt = (const char *)t.input + (size_t)b0 * g.S_i * g.C * 2;   // already channels-last
-    else if ((rc = hp_nchw_to_nhwc(gc, hd, tc.input, base + L.off_xt, stream))) return rc;
+    if (g.in_cl) xt = (const char *)t.input + (size_t)b0 * g.S_i * g.C * 2;   // already channels-last (16-bit tensors only)
+    else if ((rc = hp_nchw_to_nhwc(gc, hd, tc.input, base + L.off_xt, io32, stream))) return rc;
+    if (io32) {
+      // the chunk's grad_output as the kernels read it; grad_bias sums that copy chunk by chunk in fp32 (one chunk: the
+      // very sum of the bf16 call)
+      if ((rc = hp_f32_to_bf16((const float *)tc.grad_output, base + L.off_go16, (int64_t)bc * g.O * g.S_o, stream))) return rc;
+      tc.grad_output = base + L.off_go16;
+      if (g.with_bias && !skip.weight) {
+        Geom gb = gc;
+        if (!first) gb.acc_w = 1;
+        if ((rc = hp_grad_bias(gb, dtype, tc.grad_output, t.grad_bias, true, stream))) return rc;
+      }
+    }
     if ((rc = hp_csr_zero(gc, cnt, stream))) return rc;
     const bool bwd3 = c.bwd == HpChunk::BWD3, bwd2 = c.bwd == HpChunk::BWD2;   // (the plan checked this chunk's slots)
     profile_mark(1, true, stream, bwd3 ? "hp_bwd3_kernel" : (bwd2 ? "hp_bwd2_kernel" : "hp_bwd_kernel"));

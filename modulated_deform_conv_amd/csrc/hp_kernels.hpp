@@ -8,11 +8,14 @@ namespace mdconv {
 HpDims hp_dims(const Geom &g);
 
 // hp_prep.hip
-int hp_nchw_to_nhwc(const Geom &g, const HpDims &hd, const void *x, void *xt, hipStream_t stream);
-int hp_pack_fwd_weights(const Geom &g, const HpDims &hd, int dtype, const void *w, void *wpf,
+// `f32src` (fp32 tensors on the bf16 kernels, Tensors::io32): `x` / `w` are fp32 and are rounded to bf16 inside the pass
+int hp_nchw_to_nhwc(const Geom &g, const HpDims &hd, const void *x, void *xt, bool f32src, hipStream_t stream);
+int hp_pack_fwd_weights(const Geom &g, const HpDims &hd, int dtype, const void *w, bool f32src, void *wpf,
                         int2 *ctab, hipStream_t stream);
-int hp_pack_bwd_weights(const Geom &g, const HpDims &hd, int dtype, const void *w, void *wpb,
+int hp_pack_bwd_weights(const Geom &g, const HpDims &hd, int dtype, const void *w, bool f32src, void *wpb,
                         int4 *btab, hipStream_t stream);
+// the bf16 copy of an fp32 grad_output (Tensors::io32), `n` elements
+int hp_f32_to_bf16(const float *src, void *dst, int64_t n, hipStream_t stream);
 // gw32 != nullptr (calls cut into batch chunks): running fp32 sum; grad_weight is written by the last chunk
 // `ranges` = pixel ranges per tap in `part` (hd.ranges_w after hp_gemm2, hd.ranges after hp_bwd)
 // `wgrad32`: grad_weight / grad_bias are fp32 buffers and receive the fp32 sums (Tensors::wgrad32)

@@ -17,7 +17,9 @@ struct HpChunk {
 };
 struct HpFwdLayout { size_t off_xt, off_w, off_tab, total; };
 struct HpBwdLayout {
-  size_t off_xt, off_w, off_tab, off_gcol, off_col, off_part, off_gw32, off_cnt, off_rowptr, off_entries, off_sums, off_sort, total;
+  size_t off_xt, off_w, off_tab, off_gcol, off_col, off_part, off_gw32, off_cnt, off_rowptr, off_entries, off_sums, off_sort;
+  size_t off_go16;   // HpPlan::io32: the bf16 copy of one chunk's fp32 grad_output (behind the slots of the bf16 call)
+  size_t total;
 };
 
 struct HpPlan {
@@ -33,9 +35,14 @@ struct HpPlan {
   // split-K reduce and grad_bias; the list build, the sort and the gather -- and the slots only those stages use take no
   // bytes; hp_bwd3 chunks of a call without weight gradients run the kernel's variant without column rows.
   Skip skip;
+  // fp32 tensors on the bf16 kernels (MDCONV_FLAG_MATH_BF16): the plan of the bf16 call with fp32 offsets / masks and fp32
+  // weight gradients, whose layout passes read fp32 input and weights, whose forward and grad_input gather store fp32, and
+  // whose backward converts each chunk's grad_output into off_go16 -- the one slot the mode adds
+  bool io32;
 };
-// false: the family does not take the call.  `skip` never changes the answer, the geometry, the chunks or their kernels.
-bool hp_plan(const Geom &g, int dtype, bool backward, HpPlan *p, Skip skip = Skip());
+// false: the family does not take the call.  `skip` never changes the answer, the geometry, the chunks or their kernels;
+// nor does `io32` (with dtype MDCONV_BF16: the call's tensors are fp32, Tensors::io32).
+bool hp_plan(const Geom &g, int dtype, bool backward, HpPlan *p, Skip skip = Skip(), bool io32 = false);
 int hp_forward(int dtype, const HpPlan &p, const Tensors &t, void *ws, hipStream_t stream);
 int hp_backward(int dtype, const HpPlan &p, const Tensors &t, void *ws, hipStream_t stream);
 

@@ -12,9 +12,13 @@ int grid_for(int64_t total, int cap = 8192) {
 }
 
 // xt[b][q][Cp] = x[b][caller_channel(c)][q] (0 for padding channels): 64 x 64 tiles through LDS, 16-byte stores.
-// Element type agnostic (moves 16-bit words).
+// Element type agnostic (moves 16-bit words) -- or, X = float (fp32 tensors on the bf16 kernels, Tensors::io32), rounds the fp32
+// source to bf16 on its way into the tile: the three copies below ARE the input's conversion, there is no pass in front.
+__device__ __forceinline__ unsigned short hp_word(unsigned short v) { return v; }
+__device__ __forceinline__ unsigned short hp_word(float v) { return bf16_operand_bits(v); }
+template <typename X>
 __global__ __launch_bounds__(256) void hp_nchw_to_nhwc_kernel(Geom g, int Cp, int S,
-                                                              const unsigned short *__restrict__ x,
+                                                              const X *__restrict__ x,
                                                               unsigned short *__restrict__ xt) {
   __shared__ unsigned short t[64][66];
   const int b = blockIdx.z, c0 = blockIdx.y * 64, q0 = blockIdx.x * 64;
@@ -22,7 +26,7 @@ __global__ __launch_bounds__(256) void hp_nchw_to_nhwc_kernel(Geom g, int Cp, in
 #pragma unroll 4
   for (int r = ty; r < 64; r += 4) {
     const int c = caller_channel(g, c0 + r), q = q0 + tx;
-    t[r][tx] = (c >= 0 && q < S) ? x[((size_t)b * caller_channels(g) + c) * S + q] : (unsigned short)0;
+    t[r][tx] = (c >= 0 && q < S) ? hp_word(x[((size_t)b * caller_channels(g) + c) * S + q]) : (unsigned short)0;
   }
   __syncthreads();
   for (int item = threadIdx.x; item < 64 * 8; item += 256) {
@@ -42,8 +46,10 @@ __global__ __launch_bounds__(256) void hp_nchw_to_nhwc_kernel(Geom g, int Cp, in
 // The same copy with 8-byte loads along q (4 pixels of one channel per lane: 4 load instructions per thread instead
 // of 16 two-byte ones) for S a multiple of 4 and an 8-byte aligned source; LDS tile and the 16-byte stores as above.
 // Picked for rows of 512 bytes (cfg3, C = 256), where the transposing-read variant below loses.
+// (X = float: the quad is one 16-byte load of a 16-byte aligned source.)
+template <typename X>
 __global__ __launch_bounds__(256) void hp_nchw_to_nhwc_q4_kernel(Geom g, int Cp, int S,
-                                                                 const unsigned short *__restrict__ x,
+                                                                 const X *__restrict__ x,
                                                                  unsigned short *__restrict__ xt) {
   __shared__ __attribute__((aligned(8))) unsigned short t[64][68];   // pitch 136 B: 8-byte aligned rows
   const int b = blockIdx.z, c0 = blockIdx.y * 64, q0 = blockIdx.x * 64;
@@ -52,7 +58,15 @@ __global__ __launch_bounds__(256) void hp_nchw_to_nhwc_q4_kernel(Geom g, int Cp,
   for (int pass = 0; pass < 4; ++pass) {
     const int r = r0 + 16 * pass, c = caller_channel(g, c0 + r), q = q0 + u * 4;
     uint2 v = make_uint2(0u, 0u);
-    if (c >= 0 && q < S) v = *reinterpret_cast<const uint2 *>(x + ((size_t)b * caller_channels(g) + c) * S + q);   // S % 4 == 0: whole quad inside
+    if (c >= 0 && q < S) {   // S % 4 == 0: whole quad inside
+      const X *src = x + ((size_t)b * caller_channels(g) + c) * S + q;
+      if constexpr (sizeof(X) == 4) {
+        const float4 f = *reinterpret_cast<const float4 *>(src);
+        v = make_uint2(BF16::pack(f.x, f.y), BF16::pack(f.z, f.w));
+      } else {
+        v = *reinterpret_cast<const uint2 *>(src);
+      }
+    }
     *reinterpret_cast<uint2 *>(&t[r][u * 4]) = v;
   }
   __syncthreads();
@@ -77,8 +91,10 @@ __global__ __launch_bounds__(256) void hp_nchw_to_nhwc_q4_kernel(Geom g, int Cp,
 // land one pixel row apart, which pays for rows of 256 bytes (cfg5, C = 128: 95 -> 61 us) and not for rows of 512
 // (cfg3, C = 256: 36 -> 41 us) -- the launcher picks by row length.  (Vector loads with the two-byte LDS reads of
 // the kernel above: 16-byte aligned rows put a pixel's 8 channel octets in one bank, 49 / 82 us.)
+// (X = float: the 8 pixels are two 16-byte loads.)
+template <typename X>
 __global__ __launch_bounds__(256) void hp_nchw_to_nhwc_vec_kernel(Geom g, int Cp, int S,
-                                                                  const unsigned short *__restrict__ x,
+                                                                  const X *__restrict__ x,
                                                                   unsigned short *__restrict__ xt) {
   constexpr int P = 80;
   __shared__ __attribute__((aligned(16))) unsigned short t[64 * P];
@@ -89,7 +105,16 @@ __global__ __launch_bounds__(256) void hp_nchw_to_nhwc_vec_kernel(Geom g, int Cp
     const int row = (tid >> 3) + 32 * i, u = tid & 7;
     const int c = caller_channel(g, c0 + row), q = q0 + u * 8;
     U4 v = {0, 0, 0, 0};
-    if (c >= 0 && q < S) v = *reinterpret_cast<const U4 *>(x + ((size_t)b * caller_channels(g) + c) * S + q);
+    if (c >= 0 && q < S) {
+      const X *src = x + ((size_t)b * caller_channels(g) + c) * S + q;
+      if constexpr (sizeof(X) == 4) {
+        const float4 f0 = reinterpret_cast<const float4 *>(src)[0], f1 = reinterpret_cast<const float4 *>(src)[1];
+        v.x = BF16::pack(f0.x, f0.y); v.y = BF16::pack(f0.z, f0.w);
+        v.z = BF16::pack(f1.x, f1.y); v.w = BF16::pack(f1.z, f1.w);
+      } else {
+        v = *reinterpret_cast<const U4 *>(src);
+      }
+    }
     *reinterpret_cast<U4 *>(t + row * P + u * 8) = v;
   }
   __syncthreads();
@@ -118,16 +143,18 @@ __device__ __forceinline__ int64_t hp_weight_index(const Geom &g, int o, int c, 
   }
   return (c < g.C && o / g.Og == c / g.Cg) ? ((int64_t)o * g.Cg + (c % g.Cg)) * g.K + tap : -1;
 }
-__device__ __forceinline__ unsigned short hp_weight_or_zero(const Geom &g, const unsigned short *__restrict__ w, int o, int c,
-                                                           int tap) {
+// (X = float: fp32 weights, rounded to the bf16 operand here)
+template <typename X>
+__device__ __forceinline__ unsigned short hp_weight_or_zero(const Geom &g, const X *__restrict__ w, int o, int c, int tap) {
   const int64_t e = hp_weight_index(g, o, c, tap);
-  return e < 0 ? (unsigned short)0 : w[e];
+  return e < 0 ? (unsigned short)0 : hp_word(w[e]);
 }
 __device__ void hp_ctab_fill(const Geom &g, const HpDims &hd, int2 *__restrict__ ctab);
 __device__ __forceinline__ int4 hp_btab_entry(const Geom &g, int cblk);
 // (block 0 also writes the chunk table the forward kernel reads: one launch less than a table kernel of its own)
+template <typename X>
 __global__ __launch_bounds__(256) void hp_pack_fwd_kernel(Geom g, HpDims hd,
-                                                          const unsigned short *__restrict__ w,
+                                                          const X *__restrict__ w,
                                                           U4 *__restrict__ wpf, int2 *__restrict__ ctab) {
   if (blockIdx.x == 0) hp_ctab_fill(g, hd, ctab);
   const int nchunks = hd.Cp / 16;
@@ -187,8 +214,9 @@ __host__ __device__ inline int hp_sigma(int i) { return 16 * ((i >> 2) & 1) + 4 
 // backward A operand (W^T): wpb[tap][cblk][ks][lane][8] = W[o = o_base(cblk) + ks*16 + 8*(lane>>5) + j]
 //                                                           [c = cblk*32 + sigma(lane&31)][tap]
 // (the per-block output base is computed in place; block 0 writes the table the later kernels read)
+template <typename X>
 __global__ __launch_bounds__(256) void hp_pack_bwd_kernel(Geom g, HpDims hd, int4 *__restrict__ btab,
-                                                          const unsigned short *__restrict__ w,
+                                                          const X *__restrict__ w,
                                                           U4 *__restrict__ wpb) {
   if (blockIdx.x == 0)
     for (int cb = threadIdx.x; cb < hd.cblks; cb += blockDim.x) btab[cb] = hp_btab_entry(g, cb);
@@ -222,12 +250,7 @@ __device__ __forceinline__ int4 hp_btab_entry(const Geom &g, int cblk) {
   return make_int4(base, (o_hi - base + 31) / 32, 0, 0);
 }
 
-// fp32 grad_weight / grad_bias (MDCONV_WGRAD_F32): the output type of the two kernels below that keeps the fp32 sum
-struct OutF32 {
-  using Raw = float;
-  static __device__ __forceinline__ float ldf(const Raw *p) { return *p; }
-  static __device__ __forceinline__ void stf(Raw *p, float v) { *p = v; }
-};
+// fp32 grad_weight / grad_bias (MDCONV_WGRAD_F32): the two kernels below with the output policy that keeps the fp32 sum (F32IO)
 
 // grad_weight[o][c][tap] (+)= sum over the pixel ranges of part[tap][range][cblk][ob][lane][16]
 // (the 32x32 fp32 accumulator blocks of the fused backward kernel, D[i = o][j = c]); OUT = the type it is stored in
@@ -315,35 +338,74 @@ __global__ __launch_bounds__(kBiasThreads) void hp_grad_bias_kernel(Geom g, cons
   if (tid == 0) OUT::stf(gb + o, g.acc_w ? OUT::ldf(gb + o) + red[0] : red[0]);
 }
 
-}  // namespace
-
-int hp_nchw_to_nhwc(const Geom &g, const HpDims &hd, const void *x, void *xt, hipStream_t stream) {
-  const dim3 grid((g.S_i + 63) / 64, (hd.Cp + 63) / 64, g.B);
-  if (hd.Cp <= 128 && g.S_i % 8 == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0)
-    hipLaunchKernelGGL(hp_nchw_to_nhwc_vec_kernel, grid, dim3(256), 0, stream, g, hd.Cp, g.S_i,
-                       (const unsigned short *)x, (unsigned short *)xt);
-  else if (g.S_i % 4 == 0 && (reinterpret_cast<uintptr_t>(x) & 7) == 0)
-    hipLaunchKernelGGL(hp_nchw_to_nhwc_q4_kernel, grid, dim3(256), 0, stream, g, hd.Cp, g.S_i,
-                       (const unsigned short *)x, (unsigned short *)xt);
-  else
-    hipLaunchKernelGGL(hp_nchw_to_nhwc_kernel, grid, dim3(256), 0, stream, g, hd.Cp, g.S_i,
-                       (const unsigned short *)x, (unsigned short *)xt);
-  return check_launch("hp_nchw_to_nhwc");
+// dst[i] = bf16(src[i]): the grad_output of an fp32 call on the bf16 kernels (Tensors::io32), which the backward kernels and
+// GEMM-2 read as 16-bit NCHW.  VEC (a 16-byte aligned source): 16-byte loads, 8-byte stores, the n % 4 last elements one by one.
+template <bool VEC>
+__global__ __launch_bounds__(256) void hp_f32_to_bf16_kernel(const float *__restrict__ src, unsigned short *__restrict__ dst,
+                                                             int64_t n) {
+  const int64_t nq = VEC ? n >> 2 : 0;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < nq; i += (int64_t)gridDim.x * 256) {
+    const float4 f = reinterpret_cast<const float4 *>(src)[i];
+    reinterpret_cast<uint2 *>(dst)[i] = make_uint2(BF16::pack(f.x, f.y), BF16::pack(f.z, f.w));
+  }
+  for (int64_t i = nq * 4 + (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256)
+    dst[i] = bf16_operand_bits(src[i]);
 }
 
-int hp_pack_fwd_weights(const Geom &g, const HpDims &hd, int dtype, const void *w, void *wpf,
+}  // namespace
+
+int hp_f32_to_bf16(const float *src, void *dst, int64_t n, hipStream_t stream) {
+  if (n <= 0) return MDCONV_OK;
+  if ((reinterpret_cast<uintptr_t>(src) & 15) == 0 && (reinterpret_cast<uintptr_t>(dst) & 7) == 0)
+    hipLaunchKernelGGL(hp_f32_to_bf16_kernel<true>, dim3(grid_for((n + 3) / 4, 16384)), dim3(256), 0, stream, src,
+                       (unsigned short *)dst, n);
+  else
+    hipLaunchKernelGGL(hp_f32_to_bf16_kernel<false>, dim3(grid_for(n, 16384)), dim3(256), 0, stream, src,
+                       (unsigned short *)dst, n);
+  return check_launch("hp_f32_to_bf16");
+}
+
+// X = the source's element: 16-bit words, or fp32 (the vector kernels then need a 16-byte aligned source)
+template <typename X>
+static int nchw_to_nhwc(const Geom &g, const HpDims &hd, const void *x, void *xt, hipStream_t stream) {
+  const dim3 grid((g.S_i + 63) / 64, (hd.Cp + 63) / 64, g.B);
+  const uintptr_t a = reinterpret_cast<uintptr_t>(x);
+  if (hd.Cp <= 128 && g.S_i % 8 == 0 && (a & 15) == 0)
+    hipLaunchKernelGGL(hp_nchw_to_nhwc_vec_kernel<X>, grid, dim3(256), 0, stream, g, hd.Cp, g.S_i,
+                       (const X *)x, (unsigned short *)xt);
+  else if (g.S_i % 4 == 0 && (a & (sizeof(X) == 4 ? 15 : 7)) == 0)
+    hipLaunchKernelGGL(hp_nchw_to_nhwc_q4_kernel<X>, grid, dim3(256), 0, stream, g, hd.Cp, g.S_i,
+                       (const X *)x, (unsigned short *)xt);
+  else
+    hipLaunchKernelGGL(hp_nchw_to_nhwc_kernel<X>, grid, dim3(256), 0, stream, g, hd.Cp, g.S_i,
+                       (const X *)x, (unsigned short *)xt);
+  return check_launch("hp_nchw_to_nhwc");
+}
+int hp_nchw_to_nhwc(const Geom &g, const HpDims &hd, const void *x, void *xt, bool f32src, hipStream_t stream) {
+  return f32src ? nchw_to_nhwc<float>(g, hd, x, xt, stream) : nchw_to_nhwc<unsigned short>(g, hd, x, xt, stream);
+}
+
+int hp_pack_fwd_weights(const Geom &g, const HpDims &hd, int dtype, const void *w, bool f32src, void *wpf,
                         int2 *ctab, hipStream_t stream) {
   const int64_t total = (int64_t)g.K * (hd.Cp / 16) * hd.oblks * 64;
-  hipLaunchKernelGGL(hp_pack_fwd_kernel, dim3(grid_for(total)), dim3(256), 0, stream, g, hd,
-                     (const unsigned short *)w, (U4 *)wpf, ctab);
+  if (f32src)
+    hipLaunchKernelGGL(hp_pack_fwd_kernel<float>, dim3(grid_for(total)), dim3(256), 0, stream, g, hd,
+                       (const float *)w, (U4 *)wpf, ctab);
+  else
+    hipLaunchKernelGGL(hp_pack_fwd_kernel<unsigned short>, dim3(grid_for(total)), dim3(256), 0, stream, g, hd,
+                       (const unsigned short *)w, (U4 *)wpf, ctab);
   return check_launch("hp_pack_fwd");
 }
 
-int hp_pack_bwd_weights(const Geom &g, const HpDims &hd, int dtype, const void *w, void *wpb,
+int hp_pack_bwd_weights(const Geom &g, const HpDims &hd, int dtype, const void *w, bool f32src, void *wpb,
                         int4 *btab, hipStream_t stream) {
   const int64_t total = (int64_t)g.K * hd.cblks * hd.nks * 64;
-  hipLaunchKernelGGL(hp_pack_bwd_kernel, dim3(grid_for(total)), dim3(256), 0, stream, g, hd, btab,
-                     (const unsigned short *)w, (U4 *)wpb);
+  if (f32src)
+    hipLaunchKernelGGL(hp_pack_bwd_kernel<float>, dim3(grid_for(total)), dim3(256), 0, stream, g, hd, btab,
+                       (const float *)w, (U4 *)wpb);
+  else
+    hipLaunchKernelGGL(hp_pack_bwd_kernel<unsigned short>, dim3(grid_for(total)), dim3(256), 0, stream, g, hd, btab,
+                       (const unsigned short *)w, (U4 *)wpb);
   return check_launch("hp_pack_bwd");
 }
 
@@ -352,7 +414,7 @@ int hp_reduce_grad_weight(const Geom &g, const HpDims &hd, int ranges, int dtype
                           hipStream_t stream) {
   const int64_t total = (int64_t)g.K * hd.cblks * hd.MB2 * 1024;
   if (wgrad32)   // (the kernel reads fp32 partials whatever the tensors' type: one instance)
-    hipLaunchKernelGGL((hp_reduce_gw_kernel<F16, OutF32>), dim3(grid_for(total)), dim3(256), 0, stream, g, hd,
+    hipLaunchKernelGGL((hp_reduce_gw_kernel<F16, F32IO>), dim3(grid_for(total)), dim3(256), 0, stream, g, hd,
                        ranges, btab, part, (float *)grad_weight, gw32, first ? 1 : 0, last ? 1 : 0);
   else if (dtype == MDCONV_F16)
     hipLaunchKernelGGL((hp_reduce_gw_kernel<F16>), dim3(grid_for(total)), dim3(256), 0, stream, g, hd,
@@ -366,10 +428,10 @@ int hp_reduce_grad_weight(const Geom &g, const HpDims &hd, int ranges, int dtype
 int hp_grad_bias(const Geom &g, int dtype, const void *grad_output, void *grad_bias, bool wgrad32,
                  hipStream_t stream) {
   if (wgrad32 && dtype == MDCONV_F16)
-    hipLaunchKernelGGL((hp_grad_bias_kernel<F16, OutF32>), dim3(g.O), dim3(kBiasThreads), 0, stream, g,
+    hipLaunchKernelGGL((hp_grad_bias_kernel<F16, F32IO>), dim3(g.O), dim3(kBiasThreads), 0, stream, g,
                        (const _Float16 *)grad_output, (float *)grad_bias);
   else if (wgrad32)
-    hipLaunchKernelGGL((hp_grad_bias_kernel<BF16, OutF32>), dim3(g.O), dim3(kBiasThreads), 0, stream, g,
+    hipLaunchKernelGGL((hp_grad_bias_kernel<BF16, F32IO>), dim3(g.O), dim3(kBiasThreads), 0, stream, g,
                        (const __bf16 *)grad_output, (float *)grad_bias);
   else if (dtype == MDCONV_F16)
     hipLaunchKernelGGL((hp_grad_bias_kernel<F16>), dim3(g.O), dim3(kBiasThreads), 0, stream, g,

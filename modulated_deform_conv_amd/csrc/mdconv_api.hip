@@ -69,9 +69,10 @@ static int current_path() {
 static int desc_ndim(const mdconv_desc *d) { return d->ndim & ~MDCONV_DESC_V2; }
 
 // Call modes of one call: from the descriptor (ABI v2) or from the v1 setters of the calling thread / process.
-struct Modes { int accumulate, input_layout, path, deterministic; Skip skip; };
+// math_bf16: MDCONV_FLAG_MATH_BF16 -- the fp32 call may run on the bf16 kernels (plan_call decides whether it does)
+struct Modes { int accumulate, input_layout, path, deterministic, math_bf16; Skip skip; };
 static int call_modes(const mdconv_desc *d, Modes *m) {
-  m->deterministic = 0;   // v1 descriptors end before the flag word: they never request a flag
+  m->deterministic = m->math_bf16 = 0;   // v1 descriptors end before the flag word: they never request a flag
   m->skip = Skip();
   if (!(d->ndim & MDCONV_DESC_V2)) {
     m->accumulate = g_accumulate;
@@ -91,12 +92,22 @@ static int call_modes(const mdconv_desc *d, Modes *m) {
       set_error("mdconv_desc.reserved must be 0");
       return MDCONV_EINVAL;
     }
-  const int known = MDCONV_FLAG_DETERMINISTIC | MDCONV_FLAG_NO_GRAD_INPUT | MDCONV_FLAG_NO_GRAD_WEIGHT;
+  const int known = MDCONV_FLAG_DETERMINISTIC | MDCONV_FLAG_NO_GRAD_INPUT | MDCONV_FLAG_NO_GRAD_WEIGHT | MDCONV_FLAG_MATH_BF16;
   if (d->reserved[4] & ~known) {
     set_error("unknown bits 0x%x in the flags word of the descriptor (mdconv_desc.reserved[4]); the flags are "
-              "MDCONV_FLAG_DETERMINISTIC (1), MDCONV_FLAG_NO_GRAD_INPUT (4) and MDCONV_FLAG_NO_GRAD_WEIGHT (8)",
+              "MDCONV_FLAG_DETERMINISTIC (1), MDCONV_FLAG_NO_GRAD_INPUT (4), MDCONV_FLAG_NO_GRAD_WEIGHT (8) and "
+              "MDCONV_FLAG_MATH_BF16 (32)",
               (unsigned)(d->reserved[4] & ~known));
     return MDCONV_EINVAL;
+  }
+  if (d->reserved[4] & MDCONV_FLAG_MATH_BF16) {
+    const int dt = d->dtype & ~(MDCONV_SAMPLING_F32 | MDCONV_WGRAD_F32);   // (fill_geom has validated the dtype word)
+    if (dt != MDCONV_F32) {
+      set_error("MDCONV_FLAG_MATH_BF16 needs fp32 tensors, dtype is %s",
+                dt == MDCONV_F64 ? "MDCONV_F64" : (dt == MDCONV_F16 ? "MDCONV_F16" : "MDCONV_BF16"));
+      return MDCONV_EINVAL;
+    }
+    m->math_bf16 = 1;
   }
   m->deterministic = (d->reserved[4] & MDCONV_FLAG_DETERMINISTIC) ? 1 : 0;
   m->skip.input = (d->reserved[4] & MDCONV_FLAG_NO_GRAD_INPUT) != 0;
@@ -242,6 +253,7 @@ static int wgrad_f32(const mdconv_desc *d, bool backward) { return backward && (
 // ---------------------------------------------------------------------------------------------
 enum Route {
   ROUTE_HP,              // native 16-bit kernels
+  ROUTE_HP_F32,          // ... bf16 instances of them for fp32 tensors (MDCONV_FLAG_MATH_BF16): fp32 in and out, `hp` made for it
   ROUTE_F32,             // fp32 matrix kernels (16-bit tensors: chunk-wise fp32 copies inside the family)
   ROUTE_F32_SAMP32,      // ... through the fp32 copies of a call with fp32 offsets / masks (`s32`)
   ROUTE_DIRECT,          // shape-generic kernels
@@ -255,7 +267,7 @@ struct CallPlan {
   Refusal refused;
   size_t bytes;      // workspace the route needs
   size_t reported;   // what mdconv_workspace_bytes answers: `bytes`, but see the few-tile forwards in plan_call
-  HpPlan hp;         // ROUTE_HP
+  HpPlan hp;         // ROUTE_HP, ROUTE_HP_F32
   MfmaPlan f32;      // ROUTE_F32
   S32Plan s32;       // ROUTE_*_SAMP32
   D16Plan d16;       // ROUTE_DIRECT_16
@@ -270,11 +282,26 @@ static bool route_is_direct(Route r) { return r == ROUTE_DIRECT || r == ROUTE_DI
 // `skip` (a backward without grad_input / without the weight gradients) never changes the route either: the plans drop the
 // stages and workspace slots of the skipped gradients, and the shape-generic data kernel scatters an unwanted grad_input
 // into scratch (CallPlan::scratch_gi, appended to the route's workspace).
-static void plan_call(const Geom &g, int dt, int s32, int wg32, int path, bool backward, CallPlan *cp, Skip skip = Skip()) {
+// `mb16` (MDCONV_FLAG_MATH_BF16, fp32 tensors) is a permission: the call takes ROUTE_HP_F32 where its bf16 form is a native
+// 16-bit call -- hp_plan takes it and, a forward, prefers it -- and is planned as without the flag everywhere else
+// (MDCONV_PATH_DIRECT, an fp32 channels-last input, few-tile forwards, shapes outside hp_plan).
+// One size rule on top, from measurement (profiles/math_bf16.md): layers of fewer than 16 input or 16 output channels are declined.
+// The bf16 kernels pad channels to blocks of 32, and with the rule off such layers did not gain: DCN2d 4 -> 4 at 8 x 8 ran 0.121 ms
+// against 0.089 ms exact, MDCN2d 8 -> 8 at 56 x 56, B = 8 0.224 against 0.229 (inside the +-3 % spread), 4 -> 4 there 0.222 against 0.238.
+// Narrow CONV GROUPS of a wide layer are taken (256 -> 256 in 32 groups of 8, 56 x 56, B = 8: 0.33 against 0.97 ms).
+static void plan_call(const Geom &g, int dt, int s32, int wg32, int path, bool backward, CallPlan *cp, Skip skip = Skip(),
+                      int mb16 = 0) {
   const bool half = dt == MDCONV_F16 || dt == MDCONV_BF16;
   if (!backward) skip = Skip();
   cp->skip = skip;
   cp->scratch_gi = 0;
+  if (mb16 && dt == MDCONV_F32 && path != MDCONV_PATH_DIRECT && !g.in_cl && g.C >= 16 && g.O >= 16 &&
+      hp_plan(g, MDCONV_BF16, backward, &cp->hp, skip, true) && cp->hp.forward_preferred) {
+    cp->route = ROUTE_HP_F32;
+    cp->refused = REFUSE_NONE;
+    cp->bytes = cp->reported = cp->hp.total;
+    return;
+  }
   const bool hp = path != MDCONV_PATH_DIRECT && hp_plan(g, dt, backward, &cp->hp, skip);
   cp->refused = g.in_cl && !(hp && g.C % 32 == 0) ? REFUSE_CHANNELS_LAST : REFUSE_NONE;
   const size_t hp_bytes = hp ? cp->hp.total : 0;
@@ -391,9 +418,14 @@ static int run_forward(const mdconv_desc *d, int nd, int modulated, Tensors t, v
   t.samp32 = s32;
   g.in_cl = md.input_layout == MDCONV_LAYOUT_CHANNELS_LAST ? 1 : 0;
   CallPlan cp;
-  plan_call(g, dt, s32, 0, path, false, &cp);
+  plan_call(g, dt, s32, 0, path, false, &cp, Skip(), md.math_bf16);
   if (cp.refused) return refuse(cp, g, dt, path);
   switch (cp.route) {
+    case ROUTE_HP_F32:   // the bf16 kernels on the caller's fp32 tensors
+      if ((rc = check_ws(ws, ws_bytes, cp.bytes))) return rc;
+      g_last_path = MDCONV_PATH_MFMA;
+      g_last_kernels = MDCONV_KERNELS_HP;
+      return hp_forward(MDCONV_BF16, cp.hp, t, ws, s);
     case ROUTE_HP:
       if ((rc = check_ws(ws, ws_bytes, cp.bytes))) return rc;
       g_last_path = MDCONV_PATH_MFMA;
@@ -451,7 +483,7 @@ static int run_backward(const mdconv_desc *d, int nd, int modulated, Tensors t, 
   g.in_cl = md.input_layout == MDCONV_LAYOUT_CHANNELS_LAST ? 1 : 0;
   g.det = md.deterministic;
   CallPlan cp;
-  plan_call(g, dt, s32, t.wgrad32, path, true, &cp, skip);
+  plan_call(g, dt, s32, t.wgrad32, path, true, &cp, skip, md.math_bf16);
   if (cp.refused) return refuse(cp, g, dt, path);
   // the workspace check; without weight gradients there is nothing to wait for, so the weights-ready event goes in front
   // of the call's first kernel
@@ -459,11 +491,13 @@ static int run_backward(const mdconv_desc *d, int nd, int modulated, Tensors t, 
     const int r = check_ws(ws, ws_bytes, cp.bytes);
     return r || !skip.weight ? r : record_weight_ready(s);
   };
-  if (cp.route == ROUTE_HP) {
+  if (cp.route == ROUTE_HP || cp.route == ROUTE_HP_F32) {
     if ((rc = ready())) return rc;
     g_last_path = MDCONV_PATH_MFMA;
     g_last_kernels = MDCONV_KERNELS_HP;
-    return hp_backward(dt, cp.hp, t, ws, s);
+    if (cp.route == ROUTE_HP) return hp_backward(dt, cp.hp, t, ws, s);
+    // the bf16 kernels on the caller's fp32 tensors (HpPlan::io32)
+    return hp_backward(MDCONV_BF16, cp.hp, t, ws, s);
   }
   if (cp.route == ROUTE_F32 || cp.route == ROUTE_F32_SAMP32) {
     g_last_path = MDCONV_PATH_MFMA;
@@ -577,8 +611,19 @@ size_t mdconv_workspace_bytes(const mdconv_desc *d, int backward) {
   g.in_cl = md.input_layout == MDCONV_LAYOUT_CHANNELS_LAST ? 1 : 0;   // (the plan of a channels-last call, where the caller says so)
   g.det = backward ? md.deterministic : 0;   // the list sort's scratch (backward on the matrix-core kernels only)
   CallPlan cp;
-  plan_call(g, base_dtype(d), sampling_f32(d), wgrad_f32(d, backward != 0), md.path, backward != 0, &cp, md.skip);
+  plan_call(g, base_dtype(d), sampling_f32(d), wgrad_f32(d, backward != 0), md.path, backward != 0, &cp, md.skip, md.math_bf16);
   return cp.reported;
+}
+
+int mdconv_math_bf16_used(const mdconv_desc *d, int backward) {
+  Geom g;
+  Modes md;
+  if (fill_geom(d, &g) || call_modes(d, &md) || !md.math_bf16) return 0;
+  g.in_cl = md.input_layout == MDCONV_LAYOUT_CHANNELS_LAST ? 1 : 0;
+  g.det = backward ? md.deterministic : 0;
+  CallPlan cp;
+  plan_call(g, base_dtype(d), 0, 0, md.path, backward != 0, &cp, md.skip, 1);
+  return cp.route == ROUTE_HP_F32;
 }
 
 int mdconv_set_input_layout(int layout) {
@@ -607,7 +652,7 @@ int mdconv_deterministic_supported(const mdconv_desc *d, int backward) {
   g.in_cl = md.input_layout == MDCONV_LAYOUT_CHANNELS_LAST ? 1 : 0;
   g.det = 1;
   CallPlan cp;
-  plan_call(g, base_dtype(d), sampling_f32(d), wgrad_f32(d, true), md.path, true, &cp);
+  plan_call(g, base_dtype(d), sampling_f32(d), wgrad_f32(d, true), md.path, true, &cp, Skip(), md.math_bf16);
   if (!route_is_direct(cp.route)) return 1;
   set_det_refusal(g, base_dtype(d), md.path);   // the reason, for mdconv_last_error()
   return 0;

@@ -430,6 +430,9 @@ struct Tensors {
   int samp32;
   // 1 = grad_weight / grad_bias are fp32 while the other tensors are 16-bit (MDCONV_WGRAD_F32): the fp32 sums, not rounded
   int wgrad32;
+  // 1 = an fp32 call on the bf16 kernels (MDCONV_FLAG_MATH_BF16; implies samp32 and wgrad32): input, weight, bias,
+  // grad_output, output and grad_input are fp32 buffers, the kernels' `dtype` is MDCONV_BF16
+  int io32;
 };
 // bytes of one offset / mask element of a call
 inline size_t samp_bytes(int dtype, const Tensors &t) {

@@ -89,6 +89,9 @@ def _make_function(nd, modulated, name):
         if ctx.wgrad32:
             weight = weight.to(input.dtype)
             bias = bias.to(input.dtype)
+        # fp32 tensors, bf16 matrix math (_capi.fp32_math): the mode of this forward is the mode of its backward, whatever
+        # thread runs that and whatever the global says by then
+        ctx.fp32_math = _capi.fp32_math_mode()
         if needs_grad:
             saved = (input, offset, mask, weight, bias) if modulated else (input, offset, weight, bias)
             ctx.save_for_backward(*saved)
@@ -121,9 +124,10 @@ def _make_function(nd, modulated, name):
         skip_input = not need[0]
         skip_weight = not (need[iw] or (ctx.with_bias and need[iw + 1]))
         skip = _capi.skip_grads(input=skip_input, weight=skip_weight)
+        math = _capi.fp32_math(ctx.fp32_math)
         if returns_tensors:
             # (autograd runs this on its own thread: the modes recorded in forward are entered here)
-            with _capi.weight_grads_f32(ctx.wgrad32), skip:
+            with _capi.weight_grads_f32(ctx.wgrad32), skip, math:
                 grad_input, grad_offset, grad_mask, grad_weight, grad_bias = bwd(
                     input, weight, bias, offset, mask, grad_output, *geo)
         else:
@@ -134,7 +138,7 @@ def _make_function(nd, modulated, name):
             # one flat buffer: one in-place all-reduce (distributed.py); fp32 for fp32 weight gradients -- the entry points
             # take the mode from the buffers' dtype
             grad_weight, grad_bias = (None, None) if skip_weight else fused_grad_buffers(weight, bias, wdt)
-            with _capi.overwrite_grads(), _capi.weight_grads_f32(ctx.wgrad32), skip:
+            with _capi.overwrite_grads(), _capi.weight_grads_f32(ctx.wgrad32), skip, math:
                 if modulated:
                     grad_mask = torch.empty_like(mask)
                     bwd(input, weight, bias, offset, mask, grad_input, grad_weight, grad_bias,

@@ -231,6 +231,9 @@ def _setup_context(ctx, inputs, output):
      in_step) = inputs
     ctx.save_for_backward(input, offset, mask, weight, bias)
     ctx.conf = (list(stride), list(padding), list(dilation), groups, deformable_groups, in_step)
+    # the forward read the fp32 matrix-math mode when it was issued (MDCONV_CUDA._desc, like deterministic mode); its
+    # backward runs in the same one
+    ctx.fp32_math = _capi.fp32_math_mode()
 
 
 def _autograd(ctx, grad_output):
@@ -238,8 +241,9 @@ def _autograd(ctx, grad_output):
     # only what autograd asks for (inputs: input, offset, mask, weight, bias, ...)
     need = ctx.needs_input_grad
     need_input, need_weight = bool(need[0]), bool(need[3] or (bias is not None and need[4]))
-    gi, goff, gm, gw, gb = deform_conv_backward_masked(grad_output, input, offset, mask, weight, bias,
-                                                       *ctx.conf, need_input, need_weight)
+    with _capi.fp32_math(ctx.fp32_math):
+        gi, goff, gm, gw, gb = deform_conv_backward_masked(grad_output, input, offset, mask, weight, bias,
+                                                           *ctx.conf, need_input, need_weight)
     return (gi if need_input else None, goff, gm if mask is not None else None, gw if need_weight else None,
             gb if bias is not None and need_weight else None, None, None, None, None, None, None)
 
