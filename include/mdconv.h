@@ -163,6 +163,32 @@ typedef struct mdconv_desc {
  * With MDCONV_F16, MDCONV_BF16 or MDCONV_F64 tensors the flag is MDCONV_EINVAL; v1 descriptors never request it.
  * (The value skips 16, which stays MDCONV_EINVAL like 2 above.) */
 #define MDCONV_FLAG_MATH_BF16 32
+/* MDCONV_FLAG_OUTPUT_CHANNELS_LAST, MDCONV_FLAG_GRAD_INPUT_CHANNELS_LAST -- channels-last results of the native 16-bit
+ * kernels, for models that run in torch.channels_last / channels_last_3d.
+ *  - OUTPUT_CHANNELS_LAST is the layout of the output-shaped tensor of the call: the forward's `output` is
+ *    [B, spatial..., C_out]; the backward's `grad_output` is.  The forward kernels store that layout from their accumulators
+ *    (same accumulators, one rounding: the values are those of the unflagged call, permuted); the backward brings each batch
+ *    chunk of grad_output into the layout its matrix kernels read with one pass inside the call, and sums grad_bias from that
+ *    copy (a call cut into batch chunks: from the caller's tensor, in the same order); grad_bias is bit for bit the
+ *    unflagged call's.
+ *  - GRAD_INPUT_CHANNELS_LAST: the backward's `grad_input` is [B, spatial..., C_in], in overwrite and in accumulate mode
+ *    (accumulate mode reads and adds in that layout).  Forwards accept and ignore the flag; with MDCONV_FLAG_NO_GRAD_INPUT it
+ *    is accepted and has nothing to do.
+ *  - Every other tensor keeps its layout: offset, mask and their gradients, weight, bias and their gradients, and `input`
+ *    (mdconv_desc.input_layout, below).
+ *  - MDCONV_F16 / MDCONV_BF16 only; they combine freely with MDCONV_SAMPLING_F32, MDCONV_WGRAD_F32, MDCONV_FLAG_DETERMINISTIC,
+ *    _NO_GRAD_INPUT and _NO_GRAD_WEIGHT.  With MDCONV_F32 (MDCONV_FLAG_MATH_BF16 included) or MDCONV_F64 they are
+ *    MDCONV_EINVAL; v1 descriptors never request them.
+ *  - A flag never changes the route of a call: same kernel family, plan, padded geometry, batch chunks and kernel per chunk
+ *    as the unflagged call.  The flags are honoured exactly where the native 16-bit plan takes this direction of the call
+ *    (mdconv_last_kernels() = MDCONV_KERNELS_HP) and the channel count of every flagged tensor is a multiple of 8 (16-byte
+ *    rows): C_out for the output side, C_in for grad_input.  mdconv_result_layout_supported() tells beforehand; a flagged
+ *    call for which it answers 0 returns MDCONV_EUNSUPPORTED before anything is launched.
+ *  - mdconv_workspace_bytes honours the flags and is exact: the forward's figure is unchanged; a backward with
+ *    OUTPUT_CHANNELS_LAST grows by one batch chunk's grad_output in 16 bits (one workspace slot) and by nothing else;
+ *    GRAD_INPUT_CHANNELS_LAST adds nothing. */
+#define MDCONV_FLAG_OUTPUT_CHANNELS_LAST 64
+#define MDCONV_FLAG_GRAD_INPUT_CHANNELS_LAST 128
 #define MDCONV_DESC_FLAGS(d) ((d)->reserved[4])
 
 /* Initialiser of a v2 descriptor: `mdconv_desc d = MDCONV_DESC_INIT(2);` then fill in the shape.
@@ -212,7 +238,8 @@ int mdconv_set_accumulate(int on);
  * ([B, spatial..., C], torch.channels_last / channels_last_3d).  Channels-last input is what the
  * native 16-bit kernels gather from, so it saves their layout pass; it is accepted for fp16 / bf16
  * tensors with C_in a multiple of 32 only (MDCONV_EUNSUPPORTED otherwise).  Every other tensor,
- * grad_input included, keeps the reference layout.
+ * grad_input included, keeps the reference layout unless the call asks otherwise (MDCONV_FLAG_OUTPUT_CHANNELS_LAST /
+ * MDCONV_FLAG_GRAD_INPUT_CHANNELS_LAST above: output / grad_output and grad_input).
  * mdconv_set_input_layout() is the ABI v1 setter (calling thread, descriptors without MDCONV_DESC_V2);
  * it returns the previous setting. */
 enum { MDCONV_LAYOUT_NCHW = 0, MDCONV_LAYOUT_CHANNELS_LAST = 1 };
@@ -222,6 +249,13 @@ int mdconv_set_input_layout(int layout);
  * forward), so a caller that saved a channels-last input for its backward asks here and makes a
  * contiguous copy when the answer is 0 (modulated_deform_conv_amd/MDCONV_CUDA.py does). */
 int mdconv_input_layout_supported(const mdconv_desc *d, int layout, int backward);
+
+/* 1 if the forward (backward = 0) / backward (backward = 1) of `d` honours the result-layout flags set in `d`
+ * (MDCONV_FLAG_OUTPUT_CHANNELS_LAST / MDCONV_FLAG_GRAD_INPUT_CHANNELS_LAST), else 0 with the rule in mdconv_last_error(): the
+ * native 16-bit plan takes this direction of the call as it is routed (`path`, `input_layout`, few-tile forwards and
+ * shapes that run through fp32 copies included) and C_out (output side) / C_in (grad_input) is a multiple of 8.  The two
+ * directions of one layer can differ.  1 for a descriptor without the flags; 0 for an invalid descriptor. */
+int mdconv_result_layout_supported(const mdconv_desc *d, int backward);
 
 /* 1 if the forward (backward = 0) / backward (backward = 1) of `d` can run in deterministic mode
  * (MDCONV_FLAG_DETERMINISTIC; the flag itself need not be set in `d`), else 0.  Every forward can.  A backward can

@@ -33,14 +33,84 @@ def _is_channels_last(t):
     return t.is_contiguous(memory_format=fmt)
 
 
+def _cl_result(t):
+    """`t` is a dense channels-last (torch.channels_last / channels_last_3d) fp16 / bf16 tensor that is not contiguous as
+    well: the layout the result-layout flags name (include/mdconv.h: MDCONV_FLAG_OUTPUT_CHANNELS_LAST /
+    MDCONV_FLAG_GRAD_INPUT_CHANNELS_LAST)."""
+    if t is None or t.dim() not in (4, 5) or t.dtype not in (torch.float16, torch.bfloat16) or t.is_contiguous():
+        return False
+    return t.is_contiguous(memory_format=torch.channels_last if t.dim() == 4 else torch.channels_last_3d)
+
+
+_CL_RESULTS = ("output", "grad_output", "grad_input")
+
+
 def _check_contig(**tensors):
+    cl_results = _capi.channels_last_results_mode()
     for name, t in tensors.items():
         if t is None:   # a gradient the call leaves out (_capi.skip_grads)
             continue
         # extension of the reference's check (mdeformable_conv.cu:127-131): a channels-last `input`
-        # is accepted where the kernels consume that layout anyway
-        if not t.is_contiguous() and not (name == "input" and _is_channels_last(t)):
+        # is accepted where the kernels consume that layout anyway (SURVEY.md section 8f-3) -- and, inside
+        # _capi.channels_last_results, a channels-last 16-bit output / grad_output / grad_input
+        if not t.is_contiguous() and not (name == "input" and _is_channels_last(t)) \
+                and not (cl_results and name in _CL_RESULTS and _cl_result(t)):
             raise RuntimeError("%s tensor has to be contiguous" % name)
+
+
+def _result_flags(d, input, backward, out_like, grad_input=None):
+    """Inside _capi.channels_last_results: sets the result-layout flags of `d` from the layouts of the output-shaped tensor
+    (`output` / `grad_output`) and of `grad_input`, as far as this direction honours them (include/mdconv.h:
+    mdconv_result_layout_supported -- both, else the output side alone, else grad_input alone), and returns the flags it
+    set.  `d` is complete but for them (dtype flags, input layout of the `input` that is handed over)."""
+    want = (_capi.FLAG_OUTPUT_CHANNELS_LAST if _cl_result(out_like) else 0) | \
+        (_capi.FLAG_GRAD_INPUT_CHANNELS_LAST if backward and _cl_result(grad_input) else 0)
+    if not want or not _capi.channels_last_results_mode():
+        return 0
+    query = getattr(_capi.lib(), "mdconv_result_layout_supported", None)
+    d.input_layout = int(not input.is_contiguous() and _is_channels_last(input))
+    tried = []
+    for flags in (want, want & _capi.FLAG_OUTPUT_CHANNELS_LAST, want & _capi.FLAG_GRAD_INPUT_CHANNELS_LAST):
+        if flags and flags not in tried and query is not None:
+            tried.append(flags)
+            d.flags |= flags
+            if query(ctypes.byref(d), int(backward)):
+                return flags
+            d.flags &= ~flags
+    return 0
+
+
+def _backward_layouts(d, input, grad_output, grad_input):
+    """Inside _capi.channels_last_results: a channels-last `grad_output` / `grad_input` goes to the library as it is where
+    the backward honours the layout (`_result_flags`); otherwise the call runs on contiguous temporaries, like any other
+    PyTorch operator would.  Returns (grad_output, grad_input, final): the tensors to hand over and, when `grad_input` is
+    such a temporary, the caller's tensor it is copied into after the call."""
+    if not _capi.channels_last_results_mode():
+        return grad_output, grad_input, None
+    got = _result_flags(d, input, True, grad_output, grad_input)
+    final = None
+    if _cl_result(grad_output) and not got & _capi.FLAG_OUTPUT_CHANNELS_LAST:
+        grad_output = grad_output.contiguous()
+    if _cl_result(grad_input) and not got & _capi.FLAG_GRAD_INPUT_CHANNELS_LAST:
+        final = grad_input
+        grad_input = grad_input.contiguous() if d.accumulate else torch.empty_like(grad_input, memory_format=torch.contiguous_format)
+    return grad_output, grad_input, final
+
+
+def channels_last_results_supported(nd, modulated, input, weight, ksz, stride, pad, dil, group, deformable_group, in_step,
+                                    with_bias, backward):
+    """Whether, inside _capi.channels_last_results, the forward stores a channels-last `output` (backward = False) / the
+    backward a channels-last `grad_input` (True) for this call by itself: what an entry point that allocates its results
+    asks before it picks their memory format (a channels-last `input` is what makes it ask)."""
+    if not _capi.channels_last_results_mode() or not (_is_channels_last(input) and not input.is_contiguous()):
+        return False
+    query = getattr(_capi.lib(), "mdconv_result_layout_supported", None)
+    if query is None:
+        return False
+    d = _desc(nd, modulated, input, weight, ksz, stride, pad, dil, group, deformable_group, in_step, with_bias)
+    d.input_layout = int(bool(_capi.lib().mdconv_input_layout_supported(ctypes.byref(d), 1, int(backward))))
+    d.flags |= _capi.FLAG_GRAD_INPUT_CHANNELS_LAST if backward else _capi.FLAG_OUTPUT_CHANNELS_LAST
+    return bool(query(ctypes.byref(d), int(backward)))
 
 
 def _ptr(t):
@@ -226,6 +296,7 @@ def _forward(nd, modulated, fn_name, input, weight, bias, offset, mask, output, 
     _check_contig(**tensors)
     d = _desc(nd, modulated, input, weight, ksz, stride, pad, dil, group, deformable_group, in_step,
               with_bias)
+    cl_input = input if output is None and _capi.channels_last_results_mode() else None
     input = _layout(d, input, False)
     osz = _out_shape(d, nd)
     _check_side(d, nd, _prod(ksz), offset, mask if modulated else None, output, "output", osz)
@@ -233,13 +304,24 @@ def _forward(nd, modulated, fn_name, input, weight, bias, offset, mask, output, 
                   bias=bias if with_bias else None, output=output)
     if with_bias and bias.numel() != d.c_out:
         raise RuntimeError("bias has %d elements, expected %d" % (bias.numel(), d.c_out))
+    final = None
     if output is None:
-        output = torch.empty((d.batch, d.c_out) + osz, dtype=input.dtype, device=input.device)
+        # (inside _capi.channels_last_results: channels-last when the `input` the caller gave is and the forward stores it)
+        fmt = torch.contiguous_format
+        if cl_input is not None and channels_last_results_supported(nd, modulated, cl_input, weight, ksz, stride, pad, dil, group,
+                                                        deformable_group, in_step, with_bias, False):
+            fmt = torch.channels_last if nd == 2 else torch.channels_last_3d
+        output = torch.empty((d.batch, d.c_out) + osz, dtype=input.dtype, device=input.device, memory_format=fmt)
+    if _cl_result(output) and not _result_flags(d, input, False, output):
+        final, output = output, torch.empty_like(output, memory_format=torch.contiguous_format)   # (the fallback: copied below)
     args = [_ptr(input), _ptr(weight), _ptr(bias), _ptr(offset)]
     if modulated:
         args.append(_ptr(mask))
     args.append(_ptr(output))
     _run(fn_name, d, False, args, input)
+    if final is not None:
+        final.copy_(output)
+        output = final
     return output
 
 
@@ -270,9 +352,12 @@ def deform_conv2d_backward_cuda(input, weight, bias, offset, grad_input, grad_we
     _check_side(d, 2, kernel_h * kernel_w, offset, None, grad_output, "grad_output", osz)
     _backward_checks(input, weight, offset, None, grad_input, grad_weight, grad_bias, grad_offset,
                      None, grad_output, d, with_bias)
+    grad_output, grad_input, final = _backward_layouts(d, input, grad_output, grad_input)
     _run("mdconv_deform_conv2d_backward", d, True,
          [_ptr(input), _ptr(weight), _ptr(bias), _ptr(offset), _ptr(grad_input), _ptr(grad_weight),
           _ptr(grad_bias), _ptr(grad_offset), _ptr(grad_output)], input)
+    if final is not None:
+        final.copy_(grad_input)
     return 0
 
 
@@ -315,9 +400,14 @@ def _modulated2d_backward(fused, input, weight, bias, offset, mask, grad_output,
     """`fused`: grad_weight and grad_bias are views of ONE buffer (the data-parallel exchange reduces it in place);
     False for torch.library operators, whose returns must not share storage (ops.py)."""
     _check_contig(input=input, weight=weight, bias=bias, offset=offset, mask=mask)
-    grad_output = grad_output.contiguous()
+    if not (_capi.channels_last_results_mode() and _cl_result(grad_output)):   # (inside the mode: channels-last as it is)
+        grad_output = grad_output.contiguous()
     d = _desc(2, True, input, weight, (kernel_h, kernel_w), (stride_h, stride_w), (pad_h, pad_w),
               (dilation_h, dilation_w), group, deformable_group, in_step, with_bias)
+    # (inside _capi.channels_last_results: grad_input channels-last when the `input` the caller gave is and the backward stores it)
+    gi_fmt = torch.channels_last if channels_last_results_supported(
+        2, True, input, weight, (kernel_h, kernel_w), (stride_h, stride_w), (pad_h, pad_w), (dilation_h, dilation_w), group,
+        deformable_group, in_step, with_bias, True) else torch.contiguous_format
     input = _layout(d, input, True)
     osz = _out_shape(d, 2)
     _check_side(d, 2, kernel_h * kernel_w, offset, mask, grad_output, "grad_output", osz)
@@ -325,7 +415,7 @@ def _modulated2d_backward(fused, input, weight, bias, offset, mask, grad_output,
     # entry point owns its results, so it allocates uninitialised memory and asks the library to
     # WRITE the gradients (mdconv_desc.accumulate = 0: no zero fills, no read-modify-write)
     skip_input, skip_weight = _capi.skipped_grads()   # (inside _capi.skip_grads: None for what the call leaves out)
-    grad_input = None if skip_input else torch.empty_like(input, memory_format=torch.contiguous_format)
+    grad_input = None if skip_input else torch.empty_like(input, memory_format=gi_fmt)
     grad_offset = torch.empty_like(offset)
     grad_mask = torch.empty_like(mask)
     # grad_weight || grad_bias live in ONE flat buffer: the data-parallel exchange is then a single in-place all-reduce
@@ -339,6 +429,7 @@ def _modulated2d_backward(fused, input, weight, bias, offset, mask, grad_output,
     _backward_checks(input, weight, offset, mask, grad_input, grad_weight, grad_bias, grad_offset,
                      grad_mask, grad_output, d, with_bias)
     d.accumulate = 0
+    grad_output, grad_input, final = _backward_layouts(d, input, grad_output, grad_input)   # (`final`: dropped, the temporary is the result)
     _run("mdconv_modulated_deform_conv2d_backward", d, True,
          [_ptr(input), _ptr(weight), _ptr(bias), _ptr(offset), _ptr(mask), _ptr(grad_output),
           _ptr(grad_input), _ptr(grad_offset), _ptr(grad_mask), _ptr(grad_weight),
@@ -374,9 +465,12 @@ def deform_conv3d_backward_cuda(input, weight, bias, offset, grad_input, grad_we
     _check_side(d, 3, _prod(ksz), offset, None, grad_output, "grad_output", osz)
     _backward_checks(input, weight, offset, None, grad_input, grad_weight, grad_bias, grad_offset,
                      None, grad_output, d, with_bias)
+    grad_output, grad_input, final = _backward_layouts(d, input, grad_output, grad_input)
     _run("mdconv_deform_conv3d_backward", d, True,
          [_ptr(input), _ptr(weight), _ptr(bias), _ptr(offset), _ptr(grad_input), _ptr(grad_weight),
           _ptr(grad_bias), _ptr(grad_offset), _ptr(grad_output)], input)
+    if final is not None:
+        final.copy_(grad_input)
     return 0
 
 
@@ -412,8 +506,11 @@ def modulated_deform_conv3d_backward_cuda(input, weight, bias, offset, mask, gra
     _check_side(d, 3, _prod(ksz), offset, mask, grad_output, "grad_output", osz)
     _backward_checks(input, weight, offset, mask, grad_input, grad_weight, grad_bias, grad_offset,
                      grad_mask, grad_output, d, with_bias)
+    grad_output, grad_input, final = _backward_layouts(d, input, grad_output, grad_input)
     _run("mdconv_modulated_deform_conv3d_backward", d, True,
          [_ptr(input), _ptr(weight), _ptr(bias), _ptr(offset), _ptr(mask), _ptr(grad_input),
           _ptr(grad_weight), _ptr(grad_bias), _ptr(grad_offset), _ptr(grad_mask),
           _ptr(grad_output)], input)
+    if final is not None:
+        final.copy_(grad_input)
     return 0

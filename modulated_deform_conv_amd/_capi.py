@@ -20,6 +20,8 @@ FLAG_DETERMINISTIC = 1   # MDCONV_FLAG_DETERMINISTIC, in the flags word (MdconvD
 FLAG_NO_GRAD_INPUT = 4   # MDCONV_FLAG_NO_GRAD_INPUT: the backward leaves grad_input out (value 2 stays invalid)
 FLAG_NO_GRAD_WEIGHT = 8  # MDCONV_FLAG_NO_GRAD_WEIGHT: the backward leaves grad_weight and grad_bias out
 FLAG_MATH_BF16 = 32      # MDCONV_FLAG_MATH_BF16: fp32 tensors may run on the bf16 matrix kernels (value 16 stays invalid)
+FLAG_OUTPUT_CHANNELS_LAST = 64        # MDCONV_FLAG_OUTPUT_CHANNELS_LAST: output (forward) / grad_output (backward) is channels-last
+FLAG_GRAD_INPUT_CHANNELS_LAST = 128   # MDCONV_FLAG_GRAD_INPUT_CHANNELS_LAST: the backward's grad_input is channels-last
 
 EXPORTS = (
     "mdconv_abi_version", "mdconv_last_error", "mdconv_out_size", "mdconv_workspace_bytes",
@@ -27,6 +29,7 @@ EXPORTS = (
     "mdconv_profile_enable", "mdconv_profile_read", "mdconv_profile_reset", "mdconv_profile_name",
     "mdconv_stream_wait_weight_ready", "mdconv_stream_wait_weight_ready_on", "mdconv_set_accumulate", "mdconv_set_input_layout",
     "mdconv_input_layout_supported", "mdconv_deterministic_supported", "mdconv_math_bf16_used",
+    "mdconv_result_layout_supported",
     "mdconv_deform_conv2d_forward", "mdconv_deform_conv2d_backward",
     "mdconv_modulated_deform_conv2d_forward", "mdconv_modulated_deform_conv2d_backward",
     "mdconv_deform_conv3d_forward", "mdconv_deform_conv3d_backward",
@@ -95,8 +98,13 @@ def lib():
         has_math_query = hasattr(L, "mdconv_math_bf16_used")
         if has_math_query:
             L.mdconv_math_bf16_used.argtypes = [ctypes.c_void_p, ctypes.c_int]
+        # (likewise a build from before the result-layout query: it honours no result layout)
+        has_layout_query = hasattr(L, "mdconv_result_layout_supported")
+        if has_layout_query:
+            L.mdconv_result_layout_supported.argtypes = [ctypes.c_void_p, ctypes.c_int]
+        missing = (() if has_math_query else ("mdconv_math_bf16_used",)) + (() if has_layout_query else ("mdconv_result_layout_supported",))
         for name in EXPORTS[11:]:
-            if name != "mdconv_math_bf16_used" or has_math_query:
+            if name not in missing:
                 getattr(L, name).restype = ctypes.c_int
         if L.mdconv_abi_version() != ABI_VERSION:
             raise ImportError("libmdconv_hip.so ABI version mismatch")
@@ -251,6 +259,35 @@ class fp32_math:
 
     def __exit__(self, *exc):
         _modes.fp32_math = self._prev
+        return False
+
+
+def channels_last_results_mode():
+    """True inside a ``channels_last_results`` context manager of this thread (innermost one: its ``on``), else False."""
+    return bool(getattr(_modes, "channels_last_results", False))
+
+
+class channels_last_results:
+    """Context manager: fp16 / bf16 calls of MDCONV_CUDA issued inside by this thread accept dense channels-last
+    (``torch.channels_last`` / ``channels_last_3d``) ``output``, ``grad_output`` and ``grad_input`` tensors
+    (``MDCONV_FLAG_OUTPUT_CHANNELS_LAST`` / ``MDCONV_FLAG_GRAD_INPUT_CHANNELS_LAST``, include/mdconv.h): where the native
+    16-bit kernels take the call they store / read that layout themselves, elsewhere the binding goes through a contiguous
+    temporary like any PyTorch operator, so no call raises over the mode.  The entry points that allocate their results
+    (the modulated 2-D pair, the autograd Functions) allocate ``output`` and ``grad_input`` channels-last when the
+    ``input`` they are given is.  Outside the mode nothing changes: such tensors have to be contiguous.  ``on=False``
+    switches the mode off inside an outer block.  Thread-local, nests, and travels in each call's descriptor like
+    ``overwrite_grads``; the autograd Functions record the mode in forward and enter it in backward themselves."""
+
+    def __init__(self, on=True):
+        self._on = bool(on)
+
+    def __enter__(self):
+        self._prev = channels_last_results_mode()
+        _modes.channels_last_results = self._on
+        return self
+
+    def __exit__(self, *exc):
+        _modes.channels_last_results = self._prev
         return False
 
 

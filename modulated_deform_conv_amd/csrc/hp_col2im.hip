@@ -24,6 +24,7 @@ int grid_for(int64_t total) {
   return (int)(b > 8192 ? 8192 : (b < 1 ? 1 : b));
 }
 
+#ifndef HP_GRAD_INPUT_CL_UNIT
 __global__ __launch_bounds__(256) void hp_zero_int_kernel(int *__restrict__ p, int64_t n) {
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) p[i] = 0;
 }
@@ -36,6 +37,7 @@ __global__ __launch_bounds__(256) void hp_csr_scan_kernel(int S, const int *__re
                                             int *__restrict__ rowptr) {
   csr_scan_chunk(S, cnt, rowptr);   // mdconv_common.hpp
 }
+#endif
 
 // Long entry = 2 x int4, fp32 fields: (src, wx, wy, rl0), (rh0, rl1, rh1, anchor)  [2-D: rl1 = rl0, rh1 = rh0].
 // Short entry = 1 x int4 (round 4: half the list bytes; cfg3 writes 3.6 M of them), 2-D fp16 tensors only:
@@ -91,11 +93,44 @@ __global__ __launch_bounds__(256) void hp_csr_fill_kernel(Geom g, int S_e,
 
 constexpr int kRun = 8;   // targets per run
 
+// Channels-last grad_input (the gather kernels' store policy GCL: grad_input is [B, spatial..., C_in], C_in a multiple of
+// 8, MDCONV_FLAG_GRAD_INPUT_CHANNELS_LAST): a lane holds the fp32 sums of channels c .. c + 7 (c a multiple of 8) of the
+// kernels' rows for target `row` = b * S_i + q and stores them with ONE 16-byte access -- load + add + store in
+// accumulate mode -- with no LDS transpose.  Group-padded / width-padded plans (caller_channel): padding channels are
+// not stored; caller groups of a multiple of 8 channels keep whole octets, other sizes go element by element.
+// Rounded once, like the transposed store: OT::pack rounds as OT::stf does.
+template <typename OT>
+__device__ __forceinline__ void hp_store_grad_input_cl(const Geom &g, typename OT::Raw *__restrict__ grad_input, int64_t row,
+                                                       int c, const float (&v)[8]) {
+  typename OT::Raw *dst = grad_input + row * caller_channels(g);
+  if (g.cm_pad == 0 || g.cm_real % 8 == 0) {
+    const int cc = caller_channel(g, c);   // the octet is real or padding as a whole
+    if (cc < 0) return;
+    U4 *p = reinterpret_cast<U4 *>(dst + cc);
+    float o[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) o[k] = v[k];
+    if (g.acc_data) {
+      const U4 old = *p;
+      o[0] = OT::lo(old.x) + v[0]; o[1] = OT::hi(old.x) + v[1]; o[2] = OT::lo(old.y) + v[2]; o[3] = OT::hi(old.y) + v[3];
+      o[4] = OT::lo(old.z) + v[4]; o[5] = OT::hi(old.z) + v[5]; o[6] = OT::lo(old.w) + v[6]; o[7] = OT::hi(old.w) + v[7];
+    }
+    *p = pack8<OT>(o);
+  } else {
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      const int cc = caller_channel(g, c + k);
+      if (cc >= 0) OT::stf(dst + cc, g.acc_data ? OT::ldf(dst + cc) + v[k] : v[k]);
+    }
+  }
+}
+
 // LPD lanes (8 channels each) follow one list; a wave walks 64 / LPD runs of kRun consecutive
 // targets side by side; workgroup tile = 4 * (64 / LPD) runs.  Channel units of LPD * 8 channels
 // (one deformable group each when DG > 1) are processed one after the other.
 // OT: the type grad_input is stored in (F32IO: fp32 tensors on the bf16 kernels)
-template <int ND, typename T, int LPD, typename OT = T>
+// GCL: grad_input is channels-last (hp_store_grad_input_cl: no LDS tile, no barriers); instances in hp_col2im_cl.hip
+template <int ND, typename T, int LPD, typename OT = T, bool GCL = false>
 __global__ __launch_bounds__(256) void hp_col2im_kernel(Geom g, HpDims hd, int S_e,
                                                         const typename T::Raw *__restrict__ gcol,
                                                         const int *__restrict__ rowptr,
@@ -107,7 +142,7 @@ __global__ __launch_bounds__(256) void hp_col2im_kernel(Geom g, HpDims hd, int S
   constexpr int CW = LPD * 8;              // channels per unit
   constexpr int UB = LPD < 8 ? LPD : 8;    // row loads in flight per step
   constexpr int TP = QT + 2;               // LDS pitch (16-bit elements)
-  __shared__ Raw tile[CW * TP];
+  __shared__ Raw tile[GCL ? 1 : CW * TP];
   const int qtiles = (g.S_i + QT - 1) / QT;
   const int bid = xcd_remap(blockIdx.x, gridDim.x);
   const int b = bid / qtiles;
@@ -194,7 +229,15 @@ __global__ __launch_bounds__(256) void hp_col2im_kernel(Geom g, HpDims hd, int S
           }
         }
       }
-      if (step > 0 && chan_on) {
+      if constexpr (GCL) {
+        if (step > 0 && chan_on && on && c8 < g.C) {
+          // the transposed store goes through a 16-bit tile: the sums are rounded to T BEFORE accumulate mode adds them to
+          // the buffer, and so they are here (overwrite mode: the one rounding) -- bit for bit the same grad_input
+          const U4 r16 = pack8<T>(cur);
+          const float v[8] = {T::lo(r16.x), T::hi(r16.x), T::lo(r16.y), T::hi(r16.y), T::lo(r16.z), T::hi(r16.z), T::lo(r16.w), T::hi(r16.w)};
+          hp_store_grad_input_cl<OT>(g, grad_input, (int64_t)b * g.S_i + a, c8, v);
+        }
+      } else if (step > 0 && chan_on) {
         Raw *tp = tile + (r * 8) * TP + (a - q0);
 #pragma unroll
         for (int k = 0; k < 8; ++k) T::stf(tp + k * TP, cur[k]);
@@ -208,6 +251,7 @@ __global__ __launch_bounds__(256) void hp_col2im_kernel(Geom g, HpDims hd, int S
         else ++tc[0];
       }
     }
+    if constexpr (GCL) continue;
     __syncthreads();
     // transpose out: consecutive threads -> consecutive q of one channel
     for (int x = threadIdx.x; x < CW * QT; x += 256) {
@@ -565,7 +609,9 @@ __global__ __launch_bounds__(256, NB <= 2 ? 4 : (NB == 4 ? 3 : 1)) void hp_col2i
 
 // pass 2: grad_input[b][c][t] (+)= sum_s A[segment(b, c)][anchor row t + s][x][s][c]; workgroup = 64
 // consecutive targets x 64 channels, lanes = (target, channel octet), LDS transpose to [B, C, S_i]
-template <int ND, typename T, typename OT = T>
+// GCL: grad_input is channels-last -- the lane's eight channels of a target leave with one 16-byte access
+// (hp_store_grad_input_cl) instead of the LDS transpose; instances in hp_col2im_cl.hip
+template <int ND, typename T, typename OT = T, bool GCL = false>
 __global__ __launch_bounds__(256) void hp_col2im_combine_kernel(Geom g, HpDims hd, int S_e,
                                                                 const typename SumStore<T>::type *__restrict__ sums,
                                                                 typename OT::Raw *__restrict__ grad_input) {
@@ -573,7 +619,7 @@ __global__ __launch_bounds__(256) void hp_col2im_combine_kernel(Geom g, HpDims h
   constexpr bool WIDE = sizeof(Sum) == 4;
   constexpr int L = ND - 1, NS = 1 << L;
   constexpr int QT = 64, CW = 64, TP = QT + 1;
-  __shared__ float tile[CW * TP];   // fp32: the stencil sum is rounded once, at the grad_input store
+  __shared__ float tile[GCL ? 1 : CW * TP];   // fp32: the stencil sum is rounded once, at the grad_input store
   const int qtiles = (g.S_i + QT - 1) / QT;
   const int b = blockIdx.x / qtiles, q0 = (blockIdx.x - b * qtiles) * QT;
   const int cseg = g.DG == 1 ? hd.Cp : g.Cdg;
@@ -610,10 +656,15 @@ __global__ __launch_bounds__(256) void hp_col2im_combine_kernel(Geom g, HpDims h
           }
         }
       }
+      if constexpr (GCL) {
+        if (q < g.S_i && c < hd.Cp) hp_store_grad_input_cl<OT>(g, grad_input, (int64_t)b * g.S_i + q, c, acc);
+        continue;
+      }
       float *tp = tile + ((threadIdx.x & 7) * 8) * TP + ql;
 #pragma unroll
       for (int k = 0; k < 8; ++k) tp[k * TP] = acc[k];
     }
+    if constexpr (GCL) continue;
     __syncthreads();
     for (int x = threadIdx.x; x < CW * QT; x += 256) {
       const int cl = x / QT, ql = x - cl * QT;
@@ -628,7 +679,7 @@ __global__ __launch_bounds__(256) void hp_col2im_combine_kernel(Geom g, HpDims h
   }
 }
 
-template <int ND, typename T, typename OT = T>
+template <int ND, typename T, typename OT = T, bool GCL = false>
 int launch_col2im(const Geom &g, const HpDims &hd, const Tensors &t, const void *gcol,
                   const int *rowptr, const void *entries, hipStream_t stream) {
   using Raw = typename T::Raw;
@@ -638,7 +689,7 @@ int launch_col2im(const Geom &g, const HpDims &hd, const Tensors &t, const void 
 #define HP_C2I(LPD)                                                                              \
   do {                                                                                           \
     const int qt = 4 * (64 / LPD) * kRun;                                                        \
-    hipLaunchKernelGGL((hp_col2im_kernel<ND, T, LPD, OT>), dim3(g.B * ((g.S_i + qt - 1) / qt)),  \
+    hipLaunchKernelGGL((hp_col2im_kernel<ND, T, LPD, OT, GCL>), dim3(g.B * ((g.S_i + qt - 1) / qt)), \
                        dim3(256), 0, stream, g, hd, S_e, (const Raw *)gcol, rowptr,              \
                        (const int4 *)entries, (typename OT::Raw *)t.grad_input);                 \
   } while (0)
@@ -651,7 +702,33 @@ int launch_col2im(const Geom &g, const HpDims &hd, const Tensors &t, const void 
   return check_launch("hp_col2im");
 }
 
+// pass 2 of the two-pass gather
+template <int ND, typename T, typename OT = T, bool GCL = false>
+int launch_combine(const Geom &g, const HpDims &hd, const Tensors &t, const void *sums, hipStream_t stream) {
+  hipLaunchKernelGGL((hp_col2im_combine_kernel<ND, T, OT, GCL>), dim3(g.B * ((g.S_i + 63) / 64)), dim3(256), 0, stream, g, hd,
+                     hp_anchor_space(g), (const typename SumStore<T>::type *)sums, (typename OT::Raw *)t.grad_input);
+  return check_launch("hp_col2im_combine");
+}
+
 }  // namespace
+
+#ifdef HP_GRAD_INPUT_CL_UNIT
+// channels-last grad_input (Tensors::gi_cl): the storing kernels of the gather with the channels-last store policy, compiled
+// in their own unit (hp_col2im_cl.hip); pass 1 of the two-pass gather is hp_col2im.hip's
+int hp_col2im_combine_cl(const Geom &g, const HpDims &hd, int dtype, const Tensors &t, const void *sums, hipStream_t stream) {
+  if (dtype == MDCONV_F16)
+    return g.nd == 2 ? launch_combine<2, F16, F16, true>(g, hd, t, sums, stream) : launch_combine<3, F16, F16, true>(g, hd, t, sums, stream);
+  return g.nd == 2 ? launch_combine<2, BF16, BF16, true>(g, hd, t, sums, stream) : launch_combine<3, BF16, BF16, true>(g, hd, t, sums, stream);
+}
+int hp_col2im_cl(const Geom &g, const HpDims &hd, int dtype, const Tensors &t, const void *gcol,
+                 const int *rowptr, const void *entries, hipStream_t stream) {
+  if (dtype == MDCONV_F16)
+    return g.nd == 2 ? launch_col2im<2, F16, F16, true>(g, hd, t, gcol, rowptr, entries, stream)
+                     : launch_col2im<3, F16, F16, true>(g, hd, t, gcol, rowptr, entries, stream);
+  return g.nd == 2 ? launch_col2im<2, BF16, BF16, true>(g, hd, t, gcol, rowptr, entries, stream)
+                   : launch_col2im<3, BF16, BF16, true>(g, hd, t, gcol, rowptr, entries, stream);
+}
+#else
 
 int hp_csr_zero(const Geom &g, int *cnt, hipStream_t stream) {
   const int64_t cnt_n = (int64_t)g.B * g.DG * hp_anchor_space(g);
@@ -730,9 +807,8 @@ static int launch_col2im2(const Geom &g, const HpDims &hd, const Tensors &t, con
 #undef HP_C2S
   int rc = check_launch("hp_col2im_sums");
   if (rc) return rc;
-  hipLaunchKernelGGL((hp_col2im_combine_kernel<ND, T, OT>), dim3(g.B * ((g.S_i + 63) / 64)), dim3(256), 0, stream, g, hd,
-                     S_e, (const typename SumStore<T>::type *)sums, (typename OT::Raw *)t.grad_input);
-  return check_launch("hp_col2im_combine");
+  if (t.gi_cl) return hp_col2im_combine_cl(g, hd, ShortEntry<2, T>::value ? MDCONV_F16 : MDCONV_BF16, t, sums, stream);   // (the trait names T)
+  return launch_combine<ND, T, OT>(g, hd, t, sums, stream);
 }
 
 size_t hp_col2im_sums_bytes(const Geom &g, const HpDims &hd, int dtype) {
@@ -754,6 +830,7 @@ int hp_col2im2(const Geom &g, const HpDims &hd, int dtype, const Tensors &t, con
 
 int hp_col2im(const Geom &g, const HpDims &hd, int dtype, const Tensors &t, const void *gcol,
               const int *rowptr, const void *entries, hipStream_t stream) {
+  if (t.gi_cl) return hp_col2im_cl(g, hd, dtype, t, gcol, rowptr, entries, stream);
   if (t.io32)   // fp32 grad_input
     return g.nd == 2 ? launch_col2im<2, BF16, F32IO>(g, hd, t, gcol, rowptr, entries, stream)
                      : launch_col2im<3, BF16, F32IO>(g, hd, t, gcol, rowptr, entries, stream);
@@ -763,5 +840,6 @@ int hp_col2im(const Geom &g, const HpDims &hd, int dtype, const Tensors &t, cons
   return g.nd == 2 ? launch_col2im<2, BF16>(g, hd, t, gcol, rowptr, entries, stream)
                    : launch_col2im<3, BF16>(g, hd, t, gcol, rowptr, entries, stream);
 }
+#endif
 
 }  // namespace mdconv

@@ -117,6 +117,26 @@ struct F32IO {
   static __device__ __forceinline__ float ldf(const Raw *p) { return *p; }
   static __device__ __forceinline__ void stf(Raw *p, float v) { *p = v; }
 };
+// Channels-last store of a lane's 32 x 32 accumulators (the forward kernels' store policy OCL: `output` is
+// [B, spatial..., O] with O a multiple of 8).  Accumulator r of block ob is channel 32 ob + (r & 3) + 8 (r >> 2) + 4 kh of
+// the lane's pixel, so r = 4 q .. 4 q + 3 are four consecutive channels: one 8-byte store, and lanes l and l + 32 (kh = 0 / 1)
+// write the two halves of 16 contiguous bytes.  The values are rounded as OT::stf rounds them (OT::pack: to nearest even).
+// `row` = b * S_o + pix, `ob0` the first 32-channel block of the workgroup's row.
+template <typename OT, int MB>
+__device__ __forceinline__ void hp_store_output_cl(const Geom &g, typename OT::Raw *__restrict__ output, int64_t row, int ob0,
+                                                   int kh, const f32x16 (&acc)[MB]) {
+  typename OT::Raw *dst = output + row * g.O;
+#pragma unroll
+  for (int ob = 0; ob < MB; ++ob)
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int o = (ob0 + ob) * 32 + 8 * q + 4 * kh;
+      if (o < g.O)   // (O is a multiple of 8: the four channels are inside or outside together)
+        *reinterpret_cast<uint2 *>(dst + o) = make_uint2(OT::pack(acc[ob][4 * q], acc[ob][4 * q + 1]),
+                                                         OT::pack(acc[ob][4 * q + 2], acc[ob][4 * q + 3]));
+    }
+}
+
 // one fp32 value as the bf16 matrix operand it becomes: the rounding of BF16::stf / BF16::pack (to nearest even)
 __device__ __forceinline__ unsigned short bf16_operand_bits(float v) { return __builtin_bit_cast(unsigned short, (__bf16)v); }
 

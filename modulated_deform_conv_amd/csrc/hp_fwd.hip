@@ -26,7 +26,9 @@ namespace {
 constexpr int kStage = 4;   // 16-channel chunks per LDS stage of the weights
 
 // OT: the type `bias` and `output` are stored in (F32IO: fp32 tensors on the bf16 kernels)
-template <int ND, bool MOD, typename T, int MB, typename SE = typename T::Raw, typename OT = T>
+// OCL: `output` is channels-last [B, spatial..., O] (MDCONV_FLAG_OUTPUT_CHANNELS_LAST; 16-bit OT, O a multiple of 8) -- the
+// store policy of the epilogue, nothing else; instances in hp_fwd_cl.hip
+template <int ND, bool MOD, typename T, int MB, typename SE = typename T::Raw, typename OT = T, bool OCL = false>
 __global__ __launch_bounds__(256, 2) void hp_fwd_kernel(
     Geom g, HpDims hd, const typename T::Raw *__restrict__ xt, const U4 *__restrict__ wpf,
     const typename OT::Raw *__restrict__ bias, const SE *__restrict__ offset,
@@ -214,6 +216,10 @@ __global__ __launch_bounds__(256, 2) void hp_fwd_kernel(
           acc[ob][r] += OT::ldf(bias + (o < g.O ? o : 0));
         }
     }
+    if constexpr (OCL) {
+      hp_store_output_cl<OT, MB>(g, output, (int64_t)b * g.S_o + pix, orange * MB, kh, acc);
+      return;
+    }
 #pragma unroll
     for (int ob = 0; ob < MB; ++ob)
 #pragma unroll
@@ -226,14 +232,14 @@ __global__ __launch_bounds__(256, 2) void hp_fwd_kernel(
 
 }  // namespace
 
-template <int ND, bool MOD, typename T, typename SE, typename OT = T>
+template <int ND, bool MOD, typename T, typename SE, typename OT = T, bool OCL = false>
 static int launch_fwd_hp(const Geom &g, const HpDims &hd, const Tensors &t, const void *xt,
                          const void *wpf, const int2 *ctab, hipStream_t stream) {
   using Raw = typename T::Raw;
   using Out = typename OT::Raw;
   const dim3 grid((g.N + 127) / 128, hd.oranges);
 #define HP_FWD(MBV)                                                                              \
-  hipLaunchKernelGGL((hp_fwd_kernel<ND, MOD, T, MBV, SE, OT>), grid, dim3(256), 0, stream, g, hd,   \
+  hipLaunchKernelGGL((hp_fwd_kernel<ND, MOD, T, MBV, SE, OT, OCL>), grid, dim3(256), 0, stream, g, hd, \
                      (const Raw *)xt, (const U4 *)wpf, (const Out *)t.bias, (const SE *)t.offset,   \
                      (const SE *)t.mask, (Out *)t.output, ctab)
   switch (hd.MB) {
@@ -245,8 +251,6 @@ static int launch_fwd_hp(const Geom &g, const HpDims &hd, const Tensors &t, cons
   return check_launch("hp_fwd");
 }
 
-int hp_forward_launch(const Geom &g, const HpDims &hd, int dtype, const Tensors &t, const void *xt,
-                      const void *wpf, const int2 *ctab, hipStream_t stream) {
 #define HP_DISPATCH(...)                                                                              \
   do {                                                                                               \
     if (g.nd == 2)                                                                                   \
@@ -255,6 +259,10 @@ int hp_forward_launch(const Geom &g, const HpDims &hd, int dtype, const Tensors 
     return g.modulated ? launch_fwd_hp<3, true, __VA_ARGS__>(g, hd, t, xt, wpf, ctab, stream)          \
                        : launch_fwd_hp<3, false, __VA_ARGS__>(g, hd, t, xt, wpf, ctab, stream);        \
   } while (0)
+#ifndef HP_OUTPUT_CL_UNIT
+int hp_forward_launch(const Geom &g, const HpDims &hd, int dtype, const Tensors &t, const void *xt,
+                      const void *wpf, const int2 *ctab, hipStream_t stream) {
+  if (t.out_cl) return hp_forward_launch_cl(g, hd, dtype, t, xt, wpf, ctab, stream);
   if (t.io32) HP_DISPATCH(BF16, float, F32IO);   // fp32 bias and output (and fp32 offsets / masks)
   if (t.samp32) {
     if (dtype == MDCONV_F16) HP_DISPATCH(F16, float);
@@ -262,7 +270,20 @@ int hp_forward_launch(const Geom &g, const HpDims &hd, int dtype, const Tensors 
   }
   if (dtype == MDCONV_F16) HP_DISPATCH(F16, F16::Raw);
   HP_DISPATCH(BF16, BF16::Raw);
-#undef HP_DISPATCH
 }
+#else
+// channels-last `output` (Tensors::out_cl): the same kernels with the channels-last store policy, compiled in their own
+// unit (hp_fwd_cl.hip)
+int hp_forward_launch_cl(const Geom &g, const HpDims &hd, int dtype, const Tensors &t, const void *xt,
+                         const void *wpf, const int2 *ctab, hipStream_t stream) {
+  if (t.samp32) {
+    if (dtype == MDCONV_F16) HP_DISPATCH(F16, float, F16, true);
+    HP_DISPATCH(BF16, float, BF16, true);
+  }
+  if (dtype == MDCONV_F16) HP_DISPATCH(F16, F16::Raw, F16, true);
+  HP_DISPATCH(BF16, BF16::Raw, BF16, true);
+}
+#endif
+#undef HP_DISPATCH
 
 }  // namespace mdconv

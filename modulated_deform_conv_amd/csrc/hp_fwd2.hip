@@ -31,7 +31,8 @@ constexpr int kBtP = 72;     // LDS pitch (16-bit elements) of a pixel row of th
 
 // GRP = false: one conv group -- every chunk feeds every output-channel block, no table lookups.
 // OT: the type `bias` and `output` are stored in (F32IO: fp32 tensors on the bf16 kernels)
-template <int ND, bool MOD, typename T, int MB, bool GRP, typename SE = typename T::Raw, typename OT = T>
+// OCL: `output` is channels-last (the epilogue's store policy, hp_fwd.hip); instances in hp_fwd2_cl.hip
+template <int ND, bool MOD, typename T, int MB, bool GRP, typename SE = typename T::Raw, typename OT = T, bool OCL = false>
 __global__ __launch_bounds__(256, 2) void hp_fwd2_kernel(
     Geom g, HpDims hd, const typename T::Raw *__restrict__ xt, const U4 *__restrict__ wpf,
     const typename OT::Raw *__restrict__ bias, const SE *__restrict__ offset,
@@ -314,6 +315,10 @@ __global__ __launch_bounds__(256, 2) void hp_fwd2_kernel(
           acc[ob][r] += OT::ldf(bias + (o < g.O ? o : 0));
         }
     }
+    if constexpr (OCL) {
+      hp_store_output_cl<OT, MB>(g, output, (int64_t)b * g.S_o + pix, orange * MB, kh, acc);
+      return;
+    }
 #pragma unroll
     for (int ob = 0; ob < MB; ++ob)
 #pragma unroll
@@ -327,13 +332,13 @@ __global__ __launch_bounds__(256, 2) void hp_fwd2_kernel(
 }  // namespace
 
 
-size_t hp_fwd2_lds_bytes(const Geom &g, const HpDims &hd) {
+static size_t hp_fwd2_lds_bytes(const Geom &g, const HpDims &hd) {
   const int nc = 1 << g.nd;
   const size_t win = 0;
   return (size_t)2 * kStage * (g.G == 1 ? hd.MB : hd.fwd_nmax) * 1024 + (size_t)4 * 32 * kBtP * 2 + (size_t)4 * kStSlots * 32 * 2 * nc * 4 + win;
 }
 
-template <int ND, bool MOD, typename T, typename SE, typename OT = T>
+template <int ND, bool MOD, typename T, typename SE, typename OT = T, bool OCL = false>
 static int launch_fwd2_hp(const Geom &g, const HpDims &hd, const Tensors &t, const void *xt,
                           const void *wpf, const int2 *ctab, hipStream_t stream) {
   using Raw = typename T::Raw;
@@ -347,12 +352,12 @@ static int launch_fwd2_hp(const Geom &g, const HpDims &hd, const Tensors &t, con
 #define HP_FWD2_(MBV, GRPV)                                                                      \
   do {                                                                                           \
     if (lds > 64 * 1024) {                                                                       \
-      hipError_t ea = hipFuncSetAttribute((const void *)hp_fwd2_kernel<ND, MOD, T, MBV, GRPV, SE, OT>,    \
+      hipError_t ea = hipFuncSetAttribute((const void *)hp_fwd2_kernel<ND, MOD, T, MBV, GRPV, SE, OT, OCL>,    \
                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
       if (ea != hipSuccess) { set_error("hipFuncSetAttribute: %s", hipGetErrorString(ea)); return MDCONV_ELAUNCH; } \
     }                                                                                            \
-    hp_debug_plan("hp_fwd2", hp_fwd2_kernel<ND, MOD, T, MBV, GRPV, SE, OT>, 256, lds, (long)grid.x * grid.y);   \
-    hipLaunchKernelGGL((hp_fwd2_kernel<ND, MOD, T, MBV, GRPV, SE, OT>), grid, dim3(256), lds, stream, g, hd, \
+    hp_debug_plan("hp_fwd2", hp_fwd2_kernel<ND, MOD, T, MBV, GRPV, SE, OT, OCL>, 256, lds, (long)grid.x * grid.y);   \
+    hipLaunchKernelGGL((hp_fwd2_kernel<ND, MOD, T, MBV, GRPV, SE, OT, OCL>), grid, dim3(256), lds, stream, g, hd, \
                        (const Raw *)xt, (const U4 *)wpf, (const Out *)t.bias, (const SE *)t.offset, \
                        (const SE *)t.mask, (Out *)t.output, ctab);                              \
   } while (0)
@@ -366,8 +371,6 @@ static int launch_fwd2_hp(const Geom &g, const HpDims &hd, const Tensors &t, con
   return check_launch("hp_fwd2");
 }
 
-int hp_forward2_launch(const Geom &g, const HpDims &hd, int dtype, const Tensors &t, const void *xt,
-                       const void *wpf, const int2 *ctab, hipStream_t stream) {
 #define HP_DISPATCH(...)                                                                              \
   do {                                                                                               \
     if (g.nd == 2)                                                                                   \
@@ -376,6 +379,10 @@ int hp_forward2_launch(const Geom &g, const HpDims &hd, int dtype, const Tensors
     return g.modulated ? launch_fwd2_hp<3, true, __VA_ARGS__>(g, hd, t, xt, wpf, ctab, stream)         \
                        : launch_fwd2_hp<3, false, __VA_ARGS__>(g, hd, t, xt, wpf, ctab, stream);       \
   } while (0)
+#ifndef HP_OUTPUT_CL_UNIT
+int hp_forward2_launch(const Geom &g, const HpDims &hd, int dtype, const Tensors &t, const void *xt,
+                       const void *wpf, const int2 *ctab, hipStream_t stream) {
+  if (t.out_cl) return hp_forward2_launch_cl(g, hd, dtype, t, xt, wpf, ctab, stream);
   if (t.io32) HP_DISPATCH(BF16, float, F32IO);   // fp32 bias and output (and fp32 offsets / masks)
   if (t.samp32) {
     if (dtype == MDCONV_F16) HP_DISPATCH(F16, float);
@@ -383,7 +390,20 @@ int hp_forward2_launch(const Geom &g, const HpDims &hd, int dtype, const Tensors
   }
   if (dtype == MDCONV_F16) HP_DISPATCH(F16, F16::Raw);
   HP_DISPATCH(BF16, BF16::Raw);
-#undef HP_DISPATCH
 }
+#else
+// channels-last `output` (Tensors::out_cl): the same kernels with the channels-last store policy, compiled in their own
+// unit (hp_fwd2_cl.hip)
+int hp_forward2_launch_cl(const Geom &g, const HpDims &hd, int dtype, const Tensors &t, const void *xt,
+                          const void *wpf, const int2 *ctab, hipStream_t stream) {
+  if (t.samp32) {
+    if (dtype == MDCONV_F16) HP_DISPATCH(F16, float, F16, true);
+    HP_DISPATCH(BF16, float, BF16, true);
+  }
+  if (dtype == MDCONV_F16) HP_DISPATCH(F16, F16::Raw, F16, true);
+  HP_DISPATCH(BF16, BF16::Raw, BF16, true);
+}
+#endif
+#undef HP_DISPATCH
 
 }  // namespace mdconv

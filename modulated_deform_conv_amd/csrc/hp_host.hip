@@ -128,7 +128,7 @@ BwdNeed bwd_need(const HpChunk &c, int ranges, int dtype, bool two_pass_gather) 
   n.sums = two_pass_gather ? hp_col2im_sums_bytes(gc, hd, dtype) : 0;
   // deterministic mode (Geom::det): scratch of the list sort, shaped like the entries (csr_sort.hip)
   n.sort = gc.det ? csr_sort_scratch_bytes(hp_entry_width(gc, dtype), (int64_t)gc.K * gc.S_o, gc.B * gc.DG) : 0;
-  n.go16 = (size_t)gc.B * gc.O * gc.S_o * 2;   // (laid out for fp32 tensors on the bf16 kernels only)
+  n.go16 = (size_t)gc.B * gc.O * gc.S_o * 2;   // (laid out for fp32 tensors on the bf16 kernels / a channels-last grad_output only)
   return n;
 }
 
@@ -136,8 +136,9 @@ BwdNeed bwd_need(const HpChunk &c, int ranges, int dtype, bool two_pass_gather) 
 // `skip`: without weight gradients no column rows (hp_bwd3 runs its variant without them), no running grad_weight, and
 // no partials unless a chunk runs a kernel with GEMM-2 fused in (`fused_partials`: hp_bwd2 / hp_bwd write and discard them);
 // without grad_input no row pointers, entries, partial sums or sort scratch -- the counters stay, the kernels count into them
-// `io32`: the bf16 copy of a chunk's fp32 grad_output, last, so that every other slot sits where the bf16 call has it
-HpBwdLayout bwd_layout(const HpChunk &c, int dtype, bool two_pass_gather, bool io32, Skip skip = Skip(), bool fused_partials = true) {
+// `go16`: the 16-bit [B, C_out, spatial] copy of a chunk's grad_output (fp32 tensors: HpPlan::io32; a channels-last
+// grad_output: HpPlan::out_cl), last, so that every other slot sits where the plain 16-bit call has it
+HpBwdLayout bwd_layout(const HpChunk &c, int dtype, bool two_pass_gather, bool go16, Skip skip = Skip(), bool fused_partials = true) {
   const Geom &gc = c.gc;
   const HpDims &hd = c.hd;
   // a shorter last chunk can have MORE ranges than a full one (ranges is not monotonic in the tile
@@ -162,7 +163,7 @@ HpBwdLayout bwd_layout(const HpChunk &c, int dtype, bool two_pass_gather, bool i
   L.off_entries = b.take(n.entries);
   L.off_sums = b.take(n.sums);
   L.off_sort = b.take(n.sort);
-  L.off_go16 = b.take(io32 ? n.go16 : 0);
+  L.off_go16 = b.take(go16 ? n.go16 : 0);
   L.total = b.off;
   return L;
 }
@@ -170,14 +171,14 @@ HpBwdLayout bwd_layout(const HpChunk &c, int dtype, bool two_pass_gather, bool i
 // The layout is made for the full chunk; a tail chunk has its own dimensions and picks its own kernel (it may take hp_bwd3
 // where the full chunk did not, or have more pixel ranges), so what it needs is compared with every slot it uses.
 // Returns the name of a slot that is too small for chunk `c`, or null.
-const char *bwd_short_slot(const HpBwdLayout &L, const HpChunk &c, int dtype, bool two_pass_gather, bool io32) {
+const char *bwd_short_slot(const HpBwdLayout &L, const HpChunk &c, int dtype, bool two_pass_gather, bool go16) {
   const BwdNeed n = bwd_need(c, c.bwd == HpChunk::BWD3 ? c.hd.ranges_w : c.hd.ranges, dtype, two_pass_gather);
   const struct { const char *name; size_t need, have; } slots[] = {
       {"channels-last input copy", n.xt, L.off_w - L.off_xt},   {"grad_col rows", n.gcol, L.off_col - L.off_gcol},
       {"column rows", n.col, L.off_part - L.off_col},           {"grad_weight partials", n.part, L.off_gw32 - L.off_part},
       {"list counters", n.cnt, L.off_rowptr - L.off_cnt},       {"list row pointers", n.rowptr, L.off_entries - L.off_rowptr},
       {"list entries", n.entries, L.off_sums - L.off_entries},  {"partial sums", n.sums, L.off_sort - L.off_sums},
-      {"sort scratch", n.sort, L.off_go16 - L.off_sort},        {"grad_output copy", io32 ? n.go16 : 0, L.total - L.off_go16}};
+      {"sort scratch", n.sort, L.off_go16 - L.off_sort},        {"grad_output copy", go16 ? n.go16 : 0, L.total - L.off_go16}};
   for (const auto &s : slots)
     if (s.need > s.have) return s.name;
   return nullptr;
@@ -373,7 +374,17 @@ static bool forward_preferred(const Geom &gcall, const Geom &g, int dtype) {
   return !mfma_supported(gcall, dtype, false);
 }
 
-bool hp_plan(const Geom &gcall, int dtype, bool backward, HpPlan *p, Skip skip, bool io32) {
+// The rule of the result layouts (include/mdconv.h: mdconv_result_layout_supported), for a call hp_plan takes: the rows of a
+// flagged tensor are whole 16-byte pieces -- C_out a multiple of 8 for the output side, the CALLER's C_in for grad_input.
+static const char *result_layout_refusal(const Geom &gcall, bool out_cl, bool gi_cl) {
+  if (out_cl && gcall.O % 8)
+    return "MDCONV_FLAG_OUTPUT_CHANNELS_LAST needs C_out to be a multiple of 8 (16-byte rows)";
+  if (gi_cl && gcall.C % 8)
+    return "MDCONV_FLAG_GRAD_INPUT_CHANNELS_LAST needs C_in to be a multiple of 8 (16-byte rows)";
+  return nullptr;
+}
+
+bool hp_plan(const Geom &gcall, int dtype, bool backward, HpPlan *p, Skip skip, bool io32, bool out_cl, bool gi_cl) {
   // the geometry the kernels run: the caller's -- or, in the backward, its width-padded form where the full chunk of THAT
   // takes hp_bwd3 --, else the group-padded form
   Geom gv;
@@ -390,15 +401,20 @@ bool hp_plan(const Geom &gcall, int dtype, bool backward, HpPlan *p, Skip skip, 
   p->bwd = HpBwdLayout();
   p->skip = Skip();
   p->io32 = io32;
+  // result layouts: 16-bit tensors only (the caller checks the dtype); grad_input's is the backward's, where it is computed
+  p->out_cl = out_cl && !io32;
+  p->gi_cl = gi_cl && !io32 && backward && !skip.input;
+  p->layout_refusal = result_layout_refusal(gcall, p->out_cl, p->gi_cl);
+  const bool go16 = io32 || p->out_cl;
   if (!backward) {
     p->fwd = fwd_layout(p->full.gc, p->full.hd);
     p->total = p->fwd.total;
     return true;
   }
-  p->bwd = bwd_layout(p->full, dtype, p->two_pass_gather, io32);
+  p->bwd = bwd_layout(p->full, dtype, p->two_pass_gather, go16);
   p->total = p->bwd.total;
   for (const HpChunk *c : {&p->full, &p->tail}) {
-    const char *slot = bwd_short_slot(p->bwd, *c, dtype, p->two_pass_gather, io32);
+    const char *slot = bwd_short_slot(p->bwd, *c, dtype, p->two_pass_gather, go16);
     if (slot) {
       set_error("hp_plan: the %s of a chunk of %d images do not fit the slot laid out for chunks of %d", slot, c->gc.B, p->Bc);
       return false;
@@ -409,7 +425,7 @@ bool hp_plan(const Geom &gcall, int dtype, bool backward, HpPlan *p, Skip skip, 
   p->skip = skip;
   if (skip.input || skip.weight) {
     const bool fused = p->full.bwd != HpChunk::BWD3 || p->tail.bwd != HpChunk::BWD3;   // a chunk writes fp32 partials itself
-    p->bwd = bwd_layout(p->full, dtype, p->two_pass_gather, io32, skip, fused);
+    p->bwd = bwd_layout(p->full, dtype, p->two_pass_gather, go16, skip, fused);
     p->total = p->bwd.total;
   }
   return true;
@@ -419,6 +435,8 @@ bool hp_plan(const Geom &gcall, int dtype, bool backward, HpPlan *p, Skip skip, 
 static Tensors plan_tensors(const HpPlan &p, Tensors t) {
   t.io32 = p.io32 ? 1 : 0;
   if (p.io32) t.samp32 = t.wgrad32 = 1;
+  t.out_cl = p.out_cl ? 1 : 0;   // the result layouts (a plan with a layout_refusal is never run)
+  t.gi_cl = p.gi_cl ? 1 : 0;
   return t;
 }
 
@@ -476,7 +494,12 @@ int hp_backward(int dtype, const HpPlan &p, const Tensors &t_call, void *ws, hip
   int rc;
   if ((rc = hp_pack_bwd_weights(p.full.gc, p.full.hd, dtype, t.weight, io32, base + L.off_w, (int4 *)(base + L.off_tab), stream)))
     return rc;
-  if (g.with_bias && !skip.weight && !io32 && (rc = hp_grad_bias(g, dtype, t.grad_output, t.grad_bias, t.wgrad32 != 0, stream)))
+  if (g.with_bias && !skip.weight && !io32 && !p.out_cl && (rc = hp_grad_bias(g, dtype, t.grad_output, t.grad_bias, t.wgrad32 != 0, stream)))
+    return rc;
+  // a channels-last grad_output cut into batch chunks: grad_bias from the caller's tensor, whole batch, in the summation order
+  // of hp_grad_bias (one rounding, bit for bit the unflagged call's); a call of one chunk sums its copy below
+  if (g.with_bias && !skip.weight && p.out_cl && Bc < g.B &&
+      (rc = hp_grad_bias_cl(g, dtype, t.grad_output, t.grad_bias, t.wgrad32 != 0, stream)))
     return rc;
   for (int b0 = 0; b0 < g.B; b0 += Bc) {
     const int bc = g.B - b0 < Bc ? g.B - b0 : Bc;
@@ -506,6 +529,14 @@ int hp_backward(int dtype, const HpPlan &p, const Tensors &t_call, void *ws, hip
         if (!first) gb.acc_w = 1;
         if ((rc = hp_grad_bias(gb, dtype, tc.grad_output, t.grad_bias, true, stream))) return rc;
       }
+    } else if (p.out_cl) {
+      // a channels-last grad_output: the chunk in the layout the kernels read (their tiles are pixel-contiguous); a call of
+      // one chunk sums grad_bias from that copy (the very sum of the unflagged call)
+      if ((rc = hp_nhwc_to_nchw(gc, tc.grad_output, base + L.off_go16, stream))) return rc;
+      tc.grad_output = base + L.off_go16;
+      if (g.with_bias && !skip.weight && !multi &&
+          (rc = hp_grad_bias(gc, dtype, tc.grad_output, t.grad_bias, t.wgrad32 != 0, stream)))
+        return rc;
     }
     if ((rc = hp_csr_zero(gc, cnt, stream))) return rc;
     const bool bwd3 = c.bwd == HpChunk::BWD3, bwd2 = c.bwd == HpChunk::BWD2;   // (the plan checked this chunk's slots)

@@ -14,6 +14,9 @@ int hp_pack_fwd_weights(const Geom &g, const HpDims &hd, int dtype, const void *
                         int2 *ctab, hipStream_t stream);
 int hp_pack_bwd_weights(const Geom &g, const HpDims &hd, int dtype, const void *w, bool f32src, void *wpb,
                         int4 *btab, hipStream_t stream);
+// the inverse layout pass for a channels-last grad_output (Tensors::out_cl): dst[b][o][pix] = src[b][pix][o], 16-bit elements,
+// O a multiple of 8 -- the copy of one chunk the backward kernels read (HpBwdLayout::off_go16)
+int hp_nhwc_to_nchw(const Geom &g, const void *src, void *dst, hipStream_t stream);
 // the bf16 copy of an fp32 grad_output (Tensors::io32), `n` elements
 int hp_f32_to_bf16(const float *src, void *dst, int64_t n, hipStream_t stream);
 // gw32 != nullptr (calls cut into batch chunks): running fp32 sum; grad_weight is written by the last chunk
@@ -25,13 +28,24 @@ int hp_reduce_grad_weight(const Geom &g, const HpDims &hd, int ranges, int dtype
 int hp_grad_bias(const Geom &g, int dtype, const void *grad_output, void *grad_bias, bool wgrad32,
                  hipStream_t stream);
 
+// the same sum, bit for bit, from a channels-last grad_output [B, spatial..., C_out] (Tensors::out_cl, calls cut into batch chunks)
+int hp_grad_bias_cl(const Geom &g, int dtype, const void *grad_output, void *grad_bias, bool wgrad32,
+                    hipStream_t stream);
+
 // hp_fwd.hip
 int hp_forward_launch(const Geom &g, const HpDims &hd, int dtype, const Tensors &t, const void *xt,
                       const void *wpf, const int2 *ctab, hipStream_t stream);
 
+// channels-last output (t.out_cl): instances in hp_fwd_cl.hip, reached through hp_forward_launch
+int hp_forward_launch_cl(const Geom &g, const HpDims &hd, int dtype, const Tensors &t, const void *xt,
+                         const void *wpf, const int2 *ctab, hipStream_t stream);
+
 // hp_fwd2.hip: the same contraction with quad-contiguous (line-wide) gathers
 int hp_forward2_launch(const Geom &g, const HpDims &hd, int dtype, const Tensors &t, const void *xt,
                        const void *wpf, const int2 *ctab, hipStream_t stream);
+
+int hp_forward2_launch_cl(const Geom &g, const HpDims &hd, int dtype, const Tensors &t, const void *xt,
+                          const void *wpf, const int2 *ctab, hipStream_t stream);   // hp_fwd2_cl.hip
 
 // hp_bwd.hip: GEMM-1 + coordinate gradients + grad_col + GEMM-2, one gather pass
 int hp_backward_launch(const Geom &g, const HpDims &hd, int dtype, const Tensors &t, const void *xt,
@@ -70,6 +84,10 @@ int hp_csr_build(const Geom &g, int dtype, const Tensors &t, int *cnt, int *rowp
                  hipStream_t stream);
 int hp_col2im(const Geom &g, const HpDims &hd, int dtype, const Tensors &t, const void *gcol,
               const int *rowptr, const void *entries, hipStream_t stream);
+// channels-last grad_input (t.gi_cl): instances in hp_col2im_cl.hip, reached through hp_col2im / hp_col2im2 (pass 2)
+int hp_col2im_cl(const Geom &g, const HpDims &hd, int dtype, const Tensors &t, const void *gcol,
+                 const int *rowptr, const void *entries, hipStream_t stream);
+int hp_col2im_combine_cl(const Geom &g, const HpDims &hd, int dtype, const Tensors &t, const void *sums, hipStream_t stream);
 // two-pass gather: per-anchor partial sums (every grad_col row read once) -> stencil + transpose
 size_t hp_col2im_sums_bytes(const Geom &g, const HpDims &hd, int dtype);
 int hp_col2im2(const Geom &g, const HpDims &hd, int dtype, const Tensors &t, const void *gcol,

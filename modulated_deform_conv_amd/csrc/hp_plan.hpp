@@ -18,7 +18,9 @@ struct HpChunk {
 struct HpFwdLayout { size_t off_xt, off_w, off_tab, total; };
 struct HpBwdLayout {
   size_t off_xt, off_w, off_tab, off_gcol, off_col, off_part, off_gw32, off_cnt, off_rowptr, off_entries, off_sums, off_sort;
-  size_t off_go16;   // HpPlan::io32: the bf16 copy of one chunk's fp32 grad_output (behind the slots of the bf16 call)
+  // HpPlan::io32: the bf16 copy of one chunk's fp32 grad_output (behind the slots of the bf16 call); HpPlan::out_cl: the
+  // [B, C_out, spatial] copy of one chunk's channels-last grad_output (the two modes exclude each other by dtype)
+  size_t off_go16;
   size_t total;
 };
 
@@ -39,10 +41,21 @@ struct HpPlan {
   // weight gradients, whose layout passes read fp32 input and weights, whose forward and grad_input gather store fp32, and
   // whose backward converts each chunk's grad_output into off_go16 -- the one slot the mode adds
   bool io32;
+  // Result layouts (MDCONV_FLAG_OUTPUT_CHANNELS_LAST / _GRAD_INPUT_CHANNELS_LAST): `out_cl` -- the forward stores `output`
+  // as [B, spatial..., C_out] (the store policy of hp_fwd / hp_fwd2), the backward brings each chunk's channels-last
+  // grad_output into off_go16 (hp_nhwc_to_nchw), the one slot the flag adds, and sums grad_bias from that copy; `gi_cl` --
+  // the gather stores grad_input as [B, spatial..., C_in] (backward with grad_input only; no bytes).  Neither changes the
+  // geometry, the chunks or their kernels: a channels-last tensor is batch-major too.
+  // `layout_refusal`: null, or the rule a requested layout breaks (the text of mdconv_result_layout_supported's answer 0)
+  bool out_cl, gi_cl;
+  const char *layout_refusal;
 };
 // false: the family does not take the call.  `skip` never changes the answer, the geometry, the chunks or their kernels;
 // nor does `io32` (with dtype MDCONV_BF16: the call's tensors are fp32, Tensors::io32).
-bool hp_plan(const Geom &g, int dtype, bool backward, HpPlan *p, Skip skip = Skip(), bool io32 = false);
+// `out_cl` / `gi_cl`: the result layouts the call asks for (16-bit tensors only); recorded, sized and judged here --
+// HpPlan::layout_refusal -- so that the query, the sizing and the execution cannot drift apart.
+bool hp_plan(const Geom &g, int dtype, bool backward, HpPlan *p, Skip skip = Skip(), bool io32 = false, bool out_cl = false,
+             bool gi_cl = false);
 int hp_forward(int dtype, const HpPlan &p, const Tensors &t, void *ws, hipStream_t stream);
 int hp_backward(int dtype, const HpPlan &p, const Tensors &t, void *ws, hipStream_t stream);
 

@@ -130,6 +130,51 @@ __global__ __launch_bounds__(256) void hp_nchw_to_nhwc_vec_kernel(Geom g, int Cp
   }
 }
 
+// The inverse pass, for a channels-last grad_output (MDCONV_FLAG_OUTPUT_CHANNELS_LAST): dst[b][o][q] = src[b][q][o], 16-bit
+// words, O a multiple of 8 -- the NCHW copy of one chunk that hp_bwd* / hp_gemm2 read.  64 pixels x 64 channels per workgroup
+// through LDS: a thread loads the 8 channels of one pixel (16 bytes; `vsrc` = 0, a source that is not 16-byte aligned: word by
+// word), the tile is kept channel-major, and a thread stores 8 pixels of one channel -- 16 bytes where the row length S is a
+// multiple of 8 and the destination is 16-byte aligned (`vdst`), else word by word.
+__global__ __launch_bounds__(256) void hp_nhwc_to_nchw_kernel(int O, int S, int vsrc, int vdst,
+                                                              const unsigned short *__restrict__ src,
+                                                              unsigned short *__restrict__ dst) {
+  constexpr int P = 72;   // pitch: rows of 144 bytes, 16-byte aligned
+  __shared__ __attribute__((aligned(16))) unsigned short t[64 * P];
+  const int b = blockIdx.z, o0 = blockIdx.y * 64, q0 = blockIdx.x * 64;
+  for (int item = threadIdx.x; item < 64 * 8; item += 256) {
+    const int ql = item >> 3, oct = item & 7;
+    const int q = q0 + ql, o = o0 + oct * 8;
+    unsigned short w[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (q < S && o < O) {   // (O is a multiple of 8: whole octets)
+      const unsigned short *p = src + ((size_t)b * S + q) * O + o;
+      if (vsrc) {
+        const U4 v = *reinterpret_cast<const U4 *>(p);
+        w[0] = (unsigned short)v.x; w[1] = (unsigned short)(v.x >> 16); w[2] = (unsigned short)v.y; w[3] = (unsigned short)(v.y >> 16);
+        w[4] = (unsigned short)v.z; w[5] = (unsigned short)(v.z >> 16); w[6] = (unsigned short)v.w; w[7] = (unsigned short)(v.w >> 16);
+      } else {
+#pragma unroll
+        for (int k = 0; k < 8; ++k) w[k] = o + k < O ? p[k] : (unsigned short)0;
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < 8; ++k) t[(oct * 8 + k) * P + ql] = w[k];
+  }
+  __syncthreads();
+  for (int item = threadIdx.x; item < 64 * 8; item += 256) {
+    const int ol = item >> 3, q8 = item & 7;
+    const int o = o0 + ol, q = q0 + q8 * 8;
+    if (o >= O || q >= S) continue;
+    unsigned short *p = dst + ((size_t)b * O + o) * S + q;
+    const unsigned short *tp = t + ol * P + q8 * 8;
+    if (vdst) {   // S % 8 == 0: the whole octet is inside the row
+      *reinterpret_cast<U4 *>(p) = *reinterpret_cast<const U4 *>(tp);
+    } else {
+      const int n = S - q < 8 ? S - q : 8;
+      for (int k = 0; k < n; ++k) p[k] = tp[k];
+    }
+  }
+}
+
 // forward A operand: wpf[tap][chunk][oblk][lane][8] = W[o = oblk*32 + (lane&31)]
 //                                                      [c = chunk*16 + 8*(lane>>5) + j][tap]
 // dense block-diagonal over conv groups (0 where o and c belong to different groups, or padding).
@@ -338,6 +383,50 @@ __global__ __launch_bounds__(kBiasThreads) void hp_grad_bias_kernel(Geom g, cons
   if (tid == 0) OUT::stf(gb + o, g.acc_w ? OUT::ldf(gb + o) + red[0] : red[0]);
 }
 
+// grad_bias of a call with a CHANNELS-LAST grad_output that is cut into batch chunks (MDCONV_FLAG_OUTPUT_CHANNELS_LAST; a call
+// of one chunk sums its [B, C_out, spatial] copy with the kernel above): go[b][pix][o], whole batch, one rounding.  The same
+// sum term by term -- the thread that takes an element, the partial it adds it to, the order of the adds and the tree are those
+// of the kernel above reading a 16-byte aligned [B, C_out, spatial] tensor -- so the result is bit for bit the unflagged call's,
+// whatever the chunks; the loads are single elements, O apart.
+template <typename T, typename OUT = T>
+__global__ __launch_bounds__(kBiasThreads) void hp_grad_bias_cl_kernel(Geom g, const typename T::Raw *__restrict__ go,
+                                                                       typename OUT::Raw *__restrict__ gb) {
+  __shared__ float red[kBiasThreads];
+  const int o = blockIdx.x, tid = threadIdx.x;
+  float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
+  for (int b = 0; b < g.B; ++b) {
+    const typename T::Raw *src = go + (int64_t)b * g.S_o * g.O + o;   // element q of the row: src[q * O]
+    const int64_t row0 = ((int64_t)b * g.O + o) * g.S_o;               // where the row starts in the [B, C_out, spatial] tensor
+    int head = (int)((8 - (row0 & 7)) & 7);
+    if (head > g.S_o) head = g.S_o;
+    const int nvec = (g.S_o - head) >> 3;
+    const int tail0 = head + nvec * 8;
+    auto ld = [&](int q) { return T::ldf(src + (int64_t)q * g.O); };
+    auto sum8_at = [&](int i) {   // sum8 of vector i
+      const int q = head + i * 8;
+      return ((ld(q) + ld(q + 1)) + (ld(q + 2) + ld(q + 3))) + ((ld(q + 4) + ld(q + 5)) + (ld(q + 6) + ld(q + 7)));
+    };
+    if (tid < head) s2 += ld(tid);
+    if (tid < g.S_o - tail0) s3 += ld(tail0 + tid);
+    int i = tid;
+    for (; i + 3 * kBiasThreads < nvec; i += 4 * kBiasThreads) {
+      const float a0 = sum8_at(i), a1 = sum8_at(i + kBiasThreads), a2 = sum8_at(i + 2 * kBiasThreads), a3 = sum8_at(i + 3 * kBiasThreads);
+      s0 += a0;
+      s1 += a1;
+      s2 += a2;
+      s3 += a3;
+    }
+    for (; i < nvec; i += kBiasThreads) s0 += sum8_at(i);
+  }
+  red[tid] = (s0 + s1) + (s2 + s3);
+  __syncthreads();
+  for (int d = kBiasThreads / 2; d > 0; d >>= 1) {
+    if (tid < d) red[tid] += red[tid + d];
+    __syncthreads();
+  }
+  if (tid == 0) OUT::stf(gb + o, g.acc_w ? OUT::ldf(gb + o) + red[0] : red[0]);
+}
+
 // dst[i] = bf16(src[i]): the grad_output of an fp32 call on the bf16 kernels (Tensors::io32), which the backward kernels and
 // GEMM-2 read as 16-bit NCHW.  VEC (a 16-byte aligned source): 16-byte loads, 8-byte stores, the n % 4 last elements one by one.
 template <bool VEC>
@@ -363,6 +452,15 @@ int hp_f32_to_bf16(const float *src, void *dst, int64_t n, hipStream_t stream) {
     hipLaunchKernelGGL(hp_f32_to_bf16_kernel<false>, dim3(grid_for(n, 16384)), dim3(256), 0, stream, src,
                        (unsigned short *)dst, n);
   return check_launch("hp_f32_to_bf16");
+}
+
+int hp_nhwc_to_nchw(const Geom &g, const void *src, void *dst, hipStream_t stream) {
+  const dim3 grid((g.S_o + 63) / 64, (g.O + 63) / 64, g.B);
+  const int vsrc = (reinterpret_cast<uintptr_t>(src) & 15) == 0 && g.O % 8 == 0;
+  const int vdst = (reinterpret_cast<uintptr_t>(dst) & 15) == 0 && g.S_o % 8 == 0;
+  hipLaunchKernelGGL(hp_nhwc_to_nchw_kernel, grid, dim3(256), 0, stream, g.O, g.S_o, vsrc, vdst, (const unsigned short *)src,
+                     (unsigned short *)dst);
+  return check_launch("hp_nhwc_to_nchw");
 }
 
 // X = the source's element: 16-bit words, or fp32 (the vector kernels then need a 16-byte aligned source)
@@ -440,6 +538,23 @@ int hp_grad_bias(const Geom &g, int dtype, const void *grad_output, void *grad_b
     hipLaunchKernelGGL((hp_grad_bias_kernel<BF16>), dim3(g.O), dim3(kBiasThreads), 0, stream, g,
                        (const __bf16 *)grad_output, (__bf16 *)grad_bias);
   return check_launch("hp_grad_bias");
+}
+
+int hp_grad_bias_cl(const Geom &g, int dtype, const void *grad_output, void *grad_bias, bool wgrad32,
+                    hipStream_t stream) {
+  if (wgrad32 && dtype == MDCONV_F16)
+    hipLaunchKernelGGL((hp_grad_bias_cl_kernel<F16, F32IO>), dim3(g.O), dim3(kBiasThreads), 0, stream, g,
+                       (const _Float16 *)grad_output, (float *)grad_bias);
+  else if (wgrad32)
+    hipLaunchKernelGGL((hp_grad_bias_cl_kernel<BF16, F32IO>), dim3(g.O), dim3(kBiasThreads), 0, stream, g,
+                       (const __bf16 *)grad_output, (float *)grad_bias);
+  else if (dtype == MDCONV_F16)
+    hipLaunchKernelGGL((hp_grad_bias_cl_kernel<F16>), dim3(g.O), dim3(kBiasThreads), 0, stream, g,
+                       (const _Float16 *)grad_output, (_Float16 *)grad_bias);
+  else
+    hipLaunchKernelGGL((hp_grad_bias_cl_kernel<BF16>), dim3(g.O), dim3(kBiasThreads), 0, stream, g,
+                       (const __bf16 *)grad_output, (__bf16 *)grad_bias);
+  return check_launch("hp_grad_bias_cl");
 }
 
 }  // namespace mdconv

@@ -70,9 +70,10 @@ static int desc_ndim(const mdconv_desc *d) { return d->ndim & ~MDCONV_DESC_V2; }
 
 // Call modes of one call: from the descriptor (ABI v2) or from the v1 setters of the calling thread / process.
 // math_bf16: MDCONV_FLAG_MATH_BF16 -- the fp32 call may run on the bf16 kernels (plan_call decides whether it does)
-struct Modes { int accumulate, input_layout, path, deterministic, math_bf16; Skip skip; };
+// out_cl / gi_cl: MDCONV_FLAG_OUTPUT_CHANNELS_LAST / MDCONV_FLAG_GRAD_INPUT_CHANNELS_LAST (16-bit tensors only)
+struct Modes { int accumulate, input_layout, path, deterministic, math_bf16; Skip skip; int out_cl, gi_cl; };
 static int call_modes(const mdconv_desc *d, Modes *m) {
-  m->deterministic = m->math_bf16 = 0;   // v1 descriptors end before the flag word: they never request a flag
+  m->deterministic = m->math_bf16 = m->out_cl = m->gi_cl = 0;   // v1 descriptors end before the flag word: they never request a flag
   m->skip = Skip();
   if (!(d->ndim & MDCONV_DESC_V2)) {
     m->accumulate = g_accumulate;
@@ -92,13 +93,25 @@ static int call_modes(const mdconv_desc *d, Modes *m) {
       set_error("mdconv_desc.reserved must be 0");
       return MDCONV_EINVAL;
     }
-  const int known = MDCONV_FLAG_DETERMINISTIC | MDCONV_FLAG_NO_GRAD_INPUT | MDCONV_FLAG_NO_GRAD_WEIGHT | MDCONV_FLAG_MATH_BF16;
+  const int layouts = MDCONV_FLAG_OUTPUT_CHANNELS_LAST | MDCONV_FLAG_GRAD_INPUT_CHANNELS_LAST;
+  const int known = MDCONV_FLAG_DETERMINISTIC | MDCONV_FLAG_NO_GRAD_INPUT | MDCONV_FLAG_NO_GRAD_WEIGHT | MDCONV_FLAG_MATH_BF16 | layouts;
   if (d->reserved[4] & ~known) {
     set_error("unknown bits 0x%x in the flags word of the descriptor (mdconv_desc.reserved[4]); the flags are "
-              "MDCONV_FLAG_DETERMINISTIC (1), MDCONV_FLAG_NO_GRAD_INPUT (4), MDCONV_FLAG_NO_GRAD_WEIGHT (8) and "
-              "MDCONV_FLAG_MATH_BF16 (32)",
+              "MDCONV_FLAG_DETERMINISTIC (1), MDCONV_FLAG_NO_GRAD_INPUT (4), MDCONV_FLAG_NO_GRAD_WEIGHT (8), "
+              "MDCONV_FLAG_MATH_BF16 (32), MDCONV_FLAG_OUTPUT_CHANNELS_LAST (64) and MDCONV_FLAG_GRAD_INPUT_CHANNELS_LAST (128)",
               (unsigned)(d->reserved[4] & ~known));
     return MDCONV_EINVAL;
+  }
+  if (d->reserved[4] & layouts) {
+    const int dt = d->dtype & ~(MDCONV_SAMPLING_F32 | MDCONV_WGRAD_F32);   // (fill_geom has validated the dtype word)
+    if (dt != MDCONV_F16 && dt != MDCONV_BF16) {
+      set_error("%s needs fp16 or bf16 tensors, dtype is %s (fp32 tensors under MDCONV_FLAG_MATH_BF16 included)",
+                (d->reserved[4] & MDCONV_FLAG_OUTPUT_CHANNELS_LAST) ? "MDCONV_FLAG_OUTPUT_CHANNELS_LAST" : "MDCONV_FLAG_GRAD_INPUT_CHANNELS_LAST",
+                dt == MDCONV_F64 ? "MDCONV_F64" : "MDCONV_F32");
+      return MDCONV_EINVAL;
+    }
+    m->out_cl = (d->reserved[4] & MDCONV_FLAG_OUTPUT_CHANNELS_LAST) ? 1 : 0;
+    m->gi_cl = (d->reserved[4] & MDCONV_FLAG_GRAD_INPUT_CHANNELS_LAST) ? 1 : 0;
   }
   if (d->reserved[4] & MDCONV_FLAG_MATH_BF16) {
     const int dt = d->dtype & ~(MDCONV_SAMPLING_F32 | MDCONV_WGRAD_F32);   // (fill_geom has validated the dtype word)
@@ -261,7 +274,7 @@ enum Route {
   ROUTE_DIRECT_SAMP32    // ... through the fp32 copies of a call with fp32 offsets / masks (`s32`)
 };
 // A call can be refused; `route` and the byte counts then still say where it would have gone (the sizing query reports them).
-enum Refusal { REFUSE_NONE, REFUSE_CHANNELS_LAST, REFUSE_PATH_MFMA, REFUSE_DETERMINISTIC };
+enum Refusal { REFUSE_NONE, REFUSE_CHANNELS_LAST, REFUSE_PATH_MFMA, REFUSE_DETERMINISTIC, REFUSE_RESULT_LAYOUT };
 struct CallPlan {
   Route route;
   Refusal refused;
@@ -273,6 +286,7 @@ struct CallPlan {
   D16Plan d16;       // ROUTE_DIRECT_16
   Skip skip;         // backward: gradients the call leaves out
   size_t scratch_gi; // ROUTE_DIRECT with skip.input: bytes of the grad_input scratch (the route's whole workspace)
+  const char *layout_reason;   // REFUSE_RESULT_LAYOUT: the rule the flagged call breaks
 };
 static bool route_is_direct(Route r) { return r == ROUTE_DIRECT || r == ROUTE_DIRECT_16 || r == ROUTE_DIRECT_SAMP32; }
 
@@ -289,8 +303,10 @@ static bool route_is_direct(Route r) { return r == ROUTE_DIRECT || r == ROUTE_DI
 // The bf16 kernels pad channels to blocks of 32, and with the rule off such layers did not gain: DCN2d 4 -> 4 at 8 x 8 ran 0.121 ms
 // against 0.089 ms exact, MDCN2d 8 -> 8 at 56 x 56, B = 8 0.224 against 0.229 (inside the +-3 % spread), 4 -> 4 there 0.222 against 0.238.
 // Narrow CONV GROUPS of a wide layer are taken (256 -> 256 in 32 groups of 8, 56 x 56, B = 8: 0.33 against 0.97 ms).
-static void plan_call(const Geom &g, int dt, int s32, int wg32, int path, bool backward, CallPlan *cp, Skip skip = Skip(),
-                      int mb16 = 0) {
+// `out_cl` / `gi_cl` (the result-layout flags) never change the route either: hp_plan records them, and plan_call below refuses
+// the flagged call the route does not honour.
+static void plan_route(const Geom &g, int dt, int s32, int wg32, int path, bool backward, CallPlan *cp, Skip skip, int mb16,
+                       bool out_cl, bool gi_cl) {
   const bool half = dt == MDCONV_F16 || dt == MDCONV_BF16;
   if (!backward) skip = Skip();
   cp->skip = skip;
@@ -302,7 +318,7 @@ static void plan_call(const Geom &g, int dt, int s32, int wg32, int path, bool b
     cp->bytes = cp->reported = cp->hp.total;
     return;
   }
-  const bool hp = path != MDCONV_PATH_DIRECT && hp_plan(g, dt, backward, &cp->hp, skip);
+  const bool hp = path != MDCONV_PATH_DIRECT && hp_plan(g, dt, backward, &cp->hp, skip, false, out_cl, gi_cl);
   cp->refused = g.in_cl && !(hp && g.C % 32 == 0) ? REFUSE_CHANNELS_LAST : REFUSE_NONE;
   const size_t hp_bytes = hp ? cp->hp.total : 0;
   // 16-bit forwards of a few tiles run faster on the fp32 kernels (HpPlan::forward_preferred)
@@ -353,6 +369,25 @@ static void plan_call(const Geom &g, int dt, int s32, int wg32, int path, bool b
   if (path == MDCONV_PATH_MFMA) cp->refused = REFUSE_PATH_MFMA;
   else if (g.det) cp->refused = REFUSE_DETERMINISTIC;   // the shape-generic backward sums in arrival order
 }
+// The plan of a call: its route (plan_route), and the verdict on the result-layout flags -- honoured exactly where the native
+// 16-bit plan takes this direction and the rows of every flagged tensor are whole 16-byte pieces (hp_plan's layout_refusal);
+// any other flagged call is refused before anything is launched.  grad_input's flag: backward with grad_input only.
+static void plan_call(const Geom &g, int dt, int s32, int wg32, int path, bool backward, CallPlan *cp, Skip skip = Skip(),
+                      int mb16 = 0, bool out_cl = false, bool gi_cl = false) {
+  cp->layout_reason = nullptr;
+  gi_cl = gi_cl && backward && !skip.input;
+  plan_route(g, dt, s32, wg32, path, backward, cp, skip, mb16, out_cl, gi_cl);
+  if (cp->refused || !(out_cl || gi_cl)) return;
+  if (cp->route != ROUTE_HP)
+    cp->layout_reason = "the call does not run on the native 16-bit kernels (mdconv_last_kernels() would not be MDCONV_KERNELS_HP)";
+  else
+    cp->layout_reason = cp->hp.layout_refusal;
+  if (cp->layout_reason) cp->refused = REFUSE_RESULT_LAYOUT;
+}
+static void set_layout_refusal(const CallPlan &cp, bool backward) {
+  set_error("result layouts (MDCONV_FLAG_OUTPUT_CHANNELS_LAST / MDCONV_FLAG_GRAD_INPUT_CHANNELS_LAST): this %s cannot honour "
+            "the flags -- %s", backward ? "backward" : "forward", cp.layout_reason);
+}
 // why a backward ends on the shape-generic kernels (the text of the deterministic-mode refusal)
 static const char *direct_reason(const Geom &g, int dt, int path) {
   if (path == MDCONV_PATH_DIRECT) return "the call selects MDCONV_PATH_DIRECT";
@@ -371,11 +406,13 @@ static void set_det_refusal(const Geom &g, int dt, int path) {
 }
 
 // the error of a refused call (nothing has been launched)
-static int refuse(const CallPlan &cp, const Geom &g, int dt, int path) {
+static int refuse(const CallPlan &cp, const Geom &g, int dt, int path, bool backward) {
   if (cp.refused == REFUSE_CHANNELS_LAST)
     set_error("channels-last input is only supported by the native 16-bit kernels with C_in a multiple of 32");
   else if (cp.refused == REFUSE_PATH_MFMA)
     set_error("MDCONV_PATH=mfma but this shape/dtype is not supported by the MFMA kernels");
+  else if (cp.refused == REFUSE_RESULT_LAYOUT)
+    set_layout_refusal(cp, backward);
   else
     set_det_refusal(g, dt, path);
   return MDCONV_EUNSUPPORTED;
@@ -418,8 +455,8 @@ static int run_forward(const mdconv_desc *d, int nd, int modulated, Tensors t, v
   t.samp32 = s32;
   g.in_cl = md.input_layout == MDCONV_LAYOUT_CHANNELS_LAST ? 1 : 0;
   CallPlan cp;
-  plan_call(g, dt, s32, 0, path, false, &cp, Skip(), md.math_bf16);
-  if (cp.refused) return refuse(cp, g, dt, path);
+  plan_call(g, dt, s32, 0, path, false, &cp, Skip(), md.math_bf16, md.out_cl != 0, false);
+  if (cp.refused) return refuse(cp, g, dt, path, false);
   switch (cp.route) {
     case ROUTE_HP_F32:   // the bf16 kernels on the caller's fp32 tensors
       if ((rc = check_ws(ws, ws_bytes, cp.bytes))) return rc;
@@ -483,8 +520,8 @@ static int run_backward(const mdconv_desc *d, int nd, int modulated, Tensors t, 
   g.in_cl = md.input_layout == MDCONV_LAYOUT_CHANNELS_LAST ? 1 : 0;
   g.det = md.deterministic;
   CallPlan cp;
-  plan_call(g, dt, s32, t.wgrad32, path, true, &cp, skip, md.math_bf16);
-  if (cp.refused) return refuse(cp, g, dt, path);
+  plan_call(g, dt, s32, t.wgrad32, path, true, &cp, skip, md.math_bf16, md.out_cl != 0, md.gi_cl != 0);
+  if (cp.refused) return refuse(cp, g, dt, path, true);
   // the workspace check; without weight gradients there is nothing to wait for, so the weights-ready event goes in front
   // of the call's first kernel
   auto ready = [&]() -> int {
@@ -611,8 +648,23 @@ size_t mdconv_workspace_bytes(const mdconv_desc *d, int backward) {
   g.in_cl = md.input_layout == MDCONV_LAYOUT_CHANNELS_LAST ? 1 : 0;   // (the plan of a channels-last call, where the caller says so)
   g.det = backward ? md.deterministic : 0;   // the list sort's scratch (backward on the matrix-core kernels only)
   CallPlan cp;
-  plan_call(g, base_dtype(d), sampling_f32(d), wgrad_f32(d, backward != 0), md.path, backward != 0, &cp, md.skip, md.math_bf16);
+  plan_call(g, base_dtype(d), sampling_f32(d), wgrad_f32(d, backward != 0), md.path, backward != 0, &cp, md.skip, md.math_bf16,
+            md.out_cl != 0, md.gi_cl != 0);
   return cp.reported;
+}
+
+int mdconv_result_layout_supported(const mdconv_desc *d, int backward) {
+  Geom g;
+  Modes md;
+  if (fill_geom(d, &g) || call_modes(d, &md)) return 0;
+  g.in_cl = md.input_layout == MDCONV_LAYOUT_CHANNELS_LAST ? 1 : 0;
+  g.det = backward ? md.deterministic : 0;
+  CallPlan cp;
+  plan_call(g, base_dtype(d), sampling_f32(d), wgrad_f32(d, backward != 0), md.path, backward != 0, &cp, md.skip, md.math_bf16,
+            md.out_cl != 0, md.gi_cl != 0);
+  if (cp.refused != REFUSE_RESULT_LAYOUT) return 1;
+  set_layout_refusal(cp, backward != 0);   // the rule, for mdconv_last_error()
+  return 0;
 }
 
 int mdconv_math_bf16_used(const mdconv_desc *d, int backward) {

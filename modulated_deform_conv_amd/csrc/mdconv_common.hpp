@@ -433,6 +433,10 @@ struct Tensors {
   // 1 = an fp32 call on the bf16 kernels (MDCONV_FLAG_MATH_BF16; implies samp32 and wgrad32): input, weight, bias,
   // grad_output, output and grad_input are fp32 buffers, the kernels' `dtype` is MDCONV_BF16
   int io32;
+  // result layouts of a call on the native 16-bit kernels (MDCONV_FLAG_OUTPUT_CHANNELS_LAST / _GRAD_INPUT_CHANNELS_LAST; set
+  // from the plan, HpPlan::out_cl / gi_cl): 1 = `output` (forward) / `grad_output` (backward) is [B, spatial..., C_out];
+  // 1 = `grad_input` is [B, spatial..., C_in]
+  int out_cl, gi_cl;
 };
 // bytes of one offset / mask element of a call
 inline size_t samp_bytes(int dtype, const Tensors &t) {

@@ -67,6 +67,10 @@ def _make_function(nd, modulated, name):
         return tuple(weight.shape[2:]) + ctx.stride + ctx.padding + ctx.dilation + \
             (ctx.groups, ctx.deformable_groups, ctx.in_step, ctx.with_bias)
 
+    def _split_geo(geo):
+        """_geometry's flat tuple as (kernel, stride, padding, dilation, groups, deformable_groups, in_step, with_bias)"""
+        return tuple(geo[a * nd:(a + 1) * nd] for a in range(4)) + geo[4 * nd:]
+
     def _forward(ctx, input, offset, mask, weight, bias):
         needs_grad = weight.requires_grad or offset.requires_grad or input.requires_grad or \
             (modulated and mask.requires_grad)
@@ -92,13 +96,20 @@ def _make_function(nd, modulated, name):
         # fp32 tensors, bf16 matrix math (_capi.fp32_math): the mode of this forward is the mode of its backward, whatever
         # thread runs that and whatever the global says by then
         ctx.fp32_math = _capi.fp32_math_mode()
+        # channels-last results (_capi.channels_last_results): likewise recorded here and entered again in backward
+        ctx.cl_results = _capi.channels_last_results_mode()
         if needs_grad:
             saved = (input, offset, mask, weight, bias) if modulated else (input, offset, weight, bias)
             ctx.save_for_backward(*saved)
         geo = _geometry(ctx, weight)
         if returns_tensors:
             return fwd(input, weight, bias, offset, mask, *geo)
-        output = input.new_empty(_output_shape(input, weight, ctx.stride, ctx.padding, ctx.dilation))
+        # (inside the mode: channels-last when `input` is and the forward stores that layout itself)
+        fmt = torch.contiguous_format
+        if ctx.cl_results and MDCONV_CUDA.channels_last_results_supported(nd, modulated, input, weight, *_split_geo(geo), False):
+            fmt = torch.channels_last if nd == 2 else torch.channels_last_3d
+        output = torch.empty(_output_shape(input, weight, ctx.stride, ctx.padding, ctx.dilation), dtype=input.dtype,
+                             device=input.device, memory_format=fmt)
         if modulated:
             fwd(input, weight, bias, offset, mask, output, *geo)
         else:
@@ -106,7 +117,8 @@ def _make_function(nd, modulated, name):
         return output
 
     def _backward(ctx, grad_output):
-        grad_output = grad_output.contiguous()
+        if not (ctx.cl_results and MDCONV_CUDA._cl_result(grad_output)):   # (inside the mode: channels-last as it is)
+            grad_output = grad_output.contiguous()
         if not grad_output.is_cuda:
             raise NotImplementedError
         if modulated:
@@ -125,20 +137,26 @@ def _make_function(nd, modulated, name):
         skip_weight = not (need[iw] or (ctx.with_bias and need[iw + 1]))
         skip = _capi.skip_grads(input=skip_input, weight=skip_weight)
         math = _capi.fp32_math(ctx.fp32_math)
+        cl = _capi.channels_last_results(ctx.cl_results)
         if returns_tensors:
             # (autograd runs this on its own thread: the modes recorded in forward are entered here)
-            with _capi.weight_grads_f32(ctx.wgrad32), skip, math:
+            with _capi.weight_grads_f32(ctx.wgrad32), skip, math, cl:
                 grad_input, grad_offset, grad_mask, grad_weight, grad_bias = bwd(
                     input, weight, bias, offset, mask, grad_output, *geo)
         else:
             # the reference wrapper zero-fills and the entry points add (:53-56); here the buffers
             # are fresh, so the library is asked to write them instead (mdconv_set_accumulate)
-            grad_input = None if skip_input else torch.empty_like(input, memory_format=torch.contiguous_format)
+            # (inside the mode: channels-last when the saved input is and the backward stores that layout itself)
+            with cl:
+                gi_cl = not skip_input and MDCONV_CUDA.channels_last_results_supported(
+                    nd, modulated, input, weight, *_split_geo(geo), True)
+            gi_fmt = (torch.channels_last if nd == 2 else torch.channels_last_3d) if gi_cl else torch.contiguous_format
+            grad_input = None if skip_input else torch.empty_like(input, memory_format=gi_fmt)
             grad_offset = torch.empty_like(offset)
             # one flat buffer: one in-place all-reduce (distributed.py); fp32 for fp32 weight gradients -- the entry points
             # take the mode from the buffers' dtype
             grad_weight, grad_bias = (None, None) if skip_weight else fused_grad_buffers(weight, bias, wdt)
-            with _capi.overwrite_grads(), _capi.weight_grads_f32(ctx.wgrad32), skip, math:
+            with _capi.overwrite_grads(), _capi.weight_grads_f32(ctx.wgrad32), skip, math, cl:
                 if modulated:
                     grad_mask = torch.empty_like(mask)
                     bwd(input, weight, bias, offset, mask, grad_input, grad_weight, grad_bias,
@@ -210,14 +228,24 @@ class _DeformConvNd(nn.Module):
     summing them; INTEGRATION.md, Reproducibility).  Shapes whose backward runs on the shape-generic kernels -- fp64 tensors,
     C_in or C_out below 16 on images of a few hundred pixels (e.g. 4 -> 4 channels at 8 x 8) -- scatter with floating-point
     atomics and refuse the mode: their backward raises ``RuntimeError`` (with ``warn_only=True``: one ``UserWarning``, then
-    runs as usual); their forward is deterministic and runs."""
+    runs as usual); their forward is deterministic and runs.
+
+    ``channels_last_results`` (keyword only): ``False`` (default) returns a contiguous output and ``x.grad``, whatever the
+    layout of ``x``.  ``True``: the layer runs inside ``_capi.channels_last_results`` -- with a channels-last fp16 / bf16
+    ``x`` (a ``model.to(memory_format=torch.channels_last)`` under autocast) the output and ``x.grad`` are channels-last
+    where the native 16-bit kernels store that layout themselves, and a channels-last ``grad_output`` is taken as it is
+    ("dtypes, AMP, memory formats").  Same values either way."""
     _nd = 2
     _modulated = False
     _op = None
 
     def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, dilation=1,
-                 groups=1, deformable_groups=1, bias=False, in_step=64, *, sampling_dtype=None, weight_grad_dtype=None):
+                 groups=1, deformable_groups=1, bias=False, in_step=64, *, sampling_dtype=None, weight_grad_dtype=None,
+                 channels_last_results=False):
         super().__init__()
+        if not isinstance(channels_last_results, bool):
+            raise ValueError("channels_last_results must be True or False, got %r" % (channels_last_results,))
+        self.channels_last_results = channels_last_results
         if sampling_dtype not in (None, torch.float32):
             raise ValueError("sampling_dtype must be None or torch.float32, got %s" % (sampling_dtype,))
         if weight_grad_dtype not in (None, torch.float32):
@@ -251,11 +279,21 @@ class _DeformConvNd(nn.Module):
     def _fp32_sampling(self):
         return self.sampling_dtype is not None and torch.is_autocast_enabled("cuda")
 
+    @contextlib.contextmanager
+    def _call_modes(self):
+        """The thread-local modes the module's keywords ask for, around one call of the Function."""
+        with contextlib.ExitStack() as stack:
+            if self.weight_grad_dtype is not None:
+                stack.enter_context(_capi.weight_grads_f32())
+            if self.channels_last_results:
+                stack.enter_context(_capi.channels_last_results())
+            yield
+
     def _conv(self, op, x, offset, mask=None):
         """op(x, offset, [mask,] weight, bias, ...), with fp32 sampling under autocast when the module asks for it:
         the casts happen here, differentiably, and the Function runs with autocast off, so it keeps the dtypes."""
         wg32 = self.weight_grad_dtype is not None
-        mode = _capi.weight_grads_f32() if wg32 else contextlib.nullcontext()
+        mode = self._call_modes()
         if not self._fp32_sampling():
             head = (x, offset) if mask is None else (x, offset, mask)
             with mode:

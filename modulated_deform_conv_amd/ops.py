@@ -122,13 +122,15 @@ def deform_conv(input: torch.Tensor, offset: torch.Tensor, mask: Optional[torch.
     geo = _geometry(weight, stride, padding, dilation, groups, deformable_groups, in_step,
                     bias is not None)
     fn = _entry(nd, mask is not None, False)
-    if mask is not None and nd == 2:   # the one export that allocates its result
-        return fn(input, weight, b, offset, mask, *geo)
-    out = torch.empty([input.shape[0], weight.shape[0]] + osz, dtype=input.dtype, device=input.device)
-    if mask is not None:
-        fn(input, weight, b, offset, mask, out, *geo)
-    else:
-        fn(input, weight, b, offset, out, *geo)
+    # (the operators' results are contiguous whatever mode the caller is in: the fake kernels promise those strides)
+    with _capi.channels_last_results(False):
+        if mask is not None and nd == 2:   # the one export that allocates its result
+            return fn(input, weight, b, offset, mask, *geo)
+        out = torch.empty([input.shape[0], weight.shape[0]] + osz, dtype=input.dtype, device=input.device)
+        if mask is not None:
+            fn(input, weight, b, offset, mask, out, *geo)
+        else:
+            fn(input, weight, b, offset, out, *geo)
     return out
 
 
@@ -155,7 +157,7 @@ def _backward_impl(grad_output, input, offset, mask, weight, bias, stride, paddi
                     bias is not None)
     fn = _entry(nd, mask is not None, True)
     fake = lambda g: input.new_empty(0) if g is None else g
-    with _capi.skip_grads(input=not need_input, weight=not need_weight):
+    with _capi.skip_grads(input=not need_input, weight=not need_weight), _capi.channels_last_results(False):
         if mask is not None and nd == 2:
             # (the export itself returns grad_weight / grad_bias as two views of one buffer; an operator's returns may not alias)
             return tuple(fake(g) for g in MDCONV_CUDA._modulated2d_backward(False, input, weight, b, offset, mask, grad_output, *geo))
