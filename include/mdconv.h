@@ -81,9 +81,20 @@ enum {
   MDCONV_EUNSUPPORTED = -5
 };
 
-/* Kernel-path selector (tests and benchmarks): AUTO picks the MFMA implicit-GEMM kernels when
- * the shape qualifies and the direct (VALU) kernels otherwise. */
-enum { MDCONV_PATH_AUTO = 0, MDCONV_PATH_DIRECT = 1, MDCONV_PATH_MFMA = 2 };
+/* Kernel-path selector (tests and benchmarks): AUTO picks the depthwise kernels for the layers they take (below), else
+ * the MFMA implicit-GEMM kernels when the shape qualifies and the direct (VALU) kernels otherwise.
+ * MDCONV_PATH_DEPTHWISE forces the depthwise family: the call runs on it or returns MDCONV_EUNSUPPORTED, with the rule it
+ * breaks in mdconv_last_error(), before anything is launched (the contract of MDCONV_PATH_MFMA).  MDCONV_PATH_DIRECT and
+ * MDCONV_PATH_MFMA never reach that family: they route a depthwise layer as releases without it did.
+ * Under AUTO one size rule applies, from measurement: several deformable groups of a multiple of 64 channels, with C_in <= 256 and
+ * at least 4096 output pixels, keep the route of earlier releases (faster there); MDCONV_PATH_DEPTHWISE takes them.
+ * Depthwise layers (the shape rule of the family): MDCONV_F32 tensors, input [B, C, spatial...], groups == C_in >= 2,
+ * C_in a multiple of 4, C_out / C_in of 1, 2, 3 or 4, C_in / deformable_groups a multiple of 4, every tensor below 2^31
+ * bytes; 2-D and 3-D, modulated or not, any kernel size, stride, padding and dilation, with or without bias.  No result is
+ * summed with floating-point atomics: output, grad_offset, grad_mask, grad_weight and grad_bias are bit-identical from call
+ * to call, grad_input is under MDCONV_FLAG_DETERMINISTIC and agrees to rounding otherwise.  MDCONV_FLAG_MATH_BF16 has
+ * nothing to do there (mdconv_math_bf16_used answers 0): the call runs exact. */
+enum { MDCONV_PATH_AUTO = 0, MDCONV_PATH_DIRECT = 1, MDCONV_PATH_MFMA = 2, MDCONV_PATH_DEPTHWISE = 3 };
 
 typedef struct mdconv_desc {
   int ndim;       /* 2 or 3, | MDCONV_DESC_V2 when the v2 fields below are filled in */
@@ -108,7 +119,7 @@ typedef struct mdconv_desc {
                        entry points), 0 = OVERWRITE grad_* (buffers need not be initialised) */
   int input_layout; /* MDCONV_LAYOUT_NCHW or MDCONV_LAYOUT_CHANNELS_LAST (see below) */
   int path;         /* MDCONV_PATH_AUTO = the process default (MDCONV_PATH / mdconv_set_path), or a forced
-                       MDCONV_PATH_DIRECT / MDCONV_PATH_MFMA for this call */
+                       MDCONV_PATH_DIRECT / MDCONV_PATH_MFMA / MDCONV_PATH_DEPTHWISE for this call */
   int reserved[5];  /* reserved[0..3] must be 0; reserved[4] is the per-call FLAGS word (MDCONV_FLAG_*, below):
                        any bit other than the flags defined here is MDCONV_EINVAL */
 } mdconv_desc;
@@ -206,16 +217,20 @@ int mdconv_out_size(const mdconv_desc *d, int axis);
 size_t mdconv_workspace_bytes(const mdconv_desc *d, int backward);
 
 /* Process-wide default kernel path (MDCONV_PATH_*) for descriptors that do not name one; returns the
- * previous value.  The environment variable MDCONV_PATH=auto|direct|mfma sets the initial default.
+ * previous value.  The environment variable MDCONV_PATH=auto|direct|mfma|depthwise sets the initial default.
  * Per call: mdconv_desc.path (ABI v2). */
 int mdconv_set_path(int path);
-/* Path the last forward / backward call of this thread actually ran (MDCONV_PATH_DIRECT/MFMA). */
+/* Path the last forward / backward call of this thread actually ran (MDCONV_PATH_DIRECT/MFMA/DEPTHWISE). */
 int mdconv_last_path(void);
 /* Kernel family behind it: the shape-generic VALU kernels, the fp32 MFMA kernels (also used for
- * 16-bit tensors through fp32 copies when the native kernels do not cover the shape), or the
- * native fp16 / bf16 MFMA kernels. */
-enum { MDCONV_KERNELS_DIRECT = 1, MDCONV_KERNELS_F32 = 2, MDCONV_KERNELS_HP = 3 };
+ * 16-bit tensors through fp32 copies when the native kernels do not cover the shape), the
+ * native fp16 / bf16 MFMA kernels, or the depthwise kernels (no matrix instructions, no atomics on results). */
+enum { MDCONV_KERNELS_DIRECT = 1, MDCONV_KERNELS_F32 = 2, MDCONV_KERNELS_HP = 3, MDCONV_KERNELS_DEPTHWISE = 4 };
 int mdconv_last_kernels(void);
+/* The MDCONV_KERNELS_* family the forward (backward = 0) / backward (backward = 1) of `d` would run on -- the routing of the
+ * call itself (`path`, `input_layout`, the flags), decided without a device -- or 0 for an invalid descriptor and for a call
+ * that would be refused (MDCONV_EUNSUPPORTED).  The two directions of one layer can differ. */
+int mdconv_planned_kernels(const mdconv_desc *d, int backward);
 
 /* Per-kernel timing for benchmarks: when enabled, the four dominant kernels are bracketed by HIP
  * events ON THE CALLER'S STREAM.  After a stream/device synchronise, mdconv_profile_read() returns

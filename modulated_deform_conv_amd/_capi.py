@@ -13,7 +13,7 @@ LIB_PATH = os.environ.get("MDCONV_LIB") or os.path.join(HERE, "libmdconv_hip.so"
 F32, F16, F64, BF16 = 0, 1, 2, 3
 SAMPLING_F32 = 0x10   # MDCONV_SAMPLING_F32: ORed into F16 / BF16, offset / mask and their gradients are fp32
 WGRAD_F32 = 0x40      # MDCONV_WGRAD_F32: ORed into F16 / BF16, the backward's grad_weight / grad_bias are fp32
-PATH_AUTO, PATH_DIRECT, PATH_MFMA = 0, 1, 2
+PATH_AUTO, PATH_DIRECT, PATH_MFMA, PATH_DEPTHWISE = 0, 1, 2, 3
 ABI_VERSION = 2
 DESC_V2 = 0x100   # MDCONV_DESC_V2: the descriptor carries accumulate / input_layout / path
 FLAG_DETERMINISTIC = 1   # MDCONV_FLAG_DETERMINISTIC, in the flags word (MdconvDesc.flags = reserved[4])
@@ -29,7 +29,7 @@ EXPORTS = (
     "mdconv_profile_enable", "mdconv_profile_read", "mdconv_profile_reset", "mdconv_profile_name",
     "mdconv_stream_wait_weight_ready", "mdconv_stream_wait_weight_ready_on", "mdconv_set_accumulate", "mdconv_set_input_layout",
     "mdconv_input_layout_supported", "mdconv_deterministic_supported", "mdconv_math_bf16_used",
-    "mdconv_result_layout_supported",
+    "mdconv_result_layout_supported", "mdconv_planned_kernels",
     "mdconv_deform_conv2d_forward", "mdconv_deform_conv2d_backward",
     "mdconv_modulated_deform_conv2d_forward", "mdconv_modulated_deform_conv2d_backward",
     "mdconv_deform_conv3d_forward", "mdconv_deform_conv3d_backward",
@@ -102,7 +102,12 @@ def lib():
         has_layout_query = hasattr(L, "mdconv_result_layout_supported")
         if has_layout_query:
             L.mdconv_result_layout_supported.argtypes = [ctypes.c_void_p, ctypes.c_int]
+        # (likewise a build from before the depthwise family: planned_kernels() raises there)
+        has_plan_query = hasattr(L, "mdconv_planned_kernels")
+        if has_plan_query:
+            L.mdconv_planned_kernels.argtypes = [ctypes.c_void_p, ctypes.c_int]
         missing = (() if has_math_query else ("mdconv_math_bf16_used",)) + (() if has_layout_query else ("mdconv_result_layout_supported",))
+        missing += () if has_plan_query else ("mdconv_planned_kernels",)
         for name in EXPORTS[11:]:
             if name not in missing:
                 getattr(L, name).restype = ctypes.c_int
@@ -117,19 +122,29 @@ def last_error():
 
 
 def set_path(path):
-    """Force the kernel path: 'auto' | 'direct' | 'mfma'.  Returns the previous setting."""
-    names = {"auto": PATH_AUTO, "direct": PATH_DIRECT, "mfma": PATH_MFMA}
+    """Force the kernel path: 'auto' | 'direct' | 'mfma' | 'depthwise'.  Returns the previous setting."""
+    names = {"auto": PATH_AUTO, "direct": PATH_DIRECT, "mfma": PATH_MFMA, "depthwise": PATH_DEPTHWISE}
     prev = lib().mdconv_set_path(names[path] if isinstance(path, str) else int(path))
     return {v: k for k, v in names.items()}[prev]
 
 
 def last_path():
-    return {0: "none", PATH_DIRECT: "direct", PATH_MFMA: "mfma"}[lib().mdconv_last_path()]
+    return {0: "none", PATH_DIRECT: "direct", PATH_MFMA: "mfma", PATH_DEPTHWISE: "depthwise"}[lib().mdconv_last_path()]
 
 
 def last_kernels():
-    """Kernel family of the last call: 'direct' | 'f32' (fp32 MFMA kernels) | 'hp' (native 16-bit)."""
-    return {0: "none", 1: "direct", 2: "f32", 3: "hp"}[lib().mdconv_last_kernels()]
+    """Kernel family of the last call: 'direct' | 'f32' (fp32 MFMA kernels) | 'hp' (native 16-bit) | 'depthwise'."""
+    return KERNELS[lib().mdconv_last_kernels()]
+
+
+KERNELS = {0: "none", 1: "direct", 2: "f32", 3: "hp", 4: "depthwise"}   # MDCONV_KERNELS_*
+
+
+def planned_kernels(desc, backward):
+    """Kernel family the forward (``backward`` false) / backward of ``desc`` (an ``MdconvDesc``) would run on, by the
+    names of ``last_kernels()``; 'none' for an invalid descriptor or a call that would be refused (``last_error()`` then
+    has the rule).  Host-side planning only: no device is needed."""
+    return KERNELS[lib().mdconv_planned_kernels(ctypes.byref(desc), int(bool(backward)))]
 
 
 PROFILE_SLOTS = 5   # forward GEMM, backward data GEMM, backward weight GEMM, grad_input gather

@@ -14,6 +14,7 @@
 #include <utility>
 
 #include "mdconv_common.hpp"
+#include "dw_plan.hpp"
 #include "hp_plan.hpp"
 #include "mfma_plan.hpp"
 
@@ -59,6 +60,7 @@ static int current_path() {
     p = MDCONV_PATH_AUTO;
     if (e && !strcmp(e, "direct")) p = MDCONV_PATH_DIRECT;
     if (e && !strcmp(e, "mfma")) p = MDCONV_PATH_MFMA;
+    if (e && !strcmp(e, "depthwise")) p = MDCONV_PATH_DEPTHWISE;
     int expect = -1;
     g_path.compare_exchange_strong(expect, p);
     p = g_path.load();
@@ -83,7 +85,7 @@ static int call_modes(const mdconv_desc *d, Modes *m) {
   }
   if ((d->accumulate != 0 && d->accumulate != 1) ||
       (d->input_layout != MDCONV_LAYOUT_NCHW && d->input_layout != MDCONV_LAYOUT_CHANNELS_LAST) ||
-      d->path < MDCONV_PATH_AUTO || d->path > MDCONV_PATH_MFMA) {
+      d->path < MDCONV_PATH_AUTO || d->path > MDCONV_PATH_DEPTHWISE) {
     set_error("bad call mode in the descriptor (accumulate=%d, input_layout=%d, path=%d)", d->accumulate,
               d->input_layout, d->path);
     return MDCONV_EINVAL;
@@ -265,6 +267,7 @@ static int wgrad_f32(const mdconv_desc *d, bool backward) { return backward && (
 // mdconv_deterministic_supported and mdconv_input_layout_supported.
 // ---------------------------------------------------------------------------------------------
 enum Route {
+  ROUTE_DW,              // depthwise kernels (fp32, groups == C_in)
   ROUTE_HP,              // native 16-bit kernels
   ROUTE_HP_F32,          // ... bf16 instances of them for fp32 tensors (MDCONV_FLAG_MATH_BF16): fp32 in and out, `hp` made for it
   ROUTE_F32,             // fp32 matrix kernels (16-bit tensors: chunk-wise fp32 copies inside the family)
@@ -274,12 +277,14 @@ enum Route {
   ROUTE_DIRECT_SAMP32    // ... through the fp32 copies of a call with fp32 offsets / masks (`s32`)
 };
 // A call can be refused; `route` and the byte counts then still say where it would have gone (the sizing query reports them).
-enum Refusal { REFUSE_NONE, REFUSE_CHANNELS_LAST, REFUSE_PATH_MFMA, REFUSE_DETERMINISTIC, REFUSE_RESULT_LAYOUT };
+enum Refusal { REFUSE_NONE, REFUSE_CHANNELS_LAST, REFUSE_PATH_MFMA, REFUSE_DETERMINISTIC, REFUSE_RESULT_LAYOUT, REFUSE_PATH_DEPTHWISE };
 struct CallPlan {
   Route route;
   Refusal refused;
   size_t bytes;      // workspace the route needs
   size_t reported;   // what mdconv_workspace_bytes answers: `bytes`, but see the few-tile forwards in plan_call
+  DwPlan dw;         // ROUTE_DW
+  const char *dw_reason;   // REFUSE_PATH_DEPTHWISE: the rule of the family the call breaks
   HpPlan hp;         // ROUTE_HP, ROUTE_HP_F32
   MfmaPlan f32;      // ROUTE_F32
   S32Plan s32;       // ROUTE_*_SAMP32
@@ -305,12 +310,42 @@ static bool route_is_direct(Route r) { return r == ROUTE_DIRECT || r == ROUTE_DI
 // Narrow CONV GROUPS of a wide layer are taken (256 -> 256 in 32 groups of 8, 56 x 56, B = 8: 0.33 against 0.97 ms).
 // `out_cl` / `gi_cl` (the result-layout flags) never change the route either: hp_plan records them, and plan_call below refuses
 // the flagged call the route does not honour.
+// Depthwise layers come first: under MDCONV_PATH_AUTO a call dw_plan takes runs on the depthwise kernels -- but for the one size
+// rule of dw_declined_by_size above -- with or without `mb16` -- the flag is a permission, and the family is exact; MDCONV_PATH_DEPTHWISE
+// runs there or is refused with dw_plan's rule; MDCONV_PATH_DIRECT and MDCONV_PATH_MFMA never look at the family.
+// The one size rule of the depthwise family under MDCONV_PATH_AUTO, from measurement (profiles/depthwise.md, the `rule_*` rows;
+// step times in ms, earlier route against the family).  With several deformable groups the earlier route is the shape-generic
+// forward and the matrix backward, whose dense C x C GEMMs are tiled natively where C_in / deformable_groups is a multiple of 64:
+// cheap while C_in is small, and faster than the family's list build and gather from a few thousand pixels.  Declined, in both
+// directions and whatever the flags: deformable_groups > 1, C_in / deformable_groups a multiple of 64, C_in <= 256 and at
+// least 4096 output pixels -- 128 channels in 2 groups at 6272 / 9408 / 25088 pixels 0.17 / 0.21 / 0.36 against 0.18 / 0.24 / 0.50;
+// 256 in 4 groups at 6272 / 25088 pixels 0.23 / 0.70 against 0.28 / 0.91.  Taken, because they gain or tie: 256 in 4 groups at 1568
+// pixels (0.145 against 0.123), 512 channels at every size measured (8 groups of 64: 0.21 against 0.15 at 1568 pixels, 0.89 against
+// 0.92 at 12544, inside the 5 % spread; 2 groups of 256: 0.45 against 0.40 at 6272, 1.66 against 1.55 at 25088), groups of 16 / 32
+// channels (0.71 against 0.23, 0.48 against 0.32, 2.20 against 1.72, 3-D 2.15 against 1.48), and every layer with ONE deformable
+// group, which the matrix family pads to 16 channels per conv group (256 -> 256 at 56 x 56, B = 8: 4.21 against 0.74).
+static bool dw_declined_by_size(const Geom &g) { return g.DG > 1 && g.Cdg % 64 == 0 && g.C <= 256 && g.N >= 4096; }
 static void plan_route(const Geom &g, int dt, int s32, int wg32, int path, bool backward, CallPlan *cp, Skip skip, int mb16,
                        bool out_cl, bool gi_cl) {
   const bool half = dt == MDCONV_F16 || dt == MDCONV_BF16;
   if (!backward) skip = Skip();
   cp->skip = skip;
   cp->scratch_gi = 0;
+  cp->dw_reason = nullptr;
+  if (path == MDCONV_PATH_AUTO || path == MDCONV_PATH_DEPTHWISE) {
+    if (dw_plan(g, dt, backward, &cp->dw, skip, &cp->dw_reason) && !(path == MDCONV_PATH_AUTO && dw_declined_by_size(g))) {
+      cp->route = ROUTE_DW;
+      cp->refused = REFUSE_NONE;
+      cp->bytes = cp->reported = cp->dw.total;
+      return;
+    }
+    if (path == MDCONV_PATH_DEPTHWISE) {
+      cp->route = ROUTE_DIRECT;
+      cp->refused = REFUSE_PATH_DEPTHWISE;
+      cp->bytes = cp->reported = 0;
+      return;
+    }
+  }
   if (mb16 && dt == MDCONV_F32 && path != MDCONV_PATH_DIRECT && !g.in_cl && g.C >= 16 && g.O >= 16 &&
       hp_plan(g, MDCONV_BF16, backward, &cp->hp, skip, true) && cp->hp.forward_preferred) {
     cp->route = ROUTE_HP_F32;
@@ -413,6 +448,8 @@ static int refuse(const CallPlan &cp, const Geom &g, int dt, int path, bool back
     set_error("MDCONV_PATH=mfma but this shape/dtype is not supported by the MFMA kernels");
   else if (cp.refused == REFUSE_RESULT_LAYOUT)
     set_layout_refusal(cp, backward);
+  else if (cp.refused == REFUSE_PATH_DEPTHWISE)
+    set_error("MDCONV_PATH=depthwise but the depthwise kernels do not take this call: %s", cp.dw_reason);
   else
     set_det_refusal(g, dt, path);
   return MDCONV_EUNSUPPORTED;
@@ -458,6 +495,10 @@ static int run_forward(const mdconv_desc *d, int nd, int modulated, Tensors t, v
   plan_call(g, dt, s32, 0, path, false, &cp, Skip(), md.math_bf16, md.out_cl != 0, false);
   if (cp.refused) return refuse(cp, g, dt, path, false);
   switch (cp.route) {
+    case ROUTE_DW:   // no workspace
+      g_last_path = MDCONV_PATH_DEPTHWISE;
+      g_last_kernels = MDCONV_KERNELS_DEPTHWISE;
+      return dw_forward(cp.dw, t, s);
     case ROUTE_HP_F32:   // the bf16 kernels on the caller's fp32 tensors
       if ((rc = check_ws(ws, ws_bytes, cp.bytes))) return rc;
       g_last_path = MDCONV_PATH_MFMA;
@@ -528,6 +569,12 @@ static int run_backward(const mdconv_desc *d, int nd, int modulated, Tensors t, 
     const int r = check_ws(ws, ws_bytes, cp.bytes);
     return r || !skip.weight ? r : record_weight_ready(s);
   };
+  if (cp.route == ROUTE_DW) {
+    if ((rc = ready())) return rc;
+    g_last_path = MDCONV_PATH_DEPTHWISE;
+    g_last_kernels = MDCONV_KERNELS_DEPTHWISE;
+    return dw_backward(cp.dw, t, ws, s);
+  }
   if (cp.route == ROUTE_HP || cp.route == ROUTE_HP_F32) {
     if ((rc = ready())) return rc;
     g_last_path = MDCONV_PATH_MFMA;
@@ -667,6 +714,28 @@ int mdconv_result_layout_supported(const mdconv_desc *d, int backward) {
   return 0;
 }
 
+int mdconv_planned_kernels(const mdconv_desc *d, int backward) {
+  Geom g;
+  Modes md;
+  if (fill_geom(d, &g) || call_modes(d, &md)) return 0;
+  g.in_cl = md.input_layout == MDCONV_LAYOUT_CHANNELS_LAST ? 1 : 0;
+  g.det = backward ? md.deterministic : 0;
+  const int dt = base_dtype(d);
+  CallPlan cp;
+  plan_call(g, dt, sampling_f32(d), wgrad_f32(d, backward != 0), md.path, backward != 0, &cp, md.skip, md.math_bf16, md.out_cl != 0,
+            md.gi_cl != 0);
+  if (cp.refused) {
+    refuse(cp, g, dt, md.path, backward != 0);   // the rule, for mdconv_last_error()
+    return 0;
+  }
+  switch (cp.route) {
+    case ROUTE_DW: return MDCONV_KERNELS_DEPTHWISE;
+    case ROUTE_HP: case ROUTE_HP_F32: return MDCONV_KERNELS_HP;
+    case ROUTE_F32: case ROUTE_F32_SAMP32: return MDCONV_KERNELS_F32;
+    default: return MDCONV_KERNELS_DIRECT;
+  }
+}
+
 int mdconv_math_bf16_used(const mdconv_desc *d, int backward) {
   Geom g;
   Modes md;
@@ -693,7 +762,7 @@ int mdconv_input_layout_supported(const mdconv_desc *d, int layout, int backward
   g.in_cl = 1;   // the plan of a channels-last call (the group-padded layout needs the library's own input copy)
   CallPlan cp;
   plan_call(g, base_dtype(d), sampling_f32(d), wgrad_f32(d, backward != 0), md.path, backward != 0, &cp);
-  return cp.refused != REFUSE_CHANNELS_LAST;
+  return cp.refused != REFUSE_CHANNELS_LAST && cp.refused != REFUSE_PATH_DEPTHWISE;
 }
 
 int mdconv_deterministic_supported(const mdconv_desc *d, int backward) {
@@ -705,6 +774,10 @@ int mdconv_deterministic_supported(const mdconv_desc *d, int backward) {
   g.det = 1;
   CallPlan cp;
   plan_call(g, base_dtype(d), sampling_f32(d), wgrad_f32(d, true), md.path, true, &cp, Skip(), md.math_bf16);
+  if (cp.refused == REFUSE_PATH_DEPTHWISE) {   // the call itself would be refused
+    refuse(cp, g, base_dtype(d), md.path, true);
+    return 0;
+  }
   if (!route_is_direct(cp.route)) return 1;
   set_det_refusal(g, base_dtype(d), md.path);   // the reason, for mdconv_last_error()
   return 0;
@@ -726,7 +799,7 @@ int mdconv_stream_wait_weight_ready_on(void *stream, void *producer_stream) {
 
 int mdconv_set_path(int path) {
   const int prev = current_path();
-  if (path >= MDCONV_PATH_AUTO && path <= MDCONV_PATH_MFMA) g_path.store(path);
+  if (path >= MDCONV_PATH_AUTO && path <= MDCONV_PATH_DEPTHWISE) g_path.store(path);
   return prev;
 }
 int mdconv_last_path(void) { return g_last_path; }
