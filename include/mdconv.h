@@ -348,6 +348,65 @@ int mdconv_modulated_deform_conv3d_backward(const mdconv_desc *d, const void *in
                                             const void *grad_output, void *workspace,
                                             size_t workspace_bytes, void *stream);
 
+/* --- DCNv3 core operator: grouped deformable sampling on channels-last tensors -----------------
+ * The sampling operator of the InternImage-style "DCNv3" block: no weight, no bias -- the learned weights live in the
+ * linear layers around it.  An operator of its own with a descriptor of its own; nothing about the eight entry points
+ * above changes.  2-D only.  G groups of D channels, C = G * D, K = kh * kw; every tensor dense and row-major:
+ *     input   [B, H,  W,  G*D]          output  [B, Ho, Wo, G*D]
+ *     offset  [B, Ho, Wo, G*K*2]        last axis = (group, tap, (x, y))  -- x (width) first
+ *     mask    [B, Ho, Wo, G*K]          last axis = (group, tap)
+ *     tap = i*kh + j, i in [0, kw) indexes the kernel's WIDTH, j in [0, kh) its height (width-major)
+ *     Ho = (H + 2*pad_h - (dil_h*(kh-1)+1)) / stride_h + 1      (Wo alike)
+ *     c_w = (dil_w*(kw-1)) >> 1,  c_h = (dil_h*(kh-1)) >> 1
+ *     loc_w = wo*stride_w - pad_w + c_w + (i*dil_w - c_w + off_x) * offset_scale
+ *     loc_h = ho*stride_h - pad_h + c_h + (j*dil_h - c_h + off_y) * offset_scale
+ *     out[b,ho,wo,g,d] = sum_tap mask[b,ho,wo,g,tap] * bilinear(input[b,:,:,g,d], loc_h, loc_w)
+ *  - bilinear reads the four neighbours of (loc_h, loc_w); a neighbour outside the image contributes zero and is never
+ *    loaded.  A sample with loc <= -1 or loc >= size on either axis contributes nothing, to the output and to every gradient.
+ *  - The backward returns grad_input, grad_offset (which carries the factor offset_scale) and grad_mask in the layouts of
+ *    input, offset and mask; `accumulate` is the write mode of mdconv_desc.accumulate.
+ *  - dtype: MDCONV_F32, MDCONV_F16 or MDCONV_BF16, one type for all tensors of a call (no dtype flags); coordinates,
+ *    interpolation weights and every sum are fp32.
+ *  - Shape rule (else MDCONV_EUNSUPPORTED, with the rule in the error message, before anything is launched): D a multiple
+ *    of 4 for fp32 and of 8 for 16-bit tensors (rows of 16 bytes), every tensor below 2^31 bytes, K <= 4096, and for a
+ *    backward with grad_input B*G <= 65535.
+ *  - flags: MDCONV_FLAG_DETERMINISTIC and MDCONV_FLAG_NO_GRAD_INPUT only; any other bit is MDCONV_EINVAL.  No result is
+ *    summed with floating-point atomics: output, grad_offset and grad_mask are bit-identical from call to call, grad_input
+ *    is with MDCONV_FLAG_DETERMINISTIC and agrees to rounding otherwise.  With MDCONV_FLAG_NO_GRAD_INPUT grad_input may be
+ *    NULL and is never touched; the other gradients are bit for bit those of the full call.  Forwards ignore both flags.
+ *  - A call checks in this order: the descriptor (MDCONV_EINVAL), the pointers (MDCONV_ENULL), the shape rule
+ *    (MDCONV_EUNSUPPORTED), the workspace (MDCONV_EWORKSPACE: size and 16-byte alignment, as above).
+ *  - The workspace figure is exact, 0 for the forward, and honours both flags.  A call is a plain chain of kernels on the
+ *    caller's stream: no second stream, no host synchronisation; it captures into a HIP graph. */
+typedef struct mdconv_dcnv3_desc {
+  int dtype;           /* MDCONV_F32 / MDCONV_F16 / MDCONV_BF16 */
+  int batch;           /* B */
+  int groups;          /* G */
+  int group_channels;  /* D */
+  int in_sz[2];        /* H, W */
+  int k_sz[2];         /* kh, kw */
+  int stride[2];       /* (h, w) */
+  int pad[2];
+  int dil[2];
+  float offset_scale;
+  int accumulate;      /* backward write mode: 1 = add to grad_*, 0 = overwrite */
+  int flags;           /* MDCONV_FLAG_DETERMINISTIC | MDCONV_FLAG_NO_GRAD_INPUT */
+} mdconv_dcnv3_desc;
+/* `mdconv_dcnv3_desc d = MDCONV_DCNV3_DESC_INIT;` then fill in the shape (stride 1, no padding, dilation 1, offset_scale 1,
+ * accumulate, no flags) */
+#define MDCONV_DCNV3_DESC_INIT { 0, 0, 0, 0, {0, 0}, {0, 0}, {1, 1}, {0, 0}, {1, 1}, 1.0f, 1, 0 }
+
+/* Output extent on `axis` (0 = height, 1 = width); -1 for a bad argument. */
+int mdconv_dcnv3_out_size(const mdconv_dcnv3_desc *d, int axis);
+/* Scratch bytes of the forward (backward = 0: always 0) or the backward (backward = 1) of `d`; 0 for a descriptor that is
+ * invalid or outside the shape rule. */
+size_t mdconv_dcnv3_workspace_bytes(const mdconv_dcnv3_desc *d, int backward);
+int mdconv_dcnv3_forward(const mdconv_dcnv3_desc *d, const void *input, const void *offset, const void *mask,
+                         void *output, void *workspace, size_t workspace_bytes, void *stream);
+int mdconv_dcnv3_backward(const mdconv_dcnv3_desc *d, const void *input, const void *offset, const void *mask,
+                          const void *grad_output, void *grad_input, void *grad_offset, void *grad_mask,
+                          void *workspace, size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

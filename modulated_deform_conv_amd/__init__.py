@@ -5,6 +5,8 @@ behind the reference's own operator surface.
     modulated_deform_conv_amd.modulated_deform_conv    autograd Functions + nn.Modules
     modulated_deform_conv_amd.ops                      torch.library ops mdconv::deform_conv[_backward]
                                                        (fake kernels: torch.compile / export)
+    modulated_deform_conv_amd.dcnv3                    the DCNv3 core operator (channels-last, fp32 / fp16 / bf16):
+                                                       DCNv3Function, dcnv3_core, DCNv3 -- also exported here
     modulated_deform_conv_amd.distributed              batch-sharded multi-GPU helper (RCCL)
 
 All compute runs in libmdconv_hip.so (hand-written HIP, C ABI in include/mdconv.h); there is no
@@ -13,3 +15,14 @@ CPU or PyTorch fallback.
 from . import _capi  # noqa: F401  (does not load the library until first use)
 
 __version__ = "0.1.0"
+
+_DCNV3 = ("DCNv3Function", "dcnv3_core", "DCNv3")
+__all__ = list(_DCNV3)
+
+
+def __getattr__(name):
+    # the DCNv3 names resolve on first use, so importing the package stays as light as before
+    if name in _DCNV3:
+        from . import dcnv3
+        return getattr(dcnv3, name)
+    raise AttributeError("module %r has no attribute %r" % (__name__, name))

@@ -34,6 +34,7 @@ EXPORTS = (
     "mdconv_modulated_deform_conv2d_forward", "mdconv_modulated_deform_conv2d_backward",
     "mdconv_deform_conv3d_forward", "mdconv_deform_conv3d_backward",
     "mdconv_modulated_deform_conv3d_forward", "mdconv_modulated_deform_conv3d_backward",
+    "mdconv_dcnv3_out_size", "mdconv_dcnv3_workspace_bytes", "mdconv_dcnv3_forward", "mdconv_dcnv3_backward",
 )
 
 
@@ -56,6 +57,14 @@ class MdconvDesc(ctypes.Structure):
     @flags.setter
     def flags(self, value):
         self.reserved[4] = int(value)
+
+
+class MdconvDcnv3Desc(ctypes.Structure):
+    """Mirror of ``struct mdconv_dcnv3_desc`` (include/mdconv.h, "DCNv3 core operator"); axis order (h, w)."""
+    _fields_ = [("dtype", ctypes.c_int), ("batch", ctypes.c_int), ("groups", ctypes.c_int),
+                ("group_channels", ctypes.c_int), ("in_sz", ctypes.c_int * 2), ("k_sz", ctypes.c_int * 2),
+                ("stride", ctypes.c_int * 2), ("pad", ctypes.c_int * 2), ("dil", ctypes.c_int * 2),
+                ("offset_scale", ctypes.c_float), ("accumulate", ctypes.c_int), ("flags", ctypes.c_int)]
 
 
 _lib = None
@@ -108,9 +117,15 @@ def lib():
             L.mdconv_planned_kernels.argtypes = [ctypes.c_void_p, ctypes.c_int]
         missing = (() if has_math_query else ("mdconv_math_bf16_used",)) + (() if has_layout_query else ("mdconv_result_layout_supported",))
         missing += () if has_plan_query else ("mdconv_planned_kernels",)
+        missing += tuple(n for n in EXPORTS if n.startswith("mdconv_dcnv3_") and not hasattr(L, n))
         for name in EXPORTS[11:]:
             if name not in missing:
                 getattr(L, name).restype = ctypes.c_int
+        # (MDCONV_LIB may name a build from before the DCNv3 core operator: dcnv3.py raises there)
+        if hasattr(L, "mdconv_dcnv3_workspace_bytes"):
+            L.mdconv_dcnv3_out_size.argtypes = [ctypes.c_void_p, ctypes.c_int]
+            L.mdconv_dcnv3_workspace_bytes.restype = ctypes.c_size_t
+            L.mdconv_dcnv3_workspace_bytes.argtypes = [ctypes.c_void_p, ctypes.c_int]
         if L.mdconv_abi_version() != ABI_VERSION:
             raise ImportError("libmdconv_hip.so ABI version mismatch")
         _lib = L

@@ -1,0 +1,80 @@
+// dcn3_host.hip -- plan and execution of the DCNv3 core operator (dcn3_plan.hpp).
+#include "dcn3_plan.hpp"
+
+namespace mdconv {
+
+bool dcn3_plan(const mdconv_dcnv3_desc *d, bool backward, Dcn3Plan *p, const char **why) {
+  const char *dummy;
+  if (!why) why = &dummy;
+  *why = nullptr;
+  const int64_t lim = (int64_t)1 << 31;
+  const int esz = d->dtype == MDCONV_F32 ? 4 : 2;
+  const int64_t Ho = (d->in_sz[0] + 2 * (int64_t)d->pad[0] - ((int64_t)d->dil[0] * (d->k_sz[0] - 1) + 1)) / d->stride[0] + 1;
+  const int64_t Wo = (d->in_sz[1] + 2 * (int64_t)d->pad[1] - ((int64_t)d->dil[1] * (d->k_sz[1] - 1) + 1)) / d->stride[1] + 1;
+  const int64_t K = (int64_t)d->k_sz[0] * d->k_sz[1];
+  const int64_t C = (int64_t)d->groups * d->group_channels;
+  const int64_t S_i = (int64_t)d->in_sz[0] * d->in_sz[1], S_o = Ho * Wo;
+  const bool skip_input = backward && (d->flags & MDCONV_FLAG_NO_GRAD_INPUT);
+  const int64_t seg_stride = K * S_o * 4;
+  // (each product is checked with its factors bounded by the checks before it, so none overflows 64 bits)
+  if (esz == 4 && d->group_channels % 4) *why = "group_channels is not a multiple of 4 (fp32 rows of 16 bytes)";
+  else if (esz == 2 && d->group_channels % 8) *why = "group_channels is not a multiple of 8 (16-bit rows of 16 bytes)";
+  else if (K > 4096) *why = "the kernel has more than 4096 taps";
+  else if (C >= lim || S_i >= lim || S_o >= lim || d->batch * S_i >= lim || d->batch * S_o >= lim ||
+           d->batch * S_i * C >= lim / esz || d->batch * S_o * C >= lim / esz ||
+           d->batch * S_o * d->groups >= lim || d->batch * S_o * d->groups * K * 2 * esz >= lim)
+    *why = "a tensor of the call has 2^31 bytes or more";
+  else if (backward && !skip_input && (seg_stride >= lim || (int64_t)d->batch * d->groups > 65535))
+    *why = "batch * groups exceeds 65535 or K * output pixels * 4 reaches 2^31 (the scatter lists of grad_input)";
+  if (*why) return false;
+
+  Dcn3Plan q = {};
+  Dcn3Geom &g = q.g;
+  g.B = d->batch; g.G = d->groups; g.D = d->group_channels; g.C = (int)C; g.K = (int)K;
+  g.H = d->in_sz[0]; g.W = d->in_sz[1]; g.Ho = (int)Ho; g.Wo = (int)Wo; g.kh = d->k_sz[0]; g.kw = d->k_sz[1];
+  g.sh = d->stride[0]; g.sw = d->stride[1]; g.ph = d->pad[0]; g.pw = d->pad[1]; g.dh = d->dil[0]; g.dw = d->dil[1];
+  g.ch = (g.dh * (g.kh - 1)) >> 1;
+  g.cw = (g.dw * (g.kw - 1)) >> 1;
+  g.S_i = (int)S_i; g.S_o = (int)S_o; g.N = (int)(d->batch * S_o);
+  g.esz = esz;
+  g.V = g.D * esz / 16;
+  g.lgVL = 0;
+  while ((1 << g.lgVL) < g.V && g.lgVL < 6) ++g.lgVL;
+  g.VL = 1 << g.lgVL;
+  g.rounds = (g.V + g.VL - 1) / g.VL;
+  g.scale = d->offset_scale;
+  g.acc = d->accumulate;
+  q.dtype = d->dtype;
+  q.backward = backward;
+  q.det = backward && (d->flags & MDCONV_FLAG_DETERMINISTIC);
+  q.skip_input = skip_input;
+  q.total = 0;
+  if (backward && !skip_input) {
+    q.nseg = g.B * g.G;
+    q.seg_stride = seg_stride;
+    Bump ws;
+    q.off_cnt = ws.take((size_t)q.nseg * g.S_i * 4);
+    q.off_rowptr = ws.take((size_t)q.nseg * (g.S_i + 1) * 4);
+    q.off_entries = ws.take((size_t)q.nseg * (size_t)seg_stride * 16);
+    q.off_sort = ws.take(q.det ? csr_sort_scratch_bytes(1, seg_stride, q.nseg) : 0);
+    q.total = ws.off;
+  }
+  *p = q;
+  return true;
+}
+
+int dcn3_forward(const Dcn3Plan &p, const Dcn3Tensors &t, hipStream_t stream) { return dcn3_fwd_launch(p, t, stream); }
+
+int dcn3_backward(const Dcn3Plan &p, const Dcn3Tensors &t, void *ws, hipStream_t stream) {
+  const Dcn3Geom &g = p.g;
+  int rc;
+  if ((rc = dcn3_bwd_coord_launch(p, t, stream))) return rc;
+  if (p.skip_input) return MDCONV_OK;
+  char *base = (char *)ws;
+  int *cnt = (int *)(base + p.off_cnt), *rowptr = (int *)(base + p.off_rowptr);
+  if ((rc = zero_bytes(cnt, (size_t)p.nseg * g.S_i * 4, stream))) return rc;
+  if ((rc = dcn3_lists_launch(p, t, cnt, rowptr, base + p.off_entries, p.det ? base + p.off_sort : nullptr, stream))) return rc;
+  return dcn3_gather_launch(p, t, rowptr, base + p.off_entries, stream);
+}
+
+}  // namespace mdconv

@@ -14,6 +14,7 @@
 #include <utility>
 
 #include "mdconv_common.hpp"
+#include "dcn3_plan.hpp"
 #include "dw_plan.hpp"
 #include "hp_plan.hpp"
 #include "mfma_plan.hpp"
@@ -676,6 +677,53 @@ static int wait_weight_ready(hipStream_t waiter, bool keyed, hipStream_t produce
 
 using namespace mdconv;
 
+// ---- DCNv3 core operator (dcn3_plan.hpp): the descriptor's own validation; the shape rule is dcn3_plan's ----
+static int dcn3_validate(const mdconv_dcnv3_desc *d) {
+  if (!d) {
+    set_error("descriptor pointer is NULL");
+    return MDCONV_EINVAL;
+  }
+  if (d->dtype != MDCONV_F32 && d->dtype != MDCONV_F16 && d->dtype != MDCONV_BF16) {
+    set_error("dcnv3: dtype %d is not MDCONV_F32, MDCONV_F16 or MDCONV_BF16 (the dtype flags do not apply)", d->dtype);
+    return MDCONV_EINVAL;
+  }
+  if (d->batch <= 0 || d->groups <= 0 || d->group_channels <= 0) {
+    set_error("dcnv3: batch, groups and group_channels must be positive (%d, %d, %d)", d->batch, d->groups, d->group_channels);
+    return MDCONV_EINVAL;
+  }
+  for (int a = 0; a < 2; ++a) {
+    if (d->in_sz[a] <= 0 || d->k_sz[a] <= 0 || d->stride[a] <= 0 || d->dil[a] <= 0 || d->pad[a] < 0) {
+      set_error("dcnv3: bad geometry on axis %d (in_sz=%d, k_sz=%d, stride=%d, pad=%d, dil=%d)", a, d->in_sz[a], d->k_sz[a],
+                d->stride[a], d->pad[a], d->dil[a]);
+      return MDCONV_EINVAL;
+    }
+    const long long span = (long long)d->dil[a] * (d->k_sz[a] - 1) + 1;
+    if ((long long)d->in_sz[a] + 2LL * d->pad[a] < span) {
+      set_error("dcnv3: the output extent on axis %d is below 1 (in_sz=%d, pad=%d, dilated kernel %lld)", a, d->in_sz[a],
+                d->pad[a], span);
+      return MDCONV_EINVAL;
+    }
+  }
+  if (d->accumulate != 0 && d->accumulate != 1) {
+    set_error("dcnv3: accumulate must be 0 or 1, is %d", d->accumulate);
+    return MDCONV_EINVAL;
+  }
+  if (d->flags & ~(MDCONV_FLAG_DETERMINISTIC | MDCONV_FLAG_NO_GRAD_INPUT)) {
+    set_error("dcnv3: unknown bits 0x%x in flags; the flags are MDCONV_FLAG_DETERMINISTIC (1) and MDCONV_FLAG_NO_GRAD_INPUT (4)",
+              (unsigned)(d->flags & ~(MDCONV_FLAG_DETERMINISTIC | MDCONV_FLAG_NO_GRAD_INPUT)));
+    return MDCONV_EINVAL;
+  }
+  if (!(d->offset_scale == d->offset_scale) || d->offset_scale - d->offset_scale != 0.f) {
+    set_error("dcnv3: offset_scale is not finite");
+    return MDCONV_EINVAL;
+  }
+  return MDCONV_OK;
+}
+static int dcn3_refuse(const char *why) {
+  set_error("dcnv3: outside the shape rule of the operator: %s", why);
+  return MDCONV_EUNSUPPORTED;
+}
+
 extern "C" {
 
 int mdconv_abi_version(void) { return MDCONV_ABI_VERSION; }
@@ -891,6 +939,60 @@ int mdconv_modulated_deform_conv3d_backward(const mdconv_desc *d, const void *in
   t.grad_output = grad_output; t.grad_input = grad_input; t.grad_weight = grad_weight;
   t.grad_bias = grad_bias; t.grad_offset = grad_offset; t.grad_mask = grad_mask;
   return run_backward(d, 3, 1, t, workspace, workspace_bytes, stream);
+}
+
+int mdconv_dcnv3_out_size(const mdconv_dcnv3_desc *d, int axis) {
+  if (!d || axis < 0 || axis > 1 || d->stride[axis] <= 0) return -1;
+  return (d->in_sz[axis] + 2 * d->pad[axis] - (d->dil[axis] * (d->k_sz[axis] - 1) + 1)) / d->stride[axis] + 1;
+}
+
+size_t mdconv_dcnv3_workspace_bytes(const mdconv_dcnv3_desc *d, int backward) {
+  Dcn3Plan p;
+  const char *why;
+  if (dcn3_validate(d)) return 0;
+  if (!dcn3_plan(d, backward != 0, &p, &why)) {
+    dcn3_refuse(why);
+    return 0;
+  }
+  return p.total;
+}
+
+int mdconv_dcnv3_forward(const mdconv_dcnv3_desc *d, const void *input, const void *offset, const void *mask,
+                         void *output, void *workspace, size_t workspace_bytes, void *stream) {
+  g_err[0] = 0;
+  int rc = dcn3_validate(d);
+  if (rc) return rc;
+  if ((rc = require(input, "input")) || (rc = require(offset, "offset")) || (rc = require(mask, "mask")) ||
+      (rc = require(output, "output")))
+    return rc;
+  Dcn3Plan p;
+  const char *why;
+  if (!dcn3_plan(d, false, &p, &why)) return dcn3_refuse(why);
+  if ((rc = check_ws(workspace, workspace_bytes, p.total))) return rc;
+  Dcn3Tensors t = {};
+  t.input = input; t.offset = offset; t.mask = mask; t.output = output;
+  return dcn3_forward(p, t, (hipStream_t)stream);
+}
+
+int mdconv_dcnv3_backward(const mdconv_dcnv3_desc *d, const void *input, const void *offset, const void *mask,
+                          const void *grad_output, void *grad_input, void *grad_offset, void *grad_mask,
+                          void *workspace, size_t workspace_bytes, void *stream) {
+  g_err[0] = 0;
+  int rc = dcn3_validate(d);
+  if (rc) return rc;
+  if ((rc = require(input, "input")) || (rc = require(offset, "offset")) || (rc = require(mask, "mask")) ||
+      (rc = require(grad_output, "grad_output")) || (rc = require(grad_offset, "grad_offset")) ||
+      (rc = require(grad_mask, "grad_mask")))
+    return rc;
+  if (!(d->flags & MDCONV_FLAG_NO_GRAD_INPUT) && (rc = require(grad_input, "grad_input"))) return rc;
+  Dcn3Plan p;
+  const char *why;
+  if (!dcn3_plan(d, true, &p, &why)) return dcn3_refuse(why);
+  if ((rc = check_ws(workspace, workspace_bytes, p.total))) return rc;
+  Dcn3Tensors t = {};
+  t.input = input; t.offset = offset; t.mask = mask; t.grad_output = grad_output;
+  t.grad_input = grad_input; t.grad_offset = grad_offset; t.grad_mask = grad_mask;
+  return dcn3_backward(p, t, workspace, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -1,0 +1,224 @@
+"""DCNv3 core operator on the MI355X-native backend: grouped deformable sampling on channels-last tensors
+(include/mdconv.h, "DCNv3 core operator"; INTEGRATION.md has the contract and what is unpinned).
+
+    DCNv3Function   autograd.Function over mdconv_dcnv3_forward / mdconv_dcnv3_backward
+    dcnv3_core      the functional form
+    DCNv3           nn.Module: the block around the operator, composed from framework operators
+
+The operator has no weight: ``input [B, H, W, G*D]``, ``offset [B, Ho, Wo, G*K*2]`` ((x, y) per tap, taps width-major),
+``mask [B, Ho, Wo, G*K]`` -> ``output [B, Ho, Wo, G*D]``, fp32 / fp16 / bf16, one dtype per call.  CPU tensors raise
+``NotImplementedError``: there is no CPU or PyTorch fallback.
+"""
+import ctypes
+
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+from torch.amp import custom_bwd, custom_fwd
+from torch.autograd import Function
+from torch.autograd.function import once_differentiable
+from torch.nn.modules.utils import _pair
+
+from . import _capi
+
+__all__ = ["DCNv3Function", "dcnv3_core", "DCNv3"]
+
+_DTYPES = {torch.float32: _capi.F32, torch.float16: _capi.F16, torch.bfloat16: _capi.BF16}
+
+
+def _desc(input, kernel, stride, pad, dilation, group, group_channels, offset_scale, accumulate=1, flags=0):
+    if input.dtype not in _DTYPES:
+        raise TypeError("dcnv3: dtype %s is not float32, float16 or bfloat16" % input.dtype)
+    d = _capi.MdconvDcnv3Desc()
+    d.dtype, d.batch, d.groups, d.group_channels = _DTYPES[input.dtype], input.shape[0], int(group), int(group_channels)
+    d.in_sz = (ctypes.c_int * 2)(int(input.shape[1]), int(input.shape[2]))
+    for name, v in (("k_sz", kernel), ("stride", stride), ("pad", pad), ("dil", dilation)):
+        setattr(d, name, (ctypes.c_int * 2)(*(int(x) for x in _pair(v))))
+    d.offset_scale, d.accumulate, d.flags = float(offset_scale), int(accumulate), int(flags)
+    return d
+
+
+def _out_hw(d):
+    L = _capi.lib()
+    return tuple(int(L.mdconv_dcnv3_out_size(ctypes.byref(d), a)) for a in (0, 1))
+
+
+def _check(d, input, offset, mask, **others):
+    """Shapes, dtypes, devices and density of the tensors of a call; ``others`` have the shape of ``output``."""
+    if input.dim() != 4 or input.shape[3] != d.groups * d.group_channels:
+        raise ValueError("dcnv3: input must be [B, H, W, group * group_channels = %d], got %s" % (
+            d.groups * d.group_channels, tuple(input.shape)))
+    ho, wo = _out_hw(d)
+    if ho < 1 or wo < 1:
+        raise ValueError("dcnv3: the output extent is below 1 (%d x %d)" % (ho, wo))
+    K = d.k_sz[0] * d.k_sz[1]
+    want = dict(offset=(d.batch, ho, wo, d.groups * K * 2), mask=(d.batch, ho, wo, d.groups * K))
+    want.update({k: (d.batch, ho, wo, d.groups * d.group_channels) for k in others})
+    for name, t in dict(offset=offset, mask=mask, **others).items():
+        if tuple(t.shape) != want[name]:
+            raise ValueError("dcnv3: %s must be %s, got %s" % (name, want[name], tuple(t.shape)))
+    for name, t in dict(input=input, offset=offset, mask=mask, **others).items():
+        if t.dtype != input.dtype or t.device != input.device:
+            raise ValueError("dcnv3: %s is %s on %s, input is %s on %s (one dtype and one device per call)" % (
+                name, t.dtype, t.device, input.dtype, input.device))
+        if not t.is_contiguous():
+            raise ValueError("dcnv3: %s must be dense and row-major (contiguous)" % name)
+    return (d.batch, ho, wo, d.groups * d.group_channels)
+
+
+def _ptr(t):
+    return ctypes.c_void_p(t.data_ptr() if t is not None else 0)
+
+
+def _run(fn_name, d, backward, args_before_ws, input):
+    L = _capi.lib()
+    with torch.cuda.device(input.device):
+        ws_bytes = L.mdconv_dcnv3_workspace_bytes(ctypes.byref(d), int(backward))
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=input.device) if ws_bytes else None
+        stream = torch.cuda.current_stream().cuda_stream
+        rc = getattr(L, fn_name)(ctypes.byref(d), *args_before_ws, ctypes.c_void_p(ws.data_ptr() if ws is not None else 0),
+                                 ctypes.c_size_t(ws_bytes), ctypes.c_void_p(stream))
+    if rc != 0:
+        raise RuntimeError("%s failed (%d): %s" % (fn_name, rc, _capi.last_error()))
+
+
+def dcnv3_forward(input, offset, mask, kernel, stride, pad, dilation, group, group_channels, offset_scale, output=None):
+    """The forward entry point on dense CUDA tensors; allocates ``output`` unless it is given."""
+    if not input.is_cuda:
+        raise NotImplementedError
+    d = _desc(input, kernel, stride, pad, dilation, group, group_channels, offset_scale)
+    others = {} if output is None else dict(output=output)
+    shape = _check(d, input, offset, mask, **others)
+    if output is None:
+        output = torch.empty(shape, dtype=input.dtype, device=input.device)
+    _run("mdconv_dcnv3_forward", d, False, [_ptr(input), _ptr(offset), _ptr(mask), _ptr(output)], input)
+    return output
+
+
+def dcnv3_backward(input, offset, mask, grad_output, kernel, stride, pad, dilation, group, group_channels, offset_scale,
+                   grads=None, need_grad_input=True, deterministic=None):
+    """The backward entry point.  ``grads`` = (grad_input | None, grad_offset, grad_mask): caller-allocated buffers the
+    gradients are ADDED to; without it fresh tensors are written.  ``need_grad_input`` false: grad_input is neither computed
+    nor allocated (``MDCONV_FLAG_NO_GRAD_INPUT``) and None is returned there.  ``deterministic`` None follows
+    ``_capi.deterministic_mode()``.  Returns (grad_input | None, grad_offset, grad_mask)."""
+    if not input.is_cuda:
+        raise NotImplementedError
+    det = _capi.deterministic_mode() if deterministic is None else bool(deterministic)
+    flags = (_capi.FLAG_DETERMINISTIC if det else 0) | (0 if need_grad_input else _capi.FLAG_NO_GRAD_INPUT)
+    d = _desc(input, kernel, stride, pad, dilation, group, group_channels, offset_scale, accumulate=int(grads is not None),
+              flags=flags)
+    _check(d, input, offset, mask, grad_output=grad_output)
+    if grads is None:
+        grads = (torch.empty_like(input) if need_grad_input else None, torch.empty_like(offset), torch.empty_like(mask))
+    gi, goff, gm = grads
+    for name, g, like in (("grad_input", gi, input), ("grad_offset", goff, offset), ("grad_mask", gm, mask)):
+        if g is None and name == "grad_input" and not need_grad_input:
+            continue
+        if g is None or g.shape != like.shape or g.dtype != like.dtype or g.device != like.device or not g.is_contiguous():
+            raise ValueError("dcnv3: %s must be a dense tensor of the shape, dtype and device of its forward tensor" % name)
+    _run("mdconv_dcnv3_backward", d, True,
+         [_ptr(input), _ptr(offset), _ptr(mask), _ptr(grad_output), _ptr(gi if need_grad_input else None), _ptr(goff), _ptr(gm)],
+         input)
+    return (gi if need_grad_input else None), goff, gm
+
+
+class DCNv3Function(Function):
+    """``DCNv3Function.apply(input, offset, mask, kernel_h, kernel_w, stride_h, stride_w, pad_h, pad_w, dilation_h,
+    dilation_w, group, group_channels, offset_scale, im2col_step=256)`` -- the argument order of the published operator;
+    ``im2col_step`` is accepted for signature parity and unused.  Under ``torch.autocast`` the three tensors run in the
+    autocast dtype and the gradients go back in the dtypes the caller's tensors have."""
+
+    @staticmethod
+    @custom_fwd(device_type="cuda")
+    def forward(ctx, input, offset, mask, kernel_h, kernel_w, stride_h, stride_w, pad_h, pad_w, dilation_h, dilation_w,
+                group, group_channels, offset_scale, im2col_step=256):
+        if not input.is_cuda:
+            raise NotImplementedError
+        ctx.geo = ((kernel_h, kernel_w), (stride_h, stride_w), (pad_h, pad_w), (dilation_h, dilation_w), group,
+                   group_channels, offset_scale)
+        ctx.in_dtypes = (input.dtype, offset.dtype, mask.dtype)
+        if torch.is_autocast_enabled("cuda"):
+            dt = torch.get_autocast_dtype("cuda")
+            input, offset, mask = (t if t.dtype == dt else t.to(dt) for t in (input, offset, mask))
+        input, offset, mask = input.contiguous(), offset.contiguous(), mask.contiguous()
+        if input.requires_grad or offset.requires_grad or mask.requires_grad or any(ctx.needs_input_grad[:3]):
+            ctx.save_for_backward(input, offset, mask)
+        return dcnv3_forward(input, offset, mask, *ctx.geo)
+
+    @staticmethod
+    @custom_bwd(device_type="cuda")
+    @once_differentiable
+    def backward(ctx, grad_output):
+        if not grad_output.is_cuda:
+            raise NotImplementedError
+        input, offset, mask = ctx.saved_tensors
+        grad_output = grad_output.contiguous()
+        if grad_output.dtype != input.dtype:
+            grad_output = grad_output.to(input.dtype)
+        # selective backward: grad_input is neither computed nor allocated when `input` needs no gradient
+        grads = dcnv3_backward(input, offset, mask, grad_output, *ctx.geo, need_grad_input=bool(ctx.needs_input_grad[0]))
+        back = lambda g, dt: g if g is None or g.dtype == dt else g.to(dt)
+        return tuple(back(g, dt) for g, dt in zip(grads, ctx.in_dtypes)) + (None,) * 12
+
+
+def dcnv3_core(input, offset, mask, kernel, stride, pad, dilation, group, group_channels, offset_scale):
+    """Functional form; ``kernel``, ``stride``, ``pad`` and ``dilation`` are ints or (h, w) pairs."""
+    (kh, kw), (sh, sw), (ph, pw), (dh, dw) = (_pair(v) for v in (kernel, stride, pad, dilation))
+    return DCNv3Function.apply(input, offset, mask, kh, kw, sh, sw, ph, pw, dh, dw, group, group_channels, offset_scale)
+
+
+class _ToChannelsLast(nn.Module):
+    def forward(self, x):
+        return x.permute(0, 2, 3, 1)
+
+
+class DCNv3(nn.Module):
+    """The DCNv3 block on ``[B, H, W, C]`` tensors: input projection, the offset branch (depthwise conv, LayerNorm, GELU, then
+    the ``offset`` and ``mask`` linears with a softmax over the taps of each group), the core operator, output projection.
+    Everything but the core operator is a framework operator.  Module and parameter names follow the published block
+    (``dw_conv.0``, ``dw_conv.1.1``, ``offset``, ``mask``, ``input_proj``, ``output_proj``) so that a checkpoint can load --
+    written from memory of that code and UNPINNED against it; the ``center_feature_scale`` and
+    ``remove_center`` variants are not provided."""
+
+    def __init__(self, channels=64, kernel_size=3, dw_kernel_size=None, stride=1, pad=1, dilation=1, group=4,
+                 offset_scale=1.0):
+        super().__init__()
+        if channels % group:
+            raise ValueError("channels must be divisible by group, but got %d and %d" % (channels, group))
+        dw_kernel_size = kernel_size if dw_kernel_size is None else dw_kernel_size
+        self.channels, self.kernel_size, self.dw_kernel_size = channels, kernel_size, dw_kernel_size
+        self.stride, self.pad, self.dilation = stride, pad, dilation
+        self.group, self.group_channels, self.offset_scale = group, channels // group, offset_scale
+        self.dw_conv = nn.Sequential(
+            nn.Conv2d(channels, channels, kernel_size=dw_kernel_size, stride=1, padding=(dw_kernel_size - 1) // 2, groups=channels),
+            nn.Sequential(_ToChannelsLast(), nn.LayerNorm(channels, eps=1e-6)),
+            nn.GELU())
+        self.offset = nn.Linear(channels, group * kernel_size * kernel_size * 2)
+        self.mask = nn.Linear(channels, group * kernel_size * kernel_size)
+        self.input_proj = nn.Linear(channels, channels)
+        self.output_proj = nn.Linear(channels, channels)
+        self._core = dcnv3_core
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        for lin in (self.offset, self.mask):
+            nn.init.zeros_(lin.weight)
+            nn.init.zeros_(lin.bias)
+        for lin in (self.input_proj, self.output_proj):
+            nn.init.xavier_uniform_(lin.weight)
+            nn.init.zeros_(lin.bias)
+
+    def forward(self, input):
+        B, H, W, _ = input.shape
+        x = self.input_proj(input)
+        x1 = self.dw_conv(input.permute(0, 3, 1, 2))
+        offset = self.offset(x1)
+        mask = F.softmax(self.mask(x1).reshape(B, H, W, self.group, -1), -1).reshape(B, H, W, -1)
+        # (softmax runs in fp32 under autocast: one dtype per call)
+        x = self._core(x, offset.to(x.dtype), mask.to(x.dtype), self.kernel_size, self.stride, self.pad, self.dilation,
+                       self.group, self.group_channels, self.offset_scale)
+        return self.output_proj(x)
+
+    def extra_repr(self):
+        return "channels=%d, kernel_size=%d, stride=%d, pad=%d, dilation=%d, group=%d, offset_scale=%g" % (
+            self.channels, self.kernel_size, self.stride, self.pad, self.dilation, self.group, self.offset_scale)
