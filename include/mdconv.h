@@ -407,6 +407,67 @@ int mdconv_dcnv3_backward(const mdconv_dcnv3_desc *d, const void *input, const v
                           const void *grad_output, void *grad_input, void *grad_offset, void *grad_mask,
                           void *workspace, size_t workspace_bytes, void *stream);
 
+/* --- Multi-scale deformable attention: the sampling operator of Deformable-DETR-style attention -----
+ * ("MSDeformAttn": Deformable-DETR encoders and decoders, Mask2Former's pixel decoder, DINO, RT-DETR.)  The operator the
+ * DCNv3 core operator was derived from; an operator of its own with a descriptor of its own, nothing above changes.
+ * N images, M heads of D channels, Lq queries, L levels of P points; every tensor dense and row-major:
+ *     value               [N, S, M, D]         S = sum_l H_l*W_l: the levels concatenated in order, each row-major (y*W_l + x)
+ *     sampling_locations  [N, Lq, M, L, P, 2]  last axis (x, y), normalised: 0..1 spans the level
+ *     attention_weights   [N, Lq, M, L, P]
+ *     output              [N, Lq, M*D]
+ *     x = loc_x * W_l - 0.5,   y = loc_y * H_l - 0.5                    (pixel coordinates in level l)
+ *     out[n,q,m,:] = sum_{l,p} attn[n,q,m,l,p] * bilinear(value[n, start_l + ., m, :], y, x)
+ *  - start_l is the cumulative sum of the extents before level l: the level starts are not an input.
+ *  - bilinear reads the four neighbours of (y, x); a neighbour outside the level contributes zero and is never loaded.  A
+ *    sample with x <= -1, y <= -1, x >= W_l or y >= H_l contributes nothing, to the output and to every gradient (the gate
+ *    of the DCNv3 core operator; it equals grid_sample with zero padding and align_corners = false).
+ *  - The backward returns grad_value, grad_sampling_locations (which carries the factors W_l for x and H_l for y) and
+ *    grad_attention_weights in the layouts of their forward tensors; `accumulate` is the write mode of mdconv_desc.accumulate.
+ *  - dtype (MDCONV_F32, MDCONV_F16 or MDCONV_BF16) is the type of value, output, grad_output and grad_value; coord_dtype is
+ *    the type of sampling_locations, attention_weights and their gradients: equal to dtype, or MDCONV_F32 (a bf16
+ *    normalised location resolves 0.4 px on a level 100 pixels wide).  All arithmetic is fp32, each result is rounded once.
+ *  - Shape rule (else MDCONV_EUNSUPPORTED, with the rule in the error message, before anything is launched): D a multiple
+ *    of 4 for fp32 and of 8 for 16-bit values (rows of 16 bytes), every tensor below 2^31 bytes, L*P <= 4096, and for a
+ *    backward with grad_value N*M <= 65535 and L*P*Lq*4 below 2^31.
+ *  - flags: MDCONV_FLAG_DETERMINISTIC and MDCONV_FLAG_NO_GRAD_INPUT only (the latter: no grad_value); any other bit is
+ *    MDCONV_EINVAL.  No result is summed with floating-point atomics: output and the two coordinate gradients are
+ *    bit-identical from call to call, grad_value is with MDCONV_FLAG_DETERMINISTIC and agrees to rounding otherwise.  With
+ *    MDCONV_FLAG_NO_GRAD_INPUT grad_value may be NULL and is never touched; the other gradients are bit for bit those of the
+ *    full call.  Forwards ignore both flags.
+ *  - A call checks in this order: the descriptor (MDCONV_EINVAL), the pointers (MDCONV_ENULL), the shape rule
+ *    (MDCONV_EUNSUPPORTED), the workspace (MDCONV_EWORKSPACE: size and 16-byte alignment, as above).
+ *  - The workspace figure is exact, 0 for the forward, and honours both flags.  A call is a plain chain of kernels on the
+ *    caller's stream: no second stream, no host synchronisation; it captures into a HIP graph.
+ *  Written from memory of the published operator and UNPINNED against its code. */
+#define MDCONV_MSDA_MAX_LEVELS 8
+typedef struct mdconv_msda_desc {
+  int dtype;           /* value, output, grad_output, grad_value: MDCONV_F32 / MDCONV_F16 / MDCONV_BF16 */
+  int coord_dtype;     /* sampling_locations, attention_weights and their gradients: `dtype` or MDCONV_F32 */
+  int batch;           /* N */
+  int heads;           /* M */
+  int head_channels;   /* D */
+  int queries;         /* Lq */
+  int levels;          /* L, 1..MDCONV_MSDA_MAX_LEVELS */
+  int points;          /* P */
+  int level_sz[MDCONV_MSDA_MAX_LEVELS][2];  /* (H_l, W_l) of the first `levels` rows; the others are ignored */
+  int accumulate;      /* backward write mode: 1 = add to grad_*, 0 = overwrite */
+  int flags;           /* MDCONV_FLAG_DETERMINISTIC | MDCONV_FLAG_NO_GRAD_INPUT */
+} mdconv_msda_desc;
+/* `mdconv_msda_desc d = MDCONV_MSDA_DESC_INIT;` then fill in the shape (fp32, accumulate, no flags) */
+#define MDCONV_MSDA_DESC_INIT { 0, 0, 0, 0, 0, 0, 0, 0, {{0, 0}}, 1, 0 }
+
+/* S, the rows of `value` per image: the sum of H_l*W_l over the levels; -1 for a bad descriptor. */
+int mdconv_msda_value_len(const mdconv_msda_desc *d);
+/* Scratch bytes of the forward (backward = 0: always 0) or the backward (backward = 1) of `d`; 0 for a descriptor that is
+ * invalid or outside the shape rule. */
+size_t mdconv_msda_workspace_bytes(const mdconv_msda_desc *d, int backward);
+int mdconv_msda_forward(const mdconv_msda_desc *d, const void *value, const void *sampling_locations,
+                        const void *attention_weights, void *output, void *workspace, size_t workspace_bytes, void *stream);
+int mdconv_msda_backward(const mdconv_msda_desc *d, const void *value, const void *sampling_locations,
+                         const void *attention_weights, const void *grad_output, void *grad_value,
+                         void *grad_sampling_locations, void *grad_attention_weights, void *workspace,
+                         size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

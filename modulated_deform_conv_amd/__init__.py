@@ -7,6 +7,10 @@ behind the reference's own operator surface.
                                                        (fake kernels: torch.compile / export)
     modulated_deform_conv_amd.dcnv3                    the DCNv3 core operator (channels-last, fp32 / fp16 / bf16):
                                                        DCNv3Function, dcnv3_core, DCNv3 -- also exported here
+    modulated_deform_conv_amd.msda                     multi-scale deformable attention (channels-last, fp32 / fp16 /
+                                                       bf16, coordinates in the same type or fp32): MSDeformAttnFunction,
+                                                       ms_deform_attn, ms_deform_attn_forward / _backward, MSDeformAttn
+                                                       -- also exported here
     modulated_deform_conv_amd.distributed              batch-sharded multi-GPU helper (RCCL)
 
 All compute runs in libmdconv_hip.so (hand-written HIP, C ABI in include/mdconv.h); there is no
@@ -17,12 +21,16 @@ from . import _capi  # noqa: F401  (does not load the library until first use)
 __version__ = "0.1.0"
 
 _DCNV3 = ("DCNv3Function", "dcnv3_core", "DCNv3")
-__all__ = list(_DCNV3)
+_MSDA = ("ms_deform_attn_forward", "ms_deform_attn_backward", "MSDeformAttnFunction", "ms_deform_attn", "MSDeformAttn")
+__all__ = list(_DCNV3 + _MSDA)
 
 
 def __getattr__(name):
-    # the DCNv3 names resolve on first use, so importing the package stays as light as before
+    # the DCNv3 and MSDA names resolve on first use, so importing the package stays as light as before
     if name in _DCNV3:
         from . import dcnv3
         return getattr(dcnv3, name)
+    if name in _MSDA:
+        from . import msda
+        return getattr(msda, name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

@@ -116,17 +116,18 @@ struct Dcn3Lane {
   bool live;
   int pair, j, first;   // first: the wave lane of the pair's lane 0
 };
-__device__ __forceinline__ Dcn3Lane dcn3_lane(const Dcn3Geom &g, int npairs) {
+__device__ __forceinline__ Dcn3Lane dcn3_lane_of(int lgVL, int npairs) {   // (msda_plan.hpp shares the mapping)
   const int lane = threadIdx.x & 63;
   const int wave = blockIdx.x * 4 + (threadIdx.x >> 6);
   Dcn3Lane l;
-  l.j = lane & (g.VL - 1);
+  l.j = lane & ((1 << lgVL) - 1);
   l.first = lane - l.j;
-  const int pair = wave * (64 >> g.lgVL) + (lane >> g.lgVL);
+  const int pair = wave * (64 >> lgVL) + (lane >> lgVL);
   l.live = pair < npairs;
   l.pair = l.live ? pair : npairs - 1;
   return l;
 }
+__device__ __forceinline__ Dcn3Lane dcn3_lane(const Dcn3Geom &g, int npairs) { return dcn3_lane_of(g.lgVL, npairs); }
 
 // Sampling state of one (output pixel, group, tap), as the lanes of the pair share it: fractional parts, mask, and per
 // corner the byte offset of the group's channel row in `input` -- kDcn3Oob for a corner that is not read, whose load then

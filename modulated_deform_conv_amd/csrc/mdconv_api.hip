@@ -15,6 +15,7 @@
 
 #include "mdconv_common.hpp"
 #include "dcn3_plan.hpp"
+#include "msda_plan.hpp"
 #include "dw_plan.hpp"
 #include "hp_plan.hpp"
 #include "mfma_plan.hpp"
@@ -724,6 +725,51 @@ static int dcn3_refuse(const char *why) {
   return MDCONV_EUNSUPPORTED;
 }
 
+// ---- multi-scale deformable attention (msda_plan.hpp): the descriptor's own validation; the shape rule is msda_plan's ----
+static int msda_validate(const mdconv_msda_desc *d) {
+  if (!d) {
+    set_error("descriptor pointer is NULL");
+    return MDCONV_EINVAL;
+  }
+  if (d->dtype != MDCONV_F32 && d->dtype != MDCONV_F16 && d->dtype != MDCONV_BF16) {
+    set_error("msda: dtype %d is not MDCONV_F32, MDCONV_F16 or MDCONV_BF16 (the dtype flags do not apply)", d->dtype);
+    return MDCONV_EINVAL;
+  }
+  if (d->coord_dtype != d->dtype && d->coord_dtype != MDCONV_F32) {
+    set_error("msda: coord_dtype %d is neither dtype (%d) nor MDCONV_F32", d->coord_dtype, d->dtype);
+    return MDCONV_EINVAL;
+  }
+  if (d->batch <= 0 || d->heads <= 0 || d->head_channels <= 0 || d->queries <= 0 || d->points <= 0) {
+    set_error("msda: batch, heads, head_channels, queries and points must be positive (%d, %d, %d, %d, %d)", d->batch, d->heads,
+              d->head_channels, d->queries, d->points);
+    return MDCONV_EINVAL;
+  }
+  if (d->levels < 1 || d->levels > MDCONV_MSDA_MAX_LEVELS) {
+    set_error("msda: levels must be 1..%d, is %d", MDCONV_MSDA_MAX_LEVELS, d->levels);
+    return MDCONV_EINVAL;
+  }
+  for (int l = 0; l < d->levels; ++l) {
+    if (d->level_sz[l][0] <= 0 || d->level_sz[l][1] <= 0) {
+      set_error("msda: level %d has a non-positive extent (%d x %d)", l, d->level_sz[l][0], d->level_sz[l][1]);
+      return MDCONV_EINVAL;
+    }
+  }
+  if (d->accumulate != 0 && d->accumulate != 1) {
+    set_error("msda: accumulate must be 0 or 1, is %d", d->accumulate);
+    return MDCONV_EINVAL;
+  }
+  if (d->flags & ~(MDCONV_FLAG_DETERMINISTIC | MDCONV_FLAG_NO_GRAD_INPUT)) {
+    set_error("msda: unknown bits 0x%x in flags; the flags are MDCONV_FLAG_DETERMINISTIC (1) and MDCONV_FLAG_NO_GRAD_INPUT (4)",
+              (unsigned)(d->flags & ~(MDCONV_FLAG_DETERMINISTIC | MDCONV_FLAG_NO_GRAD_INPUT)));
+    return MDCONV_EINVAL;
+  }
+  return MDCONV_OK;
+}
+static int msda_refuse(const char *why) {
+  set_error("msda: outside the shape rule of the operator: %s", why);
+  return MDCONV_EUNSUPPORTED;
+}
+
 extern "C" {
 
 int mdconv_abi_version(void) { return MDCONV_ABI_VERSION; }
@@ -993,6 +1039,70 @@ int mdconv_dcnv3_backward(const mdconv_dcnv3_desc *d, const void *input, const v
   t.input = input; t.offset = offset; t.mask = mask; t.grad_output = grad_output;
   t.grad_input = grad_input; t.grad_offset = grad_offset; t.grad_mask = grad_mask;
   return dcn3_backward(p, t, workspace, (hipStream_t)stream);
+}
+
+int mdconv_msda_value_len(const mdconv_msda_desc *d) {
+  g_err[0] = 0;
+  if (msda_validate(d)) return -1;
+  long long S = 0;
+  for (int l = 0; l < d->levels; ++l) S += (long long)d->level_sz[l][0] * d->level_sz[l][1];   // (8 products below 2^62)
+  if (S >= (1LL << 31)) {
+    set_error("msda: the levels have 2^31 rows or more");
+    return -1;
+  }
+  return (int)S;
+}
+
+size_t mdconv_msda_workspace_bytes(const mdconv_msda_desc *d, int backward) {
+  MsdaPlan p;
+  const char *why;
+  g_err[0] = 0;
+  if (msda_validate(d)) return 0;
+  if (!msda_plan(d, backward != 0, &p, &why)) {
+    msda_refuse(why);
+    return 0;
+  }
+  return p.total;
+}
+
+int mdconv_msda_forward(const mdconv_msda_desc *d, const void *value, const void *sampling_locations,
+                        const void *attention_weights, void *output, void *workspace, size_t workspace_bytes, void *stream) {
+  g_err[0] = 0;
+  int rc = msda_validate(d);
+  if (rc) return rc;
+  if ((rc = require(value, "value")) || (rc = require(sampling_locations, "sampling_locations")) ||
+      (rc = require(attention_weights, "attention_weights")) || (rc = require(output, "output")))
+    return rc;
+  MsdaPlan p;
+  const char *why;
+  if (!msda_plan(d, false, &p, &why)) return msda_refuse(why);
+  if ((rc = check_ws(workspace, workspace_bytes, p.total))) return rc;
+  MsdaTensors t = {};
+  t.value = value; t.loc = sampling_locations; t.attn = attention_weights; t.output = output;
+  return msda_forward(p, t, (hipStream_t)stream);
+}
+
+int mdconv_msda_backward(const mdconv_msda_desc *d, const void *value, const void *sampling_locations,
+                         const void *attention_weights, const void *grad_output, void *grad_value,
+                         void *grad_sampling_locations, void *grad_attention_weights, void *workspace,
+                         size_t workspace_bytes, void *stream) {
+  g_err[0] = 0;
+  int rc = msda_validate(d);
+  if (rc) return rc;
+  if ((rc = require(value, "value")) || (rc = require(sampling_locations, "sampling_locations")) ||
+      (rc = require(attention_weights, "attention_weights")) || (rc = require(grad_output, "grad_output")) ||
+      (rc = require(grad_sampling_locations, "grad_sampling_locations")) ||
+      (rc = require(grad_attention_weights, "grad_attention_weights")))
+    return rc;
+  if (!(d->flags & MDCONV_FLAG_NO_GRAD_INPUT) && (rc = require(grad_value, "grad_value"))) return rc;
+  MsdaPlan p;
+  const char *why;
+  if (!msda_plan(d, true, &p, &why)) return msda_refuse(why);
+  if ((rc = check_ws(workspace, workspace_bytes, p.total))) return rc;
+  MsdaTensors t = {};
+  t.value = value; t.loc = sampling_locations; t.attn = attention_weights; t.grad_output = grad_output;
+  t.grad_value = grad_value; t.grad_loc = grad_sampling_locations; t.grad_attn = grad_attention_weights;
+  return msda_backward(p, t, workspace, (hipStream_t)stream);
 }
 
 }  // extern "C"
