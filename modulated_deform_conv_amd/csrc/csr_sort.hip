@@ -18,6 +18,7 @@
 //     row: correct at any length (a row is K * S_o entries when every sample of an image lands on one pixel), fast it
 //     is not -- real layers have rows of a few dozen entries.
 #include "mdconv_common.hpp"
+#include "mfma_kernels.hpp"   // zero_bytes
 
 namespace mdconv {
 
@@ -206,6 +207,32 @@ int csr_sort_rows(const int *rowptr, void *entries, void *scratch, int width, in
     hipLaunchKernelGGL(csr_sort_rows_kernel<2>, grid, dim3(256), 0, stream, rowptr, (int4 *)entries, (int4 *)scratch, S_e,
                        seg_stride, rows);
   return check_launch("csr_sort_rows");
+}
+
+// ---- the list build of the VALU families (ScatterLists, mdconv_common.hpp) ----
+namespace {
+__global__ __launch_bounds__(256) void lists_scan_kernel(int S, const int *__restrict__ cnt, int *__restrict__ rowptr) {
+  csr_scan_chunk(S, cnt, rowptr);
+}
+int csr_scan_launch(int S, int nseg, const int *cnt, int *rowptr, hipStream_t stream) {
+  hipLaunchKernelGGL(lists_scan_kernel, dim3((S + kScanChunk - 1) / kScanChunk, nseg), dim3(256), 0, stream, S, cnt, rowptr);
+  return check_launch("lists_scan");
+}
+}  // namespace
+
+int scatter_lists_build(const ScatterLists &L, void *ws, bool det, hipStream_t stream,
+                        const std::function<void(bool fill, int *cnt, const int *rowptr, void *entries)> &launch_list) {
+  char *base = (char *)ws;
+  int *cnt = (int *)(base + L.off_cnt), *rowptr = (int *)(base + L.off_rowptr);
+  int rc;
+  if ((rc = zero_bytes(cnt, (size_t)L.nseg * L.rows * 4, stream))) return rc;
+  launch_list(false, cnt, rowptr, base + L.off_entries);
+  if ((rc = check_launch("lists_count"))) return rc;
+  if ((rc = csr_scan_launch(L.rows, L.nseg, cnt, rowptr, stream))) return rc;
+  launch_list(true, cnt, rowptr, base + L.off_entries);
+  if ((rc = check_launch("lists_fill"))) return rc;
+  if (!det) return MDCONV_OK;
+  return csr_sort_rows(rowptr, base + L.off_entries, base + L.off_sort, 1, L.rows, L.seg_stride, L.nseg, stream);
 }
 
 }  // namespace mdconv

@@ -1,7 +1,16 @@
-// dcn3_host.hip -- plan and execution of the DCNv3 core operator (dcn3_plan.hpp).
+// dcn3_host.hip -- plan and execution of the DCNv3 core operator (dcn3_plan.hpp): the sampling core's kernels (samp_core.hpp)
+// instantiated with Dcn3Op, coordinates in the values' type.
 #include "dcn3_plan.hpp"
 
 namespace mdconv {
+
+// `call(DT, CT)` for the plan's type: the coordinates have the values'
+#define DCN3_DISPATCH(p, call)                                       \
+  do {                                                               \
+    if ((p).dtype == MDCONV_F32) call(MDCONV_F32, MDCONV_F32);       \
+    else if ((p).dtype == MDCONV_F16) call(MDCONV_F16, MDCONV_F16);  \
+    else call(MDCONV_BF16, MDCONV_BF16);                             \
+  } while (0)
 
 bool dcn3_plan(const mdconv_dcnv3_desc *d, bool backward, Dcn3Plan *p, const char **why) {
   const char *dummy;
@@ -36,12 +45,7 @@ bool dcn3_plan(const mdconv_dcnv3_desc *d, bool backward, Dcn3Plan *p, const cha
   g.ch = (g.dh * (g.kh - 1)) >> 1;
   g.cw = (g.dw * (g.kw - 1)) >> 1;
   g.S_i = (int)S_i; g.S_o = (int)S_o; g.N = (int)(d->batch * S_o);
-  g.esz = esz;
-  g.V = g.D * esz / 16;
-  g.lgVL = 0;
-  while ((1 << g.lgVL) < g.V && g.lgVL < 6) ++g.lgVL;
-  g.VL = 1 << g.lgVL;
-  g.rounds = (g.V + g.VL - 1) / g.VL;
+  g.ln = samp_lanes(g.D, esz);
   g.scale = d->offset_scale;
   g.acc = d->accumulate;
   q.dtype = d->dtype;
@@ -50,31 +54,40 @@ bool dcn3_plan(const mdconv_dcnv3_desc *d, bool backward, Dcn3Plan *p, const cha
   q.skip_input = skip_input;
   q.total = 0;
   if (backward && !skip_input) {
-    q.nseg = g.B * g.G;
-    q.seg_stride = seg_stride;
     Bump ws;
-    q.off_cnt = ws.take((size_t)q.nseg * g.S_i * 4);
-    q.off_rowptr = ws.take((size_t)q.nseg * (g.S_i + 1) * 4);
-    q.off_entries = ws.take((size_t)q.nseg * (size_t)seg_stride * 16);
-    q.off_sort = ws.take(q.det ? csr_sort_scratch_bytes(1, seg_stride, q.nseg) : 0);
+    q.lists = scatter_lists_take(ws, g.B * g.G, g.S_i, seg_stride, q.det);
     q.total = ws.off;
   }
   *p = q;
   return true;
 }
 
-int dcn3_forward(const Dcn3Plan &p, const Dcn3Tensors &t, hipStream_t stream) { return dcn3_fwd_launch(p, t, stream); }
+int dcn3_forward(const Dcn3Plan &p, const Dcn3Tensors &t, hipStream_t stream) {
+#define DCN3_FWD(DT, CT) samp_fwd_launch<Dcn3Op, DT, CT>(p.g, t.input, t.offset, t.mask, t.output, stream)
+  DCN3_DISPATCH(p, DCN3_FWD);
+#undef DCN3_FWD
+  return check_launch("dcn3_fwd");
+}
 
 int dcn3_backward(const Dcn3Plan &p, const Dcn3Tensors &t, void *ws, hipStream_t stream) {
   const Dcn3Geom &g = p.g;
+  const ScatterLists &L = p.lists;
   int rc;
-  if ((rc = dcn3_bwd_coord_launch(p, t, stream))) return rc;
+#define DCN3_BWD(DT, CT) \
+  samp_bwd_coord_launch<Dcn3Op, DT, CT>(g, t.input, t.offset, t.mask, t.grad_output, t.grad_offset, t.grad_mask, stream)
+  DCN3_DISPATCH(p, DCN3_BWD);
+#undef DCN3_BWD
+  if ((rc = check_launch("dcn3_bwd_coord"))) return rc;
   if (p.skip_input) return MDCONV_OK;
-  char *base = (char *)ws;
-  int *cnt = (int *)(base + p.off_cnt), *rowptr = (int *)(base + p.off_rowptr);
-  if ((rc = zero_bytes(cnt, (size_t)p.nseg * g.S_i * 4, stream))) return rc;
-  if ((rc = dcn3_lists_launch(p, t, cnt, rowptr, base + p.off_entries, p.det ? base + p.off_sort : nullptr, stream))) return rc;
-  return dcn3_gather_launch(p, t, rowptr, base + p.off_entries, stream);
+  rc = scatter_lists_build(L, ws, p.det, stream, [&](bool fill, int *cnt, const int *rowptr, void *entries) {
+#define DCN3_LIST(DT, CT) samp_list_launch<Dcn3Op, CT>(g, fill, t.offset, t.mask, cnt, rowptr, entries, L.seg_stride, stream)
+    DCN3_DISPATCH(p, DCN3_LIST);
+#undef DCN3_LIST
+  });
+  if (rc) return rc;
+  const SampGather ga = {g.B, g.S_i, g.S_o, g.G, g.D, g.C, g.ln, g.acc};
+  return samp_gather_launch(ga, p.dtype, L.seg_stride, t.grad_output, (const int *)((char *)ws + L.off_rowptr),
+                            (char *)ws + L.off_entries, t.grad_input, stream);
 }
 
 }  // namespace mdconv

@@ -3,7 +3,7 @@
 //
 // Lists: per (image, deformable group, input pixel) one entry per corner the reference scatters to -- {sample = tap * S_o +
 // pixel, scatter weight x mask, tap, pixel} -- built in the three passes of the fp32 matrix family (count with integer
-// atomics, exclusive scan with csr_scan_chunk, fill); in deterministic mode csr_sort_rows brings every list into canonical
+// atomics, exclusive scan, fill: scatter_lists_build); in deterministic mode csr_sort_rows brings every list into canonical
 // order (ascending sample; a sample reaches a pixel through one corner).  The lists do not depend on the channel.
 // Gather: lane = input pixel, workgroup = 256 pixels of one image x a slab of CS channels of one deformable group.  A lane
 // walks its list once and rebuilds grad_col(c, tap, p) = sum_m w[cM + m, tap] * go[cM + m, p] for its CS channels on the fly
@@ -15,10 +15,6 @@
 namespace mdconv {
 
 namespace {
-
-__global__ __launch_bounds__(256) void dw_scan_kernel(int S, const int *__restrict__ cnt, int *__restrict__ rowptr) {
-  csr_scan_chunk(S, cnt, rowptr);   // mdconv_common.hpp
-}
 
 // thread = sample (image, deformable group, tap, output pixel).  FILL false: count the entries per target; true: after the
 // scan, take slots from the back of each list (the counters run down to zero) and write the entries.
@@ -119,30 +115,23 @@ int dw_weight_table_launch(const DwPlan &p, const float *weight, float *wt, hipS
   return check_launch("dw_weight_table");
 }
 
-int dw_lists_launch(const DwPlan &p, const Tensors &t, int *cnt, int *rowptr, void *entries, void *sort_scratch, hipStream_t stream) {
+void dw_list_launch(const DwPlan &p, const Tensors &t, bool fill, int *cnt, const int *rowptr, void *entries, hipStream_t stream) {
   const Geom &g = p.g;
   const int64_t samples = (int64_t)g.B * g.DG * g.K * g.S_o;   // < 2^29: the offset tensor is below 2^31 bytes
   const dim3 grid(grid_1d(samples));
-  int rc;
 #define DW_LIST(ND, FILL)                                                                                              \
   hipLaunchKernelGGL((dw_list_kernel<ND, FILL>), grid, dim3(256), 0, stream, g, (const float *)t.offset, (const float *)t.mask, \
-                     cnt, (const int *)rowptr, (int4 *)entries, p.seg_stride)
-  if (g.nd == 2) DW_LIST(2, false); else DW_LIST(3, false);
-  if ((rc = check_launch("dw_list_count"))) return rc;
-  hipLaunchKernelGGL(dw_scan_kernel, dim3((g.S_i + kScanChunk - 1) / kScanChunk, p.nseg), dim3(256), 0, stream, g.S_i, cnt, rowptr);
-  if ((rc = check_launch("dw_scan"))) return rc;
-  if (g.nd == 2) DW_LIST(2, true); else DW_LIST(3, true);
+                     cnt, rowptr, (int4 *)entries, p.lists.seg_stride)
+  if (fill) { if (g.nd == 2) DW_LIST(2, true); else DW_LIST(3, true); }
+  else { if (g.nd == 2) DW_LIST(2, false); else DW_LIST(3, false); }
 #undef DW_LIST
-  if ((rc = check_launch("dw_list_fill"))) return rc;
-  if (!sort_scratch) return MDCONV_OK;
-  return csr_sort_rows(rowptr, entries, sort_scratch, 1, g.S_i, p.seg_stride, p.nseg, stream);
 }
 
 int dw_gather_launch(const DwPlan &p, const Tensors &t, const int *rowptr, const void *entries, const float *wt, hipStream_t stream) {
   const Geom &g = p.g;
   const dim3 grid(g.B * ((g.S_i + 255) / 256), g.C / p.cs_gi);
 #define DW_GATHER(M, CS)                                                                                               \
-  hipLaunchKernelGGL((dw_gather_kernel<M, CS>), grid, dim3(256), 0, stream, g, p.seg_stride, (const float *)t.grad_output, wt, \
+  hipLaunchKernelGGL((dw_gather_kernel<M, CS>), grid, dim3(256), 0, stream, g, p.lists.seg_stride, (const float *)t.grad_output, wt, \
                      rowptr, (const int4 *)entries, (float *)t.grad_input)
 #define DW_GATHER_CS(M) do { if (p.cs_gi == 8) DW_GATHER(M, 8); else DW_GATHER(M, 4); } while (0)
   switch (p.M) {

@@ -42,8 +42,6 @@ bool dw_plan(const Geom &g, int dtype, bool backward, DwPlan *p, Skip skip, cons
     if (cs < 1) cs = 1;
     if ((int64_t)g.DG * cs > 65535) { *why = "deformable_groups exceeds the grid"; return false; }
     q.csplit = cs;
-    q.nseg = g.B * g.DG;
-    q.seg_stride = seg_stride;
     Bump ws;
     q.off_goff = ws.take(cs > 1 ? (size_t)cs * n_off * 4 : 0);
     q.off_gm = ws.take(cs > 1 && g.modulated ? (size_t)cs * (n_off / g.nd) * 4 : 0);
@@ -55,10 +53,7 @@ bool dw_plan(const Geom &g, int dtype, bool backward, DwPlan *p, Skip skip, cons
     }
     if (!q.skip.input) {
       q.off_wt = ws.take((size_t)g.O * g.K * 4);
-      q.off_cnt = ws.take((size_t)q.nseg * g.S_i * 4);
-      q.off_rowptr = ws.take((size_t)q.nseg * (g.S_i + 1) * 4);
-      q.off_entries = ws.take((size_t)q.nseg * (size_t)seg_stride * 16);
-      q.off_sort = ws.take(g.det ? csr_sort_scratch_bytes(1, seg_stride, q.nseg) : 0);
+      q.lists = scatter_lists_take(ws, g.B * g.DG, g.S_i, seg_stride, g.det != 0);
     }
     q.total = ws.off;
   }
@@ -101,12 +96,13 @@ int dw_backward(const DwPlan &p, const Tensors &t, void *ws, hipStream_t stream)
       return rc;
   }
   if (p.skip.input) return MDCONV_OK;
-  int *cnt = (int *)(base + p.off_cnt), *rowptr = (int *)(base + p.off_rowptr);
   float *wt = (float *)(base + p.off_wt);
-  if ((rc = zero_bytes(cnt, (size_t)p.nseg * g.S_i * 4, stream))) return rc;
   if ((rc = dw_weight_table_launch(p, (const float *)t.weight, wt, stream))) return rc;
-  if ((rc = dw_lists_launch(p, t, cnt, rowptr, base + p.off_entries, g.det ? base + p.off_sort : nullptr, stream))) return rc;
-  return dw_gather_launch(p, t, rowptr, base + p.off_entries, wt, stream);
+  rc = scatter_lists_build(p.lists, ws, g.det != 0, stream, [&](bool fill, int *cnt, const int *rowptr, void *entries) {
+    dw_list_launch(p, t, fill, cnt, rowptr, entries, stream);
+  });
+  if (rc) return rc;
+  return dw_gather_launch(p, t, (const int *)(base + p.lists.off_rowptr), base + p.lists.off_entries, wt, stream);
 }
 
 }  // namespace mdconv

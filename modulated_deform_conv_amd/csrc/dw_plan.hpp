@@ -24,11 +24,11 @@ struct DwPlan {
   int csplit;         // workgroups per (pixel tile, deformable group); > 1: grad_offset / grad_mask go through partial slices
   int row_len;        // floats per partial row: C_out * K weight sums, then C_out bias sums (with bias)
   int row_groups;     // rows of the second reduce stage (0: one stage)
-  // backward, grad_input (dw_gi.hip): scatter lists per (image, deformable group, input pixel), one entry per corner
-  int nseg;           // B * DG
-  int64_t seg_stride; // entries per segment: K * S_o * 2^nd
+  // backward, grad_input (dw_gi.hip): scatter lists per (image, deformable group, input pixel), one entry per corner:
+  // B * DG segments of S_i lists, K * S_o * 2^nd entries per segment
+  ScatterLists lists;
   int cs_gi;          // channels per thread of the gather (8 / 4)
-  size_t off_goff, off_gm, off_wpart, off_wstage, off_wt, off_cnt, off_rowptr, off_entries, off_sort;
+  size_t off_goff, off_gm, off_wpart, off_wstage, off_wt;
   size_t total;       // workspace bytes
 };
 
@@ -46,7 +46,8 @@ int dw_bwd_coord_launch(const DwPlan &p, const Tensors &t, float *part_off, floa
 // dst[grp][e] (+)= sum over the rows r of group grp, in row order, of src[r * stride + e]: groups of `group` rows, e < len
 int dw_reduce_rows(const float *src, int64_t stride, int nrows, int len, int group, float *dst, int64_t dst_stride, bool acc,
                    hipStream_t stream);
-int dw_lists_launch(const DwPlan &p, const Tensors &t, int *cnt, int *rowptr, void *entries, void *sort_scratch, hipStream_t stream);
+// the list kernel, counting or filling (the callable of scatter_lists_build)
+void dw_list_launch(const DwPlan &p, const Tensors &t, bool fill, int *cnt, const int *rowptr, void *entries, hipStream_t stream);
 int dw_weight_table_launch(const DwPlan &p, const float *weight, float *wt, hipStream_t stream);   // wt[tap][C_out]
 int dw_gather_launch(const DwPlan &p, const Tensors &t, const int *rowptr, const void *entries, const float *wt, hipStream_t stream);
 

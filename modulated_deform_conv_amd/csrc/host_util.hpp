@@ -19,6 +19,16 @@ struct Bump {
   }
 };
 
+// the slots of scatter lists (ScatterLists, mdconv_common.hpp); the sort scratch only in deterministic mode
+inline ScatterLists scatter_lists_take(Bump &ws, int nseg, int rows, int64_t seg_stride, bool det) {
+  ScatterLists L = {nseg, rows, seg_stride};
+  L.off_cnt = ws.take((size_t)nseg * rows * 4);
+  L.off_rowptr = ws.take((size_t)nseg * (rows + 1) * 4);
+  L.off_entries = ws.take((size_t)nseg * (size_t)seg_stride * 16);
+  L.off_sort = ws.take(det ? csr_sort_scratch_bytes(1, seg_stride, nseg) : 0);
+  return L;
+}
+
 // the geometry of `bc` images of a call
 inline Geom chunk_geom(const Geom &g, int bc) {
   Geom c = g;

@@ -9,6 +9,7 @@
 #include <hip/hip_runtime.h>
 #include <hip/hip_fp16.h>
 #include <stdint.h>
+#include <functional>
 
 #include "../../include/mdconv.h"
 
@@ -351,41 +352,7 @@ __device__ __forceinline__ void sample_anchor(const Geom &g, const TapCoef<ND, f
   sa.on = on;
 }
 
-// ---- sampling state of the DCNv3 core operator (dcn3_*.hip; include/mdconv.h "DCNv3 core operator") ----
-// A sibling of make_tap for that operator's own position formula and gate; the four reference flavours above are not
-// involved.  The sample at (loc_h, loc_w) has the neighbours (y0 + cy, x0 + cx), corner ci = 2 * cy + cx, with the bilinear
-// weights (cy ? ly : 1 - ly) * (cx ? lx : 1 - lx).  A corner is READ iff the sample passes the gate -1 < loc < size on both
-// axes and the corner lies inside the image; every other corner contributes nothing to any result and is never loaded.
-struct Dcn3Sample {
-  float lx, ly;   // fractional parts
-  int x0, y0;     // low neighbour (may be -1)
-  bool inside;    // the gate
-};
-__device__ __forceinline__ void dcn3_sample(float loc_h, float loc_w, int H, int W, Dcn3Sample &s) {
-  s.inside = loc_h > -1.f && loc_w > -1.f && loc_h < (float)H && loc_w < (float)W;
-  // clamp before the int conversion so wild offsets (and NaN, which fails the gate) cannot overflow
-  const float yc = s.inside ? loc_h : 0.f, xc = s.inside ? loc_w : 0.f;
-  const float fy = floorf(yc), fx = floorf(xc);
-  s.y0 = (int)fy;
-  s.x0 = (int)fx;
-  s.ly = yc - fy;
-  s.lx = xc - fx;
-}
-__device__ __forceinline__ bool dcn3_corner_read(const Dcn3Sample &s, int ci, int H, int W) {
-  const int y = s.y0 + (ci >> 1), x = s.x0 + (ci & 1);
-  return s.inside && y >= 0 && y < H && x >= 0 && x < W;
-}
-__device__ __forceinline__ int dcn3_corner_pixel(const Dcn3Sample &s, int ci, int W) {
-  return (s.y0 + (ci >> 1)) * W + s.x0 + (ci & 1);
-}
-__device__ __forceinline__ float dcn3_corner_weight(float lx, float ly, int ci) {
-  return ((ci >> 1) ? ly : 1.f - ly) * ((ci & 1) ? lx : 1.f - lx);
-}
-// d(weight)/d(loc_w) and d(weight)/d(loc_h) of corner ci
-__device__ __forceinline__ float dcn3_corner_dx(float ly, int ci) { return ((ci >> 1) ? ly : 1.f - ly) * ((ci & 1) ? 1.f : -1.f); }
-__device__ __forceinline__ float dcn3_corner_dy(float lx, int ci) { return ((ci & 1) ? lx : 1.f - lx) * ((ci >> 1) ? 1.f : -1.f); }
-
-// ---- exclusive scan of the scatter-list counters (shared by csr_scan_kernel and hp_csr_scan_kernel) ----
+// ---- exclusive scan of the scatter-list counters (shared by csr_scan_kernel, hp_csr_scan_kernel and lists_scan_kernel) ----
 // cnt[seg][0..S) -> rowptr[seg][0..S]; grid (chunks of kScanChunk elements, segments), 256 threads.  A workgroup first sums
 // everything before its chunk (the counters are L2-resident, at most S coalesced reads, eight loads in flight), then scans
 // its chunk in ONE pass: thread t holds elements lo + 256 j + t (j = 0..7), the eight wave scans run as independent chains,
@@ -451,6 +418,19 @@ __device__ __forceinline__ void csr_scan_chunk(int S, const int *__restrict__ cn
 size_t csr_sort_scratch_bytes(int width, int64_t seg_stride, int nseg);
 int csr_sort_rows(const int *rowptr, void *entries, void *scratch, int width, int S_e, int64_t seg_stride, int nseg,
                   hipStream_t stream);
+
+// ---- the list build of the VALU families (depthwise, DCNv3, deformable attention; csr_sort.hip) ----
+// Workspace layout of scatter lists of one int4 per entry: `nseg` segments of `rows` lists, `seg_stride` entries per
+// segment (scatter_lists_take, host_util.hpp, lays it out).
+struct ScatterLists {
+  int nseg, rows;
+  int64_t seg_stride;
+  size_t off_cnt, off_rowptr, off_entries, off_sort;
+};
+// Builds the lists in the workspace `ws` on `stream`: zero the counters, count, exclusive scan (csr_scan_chunk), fill, and
+// with `det` csr_sort_rows.  launch_list(fill, cnt, rowptr, entries) launches the family's list kernel, counting or filling.
+int scatter_lists_build(const ScatterLists &L, void *ws, bool det, hipStream_t stream,
+                        const std::function<void(bool fill, int *cnt, const int *rowptr, void *entries)> &launch_list);
 
 // ---- host-side helpers ------------------------------------------------------------------------
 int fill_geom(const mdconv_desc *d, Geom *g);  // validates; returns MDCONV_* code

@@ -1,4 +1,5 @@
-// msda_host.hip -- plan and execution of multi-scale deformable attention (msda_plan.hpp).
+// msda_host.hip -- plan and execution of multi-scale deformable attention (msda_plan.hpp): the sampling core's kernels
+// (samp_core.hpp) instantiated with MsdaOp for the five (value type, coordinate type) pairings.
 #include "msda_plan.hpp"
 
 namespace mdconv {
@@ -48,12 +49,7 @@ bool msda_plan(const mdconv_msda_desc *d, bool backward, MsdaPlan *p, const char
     g.lvS[l] = used ? start : 0;
     if (used) start += g.lvH[l] * g.lvW[l];
   }
-  g.esz = esz;
-  g.V = g.D * esz / 16;
-  g.lgVL = 0;
-  while ((1 << g.lgVL) < g.V && g.lgVL < 6) ++g.lgVL;
-  g.VL = 1 << g.lgVL;
-  g.rounds = (g.V + g.VL - 1) / g.VL;
+  g.ln = samp_lanes(g.D, esz);
   g.acc = d->accumulate;
   q.dtype = d->dtype;
   q.coord_dtype = d->coord_dtype;
@@ -62,31 +58,40 @@ bool msda_plan(const mdconv_msda_desc *d, bool backward, MsdaPlan *p, const char
   q.skip_value = skip_value;
   q.total = 0;
   if (backward && !skip_value) {
-    q.nseg = g.N * g.M;
-    q.seg_stride = seg_stride;
     Bump ws;
-    q.off_cnt = ws.take((size_t)q.nseg * g.S * 4);
-    q.off_rowptr = ws.take((size_t)q.nseg * (g.S + 1) * 4);
-    q.off_entries = ws.take((size_t)q.nseg * (size_t)seg_stride * 16);
-    q.off_sort = ws.take(q.det ? csr_sort_scratch_bytes(1, seg_stride, q.nseg) : 0);
+    q.lists = scatter_lists_take(ws, g.N * g.M, g.S, seg_stride, q.det);
     q.total = ws.off;
   }
   *p = q;
   return true;
 }
 
-int msda_forward(const MsdaPlan &p, const MsdaTensors &t, hipStream_t stream) { return msda_fwd_launch(p, t, stream); }
+int msda_forward(const MsdaPlan &p, const MsdaTensors &t, hipStream_t stream) {
+#define MSDA_FWD(DT, CT) samp_fwd_launch<MsdaOp, DT, CT>(p.g, t.value, t.loc, t.attn, t.output, stream)
+  MSDA_DISPATCH(p, MSDA_FWD);
+#undef MSDA_FWD
+  return check_launch("msda_fwd");
+}
 
 int msda_backward(const MsdaPlan &p, const MsdaTensors &t, void *ws, hipStream_t stream) {
   const MsdaGeom &g = p.g;
+  const ScatterLists &L = p.lists;
   int rc;
-  if ((rc = msda_bwd_coord_launch(p, t, stream))) return rc;
+#define MSDA_BWD(DT, CT) \
+  samp_bwd_coord_launch<MsdaOp, DT, CT>(g, t.value, t.loc, t.attn, t.grad_output, t.grad_loc, t.grad_attn, stream)
+  MSDA_DISPATCH(p, MSDA_BWD);
+#undef MSDA_BWD
+  if ((rc = check_launch("msda_bwd_coord"))) return rc;
   if (p.skip_value) return MDCONV_OK;
-  char *base = (char *)ws;
-  int *cnt = (int *)(base + p.off_cnt), *rowptr = (int *)(base + p.off_rowptr);
-  if ((rc = zero_bytes(cnt, (size_t)p.nseg * g.S * 4, stream))) return rc;
-  if ((rc = msda_lists_launch(p, t, cnt, rowptr, base + p.off_entries, p.det ? base + p.off_sort : nullptr, stream))) return rc;
-  return msda_gather_launch(p, t, rowptr, base + p.off_entries, stream);
+  rc = scatter_lists_build(L, ws, p.det, stream, [&](bool fill, int *cnt, const int *rowptr, void *entries) {
+#define MSDA_LIST(DT, CT) samp_list_launch<MsdaOp, CT>(g, fill, t.loc, t.attn, cnt, rowptr, entries, L.seg_stride, stream)
+    MSDA_DISPATCH(p, MSDA_LIST);   // (by coordinate type: three instances)
+#undef MSDA_LIST
+  });
+  if (rc) return rc;
+  const SampGather ga = {g.N, g.S, g.Lq, g.M, g.D, g.C, g.ln, g.acc};
+  return samp_gather_launch(ga, p.dtype, L.seg_stride, t.grad_output, (const int *)((char *)ws + L.off_rowptr),
+                            (char *)ws + L.off_entries, t.grad_value, stream);
 }
 
 }  // namespace mdconv

@@ -1,4 +1,4 @@
-"""Step time (forward + backward) of the DCNv3 core operator (include/mdconv.h, "DCNv3 core operator"; csrc/dcn3_*.hip)
+"""Step time (forward + backward) of the DCNv3 core operator (include/mdconv.h, "DCNv3 core operator"; csrc/dcn3_*.hip on csrc/samp_core.hpp)
 against the composed route through the existing entry points of the same build: permute to NCHW, the depthwise modulated
 2-D call with a weight of ones (groups = C, deformable_groups = G, weight gradients skipped), permute back.
 
@@ -28,11 +28,11 @@ B, KSZ = 8, 3
 SHAPES = [(56, 4, 16, 1.0), (28, 8, 16, 1.0), (14, 16, 16, 1.0), (7, 32, 16, 1.0), (56, 4, 16, 2.0)]
 
 NOTES = [
-    "## Kernel resources (`tools/kres.py dcn3_fwd | dcn3_bwd | dcn3_gi`)", "",
-    "No kernel of the family uses scratch or AGPRs; none but the scan uses LDS.  VGPRs (fp32 / fp16 / bf16 instance): "
-    "`dcn3_fwd_kernel` 54 / 58 / 60 (8 waves per SIMD); `dcn3_bwd_coord_kernel` 76 / 83 / 91 (6 / 5 / 5 waves); "
-    "`dcn3_list_kernel` 12 / 11 / 11 counting, 24 filling; `dcn3_gather_kernel` 28 / 40 / 36; `dcn3_scan_kernel` 44 with the "
-    "144 bytes of LDS of `csr_scan_chunk`.", "",
+    "## Kernel resources (`tools/kres.py dcn3_host | samp_gather | csr_sort`)", "",
+    "No kernel of the family uses scratch or AGPRs; none but the scan uses LDS.  VGPRs (fp32 / fp16 / bf16 instance of the "
+    "sampling core's kernels under `Dcn3Op`): `samp_fwd_kernel` 54 / 58 / 60 (8 waves per SIMD); `samp_bwd_coord_kernel` "
+    "76 / 83 / 91 (6 / 5 / 5 waves); `samp_list_kernel` 12 / 11 / 11 counting, 24 filling; `samp_gather_kernel` 28 / 40 / 36; "
+    "`lists_scan_kernel` 44 with the 144 bytes of LDS of `csr_scan_chunk`.", "",
 ]
 
 

@@ -72,7 +72,7 @@ NOTES = [
     "## Kernel resources (`tools/kres.py dw_fwd | dw_bwd | dw_gi`)", "",
     "No kernel of the family uses scratch.  VGPRs: `dw_fwd_kernel<ND, M, CS>` 58-82 (CS = 4), 84-118 (CS = 8), no LDS; "
     "`dw_bwd_coord_kernel<ND, M>` 79-96 in 2-D with 3 KB of LDS, 135-149 in 3-D with 4 KB; `dw_list_kernel` 18-34; "
-    "`dw_gather_kernel<M, CS>` 24-82; `dw_reduce_rows_kernel`, `dw_scan_kernel`, `dw_weight_table_kernel` below 32.", "",
+    "`dw_gather_kernel<M, CS>` 24-82; `dw_reduce_rows_kernel`, `dw_weight_table_kernel` below 32; `lists_scan_kernel` (csr_sort.hip) 44.", "",
     "## Where a step goes (one kernel trace per shape, us per launch)", "",
     "| shape | forward | coordinate / weight gradients | list count + fill | gather | small kernels (scan, table, clear, row sums) |",
     "|---|---|---|---|---|---|",

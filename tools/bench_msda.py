@@ -1,5 +1,5 @@
 """Step time (forward + backward) of multi-scale deformable attention (include/mdconv.h, "Multi-scale deformable
-attention"; csrc/msda_*.hip) against the composed route of plain PyTorch: one `F.grid_sample` per level with the permutes
+attention"; csrc/msda_*.hip on csrc/samp_core.hpp) against the composed route of plain PyTorch: one `F.grid_sample` per level with the permutes
 around it, times the attention weights, summed -- the fallback a model uses without the extension -- and its autograd
 backward.
 
@@ -31,12 +31,12 @@ PYRAMID = [(64, 64), (32, 32), (16, 16), (8, 8)]
 SHAPES = [("encoder", PYRAMID, None), ("decoder", PYRAMID, 300), ("pixel_decoder", [(32, 32), (16, 16), (8, 8)], None)]
 
 NOTES = [
-    "## Kernel resources (`tools/kres.py msda_fwd | msda_bwd | msda_gi`)", "",
+    "## Kernel resources (`tools/kres.py msda_host | samp_gather | csr_sort`)", "",
     "No kernel of the family uses scratch or AGPRs -- the level table is read through an unrolled select chain over constant "
     "indices of the kernel argument -- and none but the scan uses LDS.  VGPRs (value / coordinate type: fp32 / fp32, fp16 / fp16, "
-    "fp16 / fp32, bf16 / bf16, bf16 / fp32): `msda_fwd_kernel` 48 / 72 / 72 / 54 / 54 (8 / 7 / 7 / 8 / 8 waves per SIMD); "
-    "`msda_bwd_coord_kernel` 72 / 79 / 79 / 86 / 95 (7 / 6 / 6 / 5 / 5 waves); `msda_list_kernel` (by coordinate type, fp32 / "
-    "fp16 / bf16) 14 / 13 / 13 counting, 26 filling; `msda_gather_kernel` (by value type) 28 / 40 / 36; `msda_scan_kernel` 44 "
+    "fp16 / fp32, bf16 / bf16, bf16 / fp32; the sampling core's kernels under `MsdaOp`): `samp_fwd_kernel` 48 / 72 / 72 / 54 / 54 (8 / 7 / 7 / 8 / 8 waves per SIMD); "
+    "`samp_bwd_coord_kernel` 72 / 79 / 79 / 86 / 95 (7 / 6 / 6 / 5 / 5 waves); `samp_list_kernel` (by coordinate type, fp32 / "
+    "fp16 / bf16) 14 / 13 / 13 counting, 26 filling; `samp_gather_kernel` (by value type) 28 / 40 / 36; `lists_scan_kernel` 44 "
     "with the 144 bytes of LDS of `csr_scan_chunk`.", "",
 ]
 

@@ -16,12 +16,13 @@ for line in r.stderr.splitlines():
         cur = {"name": subprocess.run(["c++filt", m.group(1)], capture_output=True, text=True).stdout.strip()}
         rows.append(cur)
     for key, pat in (("vgpr", r" VGPRs: (\d+)"), ("agpr", r"AGPRs: (\d+)"), ("scratch", r"ScratchSize \[bytes/lane\]: (\d+)"),
-                     ("occ", r"Occupancy \[waves/SIMD\]: (\d+)"), ("sgpr", r" SGPRs: (\d+)"), ("lds", r"LDS Size \[bytes/block\]: (\d+)")):
+                     ("occ", r"Occupancy \[waves/SIMD\]: (\d+)"), ("sgpr", r"TotalSGPRs: (\d+)"), ("lds", r"LDS Size \[bytes/block\]: (\d+)")):
         m = re.search(pat, line)
         if m and cur is not None:
             cur[key] = m.group(1)
 for c in rows:
-    n = re.sub(r"^void mdconv::\(anonymous namespace\)::", "", c["name"])
+    # (a non-template kernel demangles without the "void " of its return type)
+    n = re.sub(r"^(void )?mdconv::(\(anonymous namespace\)::)?", "", c["name"])
     n = re.sub(r"\(.*$", "", n)
     if flt in n:
         print("%-70s v%-4s a%-3s s%-3s scr%-5s occ%s lds%s" % (n[:70], c.get("vgpr"), c.get("agpr"), c.get("sgpr"), c.get("scratch"), c.get("occ"), c.get("lds")))
