@@ -468,6 +468,74 @@ int mdconv_msda_backward(const mdconv_msda_desc *d, const void *value, const voi
                          void *grad_sampling_locations, void *grad_attention_weights, void *workspace,
                          size_t workspace_bytes, void *stream);
 
+/* --- DCNv4 operator: the DCNv3 core operator's sampling with one packed coordinate tensor ----------
+ * The sampling operator of the "DCNv4" block, the successor of DCNv3: no weight, no bias, no softmax over the taps -- the
+ * masks are whatever the linear layer before it produced, of any sign and size.  An operator of its own with a descriptor of
+ * its own; nothing above changes.  2-D only.  G groups of D channels; every tensor dense and row-major:
+ *     input        [B, H,  W,  G*D]          output  [B, Ho, Wo, G*D]
+ *     offset_mask  [B, Ho, Wo, OM]           OM = ceil(G*K*3 / 8) * 8        (mdconv_dcnv4_offset_mask_len)
+ *        row = for g in 0..G-1: { (x, y) of tap 0, ..., (x, y) of tap K-1, mask of tap 0, ..., mask of tap K-1 },
+ *              then OM - G*K*3 padding columns
+ *        element of (g, tap): x at g*3K + 2*tap, y at g*3K + 2*tap + 1, mask at g*3K + 2K + tap
+ *     K = kh*kw - (remove_center ? 1 : 0)
+ *     kernel-grid tap u = i*kh + j, i in [0, kw) the kernel's WIDTH index, j in [0, kh) its height index (as in DCNv3)
+ *     with remove_center the grid tap (kh*kw - 1)/2 is skipped: tensor tap t maps to u = t + (t >= (kh*kw - 1)/2)
+ *     Ho, Wo, c_h, c_w, loc_h, loc_w, the gate (-1 < loc < size) and the corner rule: exactly those of the DCNv3 core
+ *     operator above, with (i, j) taken from u
+ *     out[b,ho,wo,g,:] = sum_t mask[t] * bilinear(input[b,:,:,g,:], loc_h(t), loc_w(t))
+ *  - The padding columns of offset_mask are never read into any result (they may hold NaN).  The backward returns grad_input
+ *    and grad_offset_mask in the layouts of input and offset_mask (the offset gradients carry the factor offset_scale);
+ *    `accumulate` is the write mode of mdconv_desc.accumulate: in overwrite mode the padding columns of grad_offset_mask
+ *    come back as exact zeros, in accumulate mode they are not touched.
+ *  - dtype (MDCONV_F32, MDCONV_F16 or MDCONV_BF16) is the type of input, output, grad_output and grad_input; coord_dtype is
+ *    the type of offset_mask and its gradient: equal to dtype, or MDCONV_F32 (a bf16 offset of a few pixels resolves no
+ *    better than 1/32 px).  All arithmetic is fp32, each result is rounded once.
+ *  - Descriptor rules beyond DCNv3's (MDCONV_EINVAL): remove_center is 0 or 1, and 1 only with odd kh and kw that are not
+ *    both 1 (K = 0); coord_dtype is dtype or MDCONV_F32.
+ *  - Shape rule (else MDCONV_EUNSUPPORTED, with the rule in the error message, before anything is launched): D a multiple
+ *    of 4 for fp32 and of 8 for 16-bit values (rows of 16 bytes), every tensor -- offset_mask included -- below 2^31 bytes,
+ *    K <= 4096, and for a backward with grad_input B*G <= 65535 and K*Ho*Wo*4 below 2^31.
+ *  - flags: MDCONV_FLAG_DETERMINISTIC and MDCONV_FLAG_NO_GRAD_INPUT only; any other bit is MDCONV_EINVAL.  No result is
+ *    summed with floating-point atomics: output and grad_offset_mask are bit-identical from call to call, grad_input is with
+ *    MDCONV_FLAG_DETERMINISTIC and agrees to rounding otherwise.  With MDCONV_FLAG_NO_GRAD_INPUT grad_input may be NULL and
+ *    is never touched; grad_offset_mask is bit for bit that of the full call.  Forwards ignore both flags.
+ *  - A call checks in this order: the descriptor (MDCONV_EINVAL), the pointers (MDCONV_ENULL), the shape rule
+ *    (MDCONV_EUNSUPPORTED), the workspace (MDCONV_EWORKSPACE: size and 16-byte alignment, as above).
+ *  - The workspace figure is exact, 0 for the forward, honours both flags and does not depend on coord_dtype.  A call is a
+ *    plain chain of kernels on the caller's stream: no second stream, no host synchronisation; it captures into a HIP graph.
+ *  Written from memory of the published operator and UNPINNED against its code. */
+typedef struct mdconv_dcnv4_desc {
+  int dtype;           /* input, output, grad_output, grad_input: MDCONV_F32 / MDCONV_F16 / MDCONV_BF16 */
+  int coord_dtype;     /* offset_mask and its gradient: `dtype` or MDCONV_F32 */
+  int batch;           /* B */
+  int groups;          /* G */
+  int group_channels;  /* D */
+  int in_sz[2];        /* H, W */
+  int k_sz[2];         /* kh, kw */
+  int stride[2];       /* (h, w) */
+  int pad[2];
+  int dil[2];
+  float offset_scale;
+  int remove_center;   /* 1 = the centre tap of the (odd) kernel is left out: K = kh*kw - 1 */
+  int accumulate;      /* backward write mode: 1 = add to grad_*, 0 = overwrite */
+  int flags;           /* MDCONV_FLAG_DETERMINISTIC | MDCONV_FLAG_NO_GRAD_INPUT */
+} mdconv_dcnv4_desc;
+/* `mdconv_dcnv4_desc d = MDCONV_DCNV4_DESC_INIT;` then fill in the shape (fp32, stride 1, no padding, dilation 1,
+ * offset_scale 1, the full kernel, accumulate, no flags) */
+#define MDCONV_DCNV4_DESC_INIT { 0, 0, 0, 0, 0, {0, 0}, {0, 0}, {1, 1}, {0, 0}, {1, 1}, 1.0f, 0, 1, 0 }
+
+/* Output extent on `axis` (0 = height, 1 = width); -1 for a bad argument. */
+int mdconv_dcnv4_out_size(const mdconv_dcnv4_desc *d, int axis);
+/* OM, the elements per row of offset_mask; -1 for a bad descriptor. */
+int mdconv_dcnv4_offset_mask_len(const mdconv_dcnv4_desc *d);
+/* Scratch bytes of the forward (backward = 0: always 0) or the backward (backward = 1) of `d`; 0 for a descriptor that is
+ * invalid or outside the shape rule. */
+size_t mdconv_dcnv4_workspace_bytes(const mdconv_dcnv4_desc *d, int backward);
+int mdconv_dcnv4_forward(const mdconv_dcnv4_desc *d, const void *input, const void *offset_mask, void *output,
+                         void *workspace, size_t workspace_bytes, void *stream);
+int mdconv_dcnv4_backward(const mdconv_dcnv4_desc *d, const void *input, const void *offset_mask, const void *grad_output,
+                          void *grad_input, void *grad_offset_mask, void *workspace, size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

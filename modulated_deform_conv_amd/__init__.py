@@ -11,6 +11,9 @@ behind the reference's own operator surface.
                                                        bf16, coordinates in the same type or fp32): MSDeformAttnFunction,
                                                        ms_deform_attn, ms_deform_attn_forward / _backward, MSDeformAttn
                                                        -- also exported here
+    modulated_deform_conv_amd.dcnv4                    the DCNv4 operator (channels-last, one packed offset_mask tensor in
+                                                       the values' dtype or fp32, remove_center): DCNv4Function,
+                                                       dcnv4_core, dcnv4_forward / _backward, DCNv4 -- also exported here
     modulated_deform_conv_amd.distributed              batch-sharded multi-GPU helper (RCCL)
 
 All compute runs in libmdconv_hip.so (hand-written HIP, C ABI in include/mdconv.h); there is no
@@ -22,15 +25,19 @@ __version__ = "0.1.0"
 
 _DCNV3 = ("DCNv3Function", "dcnv3_core", "DCNv3")
 _MSDA = ("ms_deform_attn_forward", "ms_deform_attn_backward", "MSDeformAttnFunction", "ms_deform_attn", "MSDeformAttn")
-__all__ = list(_DCNV3 + _MSDA)
+_DCNV4 = ("dcnv4_forward", "dcnv4_backward", "DCNv4Function", "dcnv4_core", "DCNv4")
+__all__ = list(_DCNV3 + _MSDA + _DCNV4)
 
 
 def __getattr__(name):
-    # the DCNv3 and MSDA names resolve on first use, so importing the package stays as light as before
+    # the DCNv3, MSDA and DCNv4 names resolve on first use, so importing the package stays as light as before
     if name in _DCNV3:
         from . import dcnv3
         return getattr(dcnv3, name)
     if name in _MSDA:
         from . import msda
         return getattr(msda, name)
+    if name in _DCNV4:
+        from . import dcnv4
+        return getattr(dcnv4, name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

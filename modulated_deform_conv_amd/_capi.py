@@ -36,6 +36,8 @@ EXPORTS = (
     "mdconv_modulated_deform_conv3d_forward", "mdconv_modulated_deform_conv3d_backward",
     "mdconv_dcnv3_out_size", "mdconv_dcnv3_workspace_bytes", "mdconv_dcnv3_forward", "mdconv_dcnv3_backward",
     "mdconv_msda_value_len", "mdconv_msda_workspace_bytes", "mdconv_msda_forward", "mdconv_msda_backward",
+    "mdconv_dcnv4_out_size", "mdconv_dcnv4_offset_mask_len", "mdconv_dcnv4_workspace_bytes", "mdconv_dcnv4_forward",
+    "mdconv_dcnv4_backward",
 )
 
 
@@ -66,6 +68,15 @@ class MdconvDcnv3Desc(ctypes.Structure):
                 ("group_channels", ctypes.c_int), ("in_sz", ctypes.c_int * 2), ("k_sz", ctypes.c_int * 2),
                 ("stride", ctypes.c_int * 2), ("pad", ctypes.c_int * 2), ("dil", ctypes.c_int * 2),
                 ("offset_scale", ctypes.c_float), ("accumulate", ctypes.c_int), ("flags", ctypes.c_int)]
+
+
+class MdconvDcnv4Desc(ctypes.Structure):
+    """Mirror of ``struct mdconv_dcnv4_desc`` (include/mdconv.h, "DCNv4 operator"); axis order (h, w)."""
+    _fields_ = [("dtype", ctypes.c_int), ("coord_dtype", ctypes.c_int), ("batch", ctypes.c_int), ("groups", ctypes.c_int),
+                ("group_channels", ctypes.c_int), ("in_sz", ctypes.c_int * 2), ("k_sz", ctypes.c_int * 2),
+                ("stride", ctypes.c_int * 2), ("pad", ctypes.c_int * 2), ("dil", ctypes.c_int * 2),
+                ("offset_scale", ctypes.c_float), ("remove_center", ctypes.c_int), ("accumulate", ctypes.c_int),
+                ("flags", ctypes.c_int)]
 
 
 MSDA_MAX_LEVELS = 8   # MDCONV_MSDA_MAX_LEVELS
@@ -130,7 +141,7 @@ def lib():
             L.mdconv_planned_kernels.argtypes = [ctypes.c_void_p, ctypes.c_int]
         missing = (() if has_math_query else ("mdconv_math_bf16_used",)) + (() if has_layout_query else ("mdconv_result_layout_supported",))
         missing += () if has_plan_query else ("mdconv_planned_kernels",)
-        missing += tuple(n for n in EXPORTS if n.startswith(("mdconv_dcnv3_", "mdconv_msda_")) and not hasattr(L, n))
+        missing += tuple(n for n in EXPORTS if n.startswith(("mdconv_dcnv3_", "mdconv_msda_", "mdconv_dcnv4_")) and not hasattr(L, n))
         for name in EXPORTS[11:]:
             if name not in missing:
                 getattr(L, name).restype = ctypes.c_int
@@ -144,6 +155,12 @@ def lib():
             L.mdconv_msda_value_len.argtypes = [ctypes.c_void_p]
             L.mdconv_msda_workspace_bytes.restype = ctypes.c_size_t
             L.mdconv_msda_workspace_bytes.argtypes = [ctypes.c_void_p, ctypes.c_int]
+        # (likewise a build from before the DCNv4 operator: dcnv4.py raises there)
+        if hasattr(L, "mdconv_dcnv4_workspace_bytes"):
+            L.mdconv_dcnv4_out_size.argtypes = [ctypes.c_void_p, ctypes.c_int]
+            L.mdconv_dcnv4_offset_mask_len.argtypes = [ctypes.c_void_p]
+            L.mdconv_dcnv4_workspace_bytes.restype = ctypes.c_size_t
+            L.mdconv_dcnv4_workspace_bytes.argtypes = [ctypes.c_void_p, ctypes.c_int]
         if L.mdconv_abi_version() != ABI_VERSION:
             raise ImportError("libmdconv_hip.so ABI version mismatch")
         _lib = L

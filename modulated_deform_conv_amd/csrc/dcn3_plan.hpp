@@ -73,32 +73,52 @@ struct Dcn3Op {
     const float loc_h = px.base_h + ((float)(j * g.dh - g.ch) + off_y) * g.scale;
     samp_sample(loc_h, loc_w, g.H, g.W, s);
   }
+  // offset [.., G, K, 2] and mask [.., G, K]: element pair * K + tap of the mask, twice that of the offset
+  static __device__ __forceinline__ int coord_index(const Geom &g, const Ctx &, int pair, int tap, int xy) {
+    return 2 * (pair * g.K + tap) + xy;
+  }
+  static __device__ __forceinline__ int factor_index(const Geom &g, const Ctx &, int pair, int tap) { return pair * g.K + tap; }
+  static __device__ __forceinline__ int list_factor_index(const Geom &, int id) { return id; }
   template <int CT>
   static __device__ __forceinline__ void build_tap(const Geom &g, const Ctx &px, int pair, int tap, bool on, const void *offset,
                                                    const void *mask, SampTap &t, float &fx, float &fy) {
     samp_tap_clear(t);
     fx = fy = g.scale;
+    // (the indices are taken behind the `on` test: taken at the call they would stay live up to the kernel's stores)
     if (!on) return;
-    const int e = pair * g.K + tap;
+    tap_state<CT>(g, px, tap, offset, coord_index(g, px, pair, tap, 0), coord_index(g, px, pair, tap, 1), mask,
+                  factor_index(g, px, pair, tap), t);
+  }
+  // the state of the tap at kernel-grid position `grid_tap` from the elements ex, ey (offset) and ef (mask)
+  template <int CT>
+  static __device__ __forceinline__ void tap_state(const Geom &g, const Ctx &px, int grid_tap, const void *offset, int ex, int ey,
+                                                   const void *mask, int ef, SampTap &t) {
     SampSample s;
-    position(g, px, tap, samp_ld<CT>(offset, 2 * e), samp_ld<CT>(offset, 2 * e + 1), s);
+    position(g, px, grid_tap, samp_ld<CT>(offset, ex), samp_ld<CT>(offset, ey), s);
     t.lx = s.lx;
     t.ly = s.ly;
-    t.m = samp_ld<CT>(mask, e);
+    t.m = samp_ld<CT>(mask, ef);
 #pragma unroll
     for (int ci = 0; ci < 4; ++ci)
       if (samp_corner_read(s, ci, g.H, g.W))
         t.off[ci] = (px.img_pix + samp_corner_pixel(s, ci, g.W)) * g.C * g.ln.esz + px.grp_byte;
   }
-  // sample id = pair * K + tap; lists per (image, group, input pixel)
-  template <int CT> static __device__ __forceinline__ void list_item(const Geom &g, int id, const void *offset, SampItem &it) {
-    const int pair = id / g.K, tap = id - pair * g.K;
+  template <int CT> static __device__ __forceinline__ void finish_pair(const Geom &, const Ctx &, const SampLane &, void *) {}
+  // the item of tap `tap` of `pair`, at kernel-grid position `grid_tap`, from the elements ex, ey; lists per (image, group, input pixel)
+  template <int CT>
+  static __device__ __forceinline__ void list_item_at(const Geom &g, int pair, int tap, int grid_tap, const void *offset, int ex,
+                                                      int ey, SampItem &it) {
     const int n = pair / g.G, grp = pair - n * g.G;
     const int b = n / g.S_o, pix = n - b * g.S_o;
-    position(g, ctx(g, pair), tap, samp_ld<CT>(offset, 2 * id), samp_ld<CT>(offset, 2 * id + 1), it.s);
+    position(g, ctx(g, pair), grid_tap, samp_ld<CT>(offset, ex), samp_ld<CT>(offset, ey), it.s);
     it.H = g.H; it.W = g.W;
     it.seg = b * g.G + grp; it.row0 = 0;
     it.tap = tap; it.q = pix; it.rows_out = g.S_o;
+  }
+  // sample id = pair * K + tap
+  template <int CT> static __device__ __forceinline__ void list_item(const Geom &g, int id, const void *offset, SampItem &it) {
+    const int pair = id / g.K, tap = id - pair * g.K;
+    list_item_at<CT>(g, pair, tap, tap, offset, 2 * id, 2 * id + 1, it);
   }
 };
 #endif  // __HIPCC__

@@ -15,6 +15,7 @@
 
 #include "mdconv_common.hpp"
 #include "dcn3_plan.hpp"
+#include "dcn4_plan.hpp"
 #include "msda_plan.hpp"
 #include "dw_plan.hpp"
 #include "hp_plan.hpp"
@@ -725,6 +726,65 @@ static int dcn3_refuse(const char *why) {
   return MDCONV_EUNSUPPORTED;
 }
 
+// ---- DCNv4 operator (dcn4_plan.hpp): the descriptor's own validation; the shape rule is dcn4_plan's ----
+static int dcn4_validate(const mdconv_dcnv4_desc *d) {
+  if (!d) {
+    set_error("descriptor pointer is NULL");
+    return MDCONV_EINVAL;
+  }
+  if (d->dtype != MDCONV_F32 && d->dtype != MDCONV_F16 && d->dtype != MDCONV_BF16) {
+    set_error("dcnv4: dtype %d is not MDCONV_F32, MDCONV_F16 or MDCONV_BF16 (the dtype flags do not apply)", d->dtype);
+    return MDCONV_EINVAL;
+  }
+  if (d->coord_dtype != d->dtype && d->coord_dtype != MDCONV_F32) {
+    set_error("dcnv4: coord_dtype %d is neither dtype (%d) nor MDCONV_F32", d->coord_dtype, d->dtype);
+    return MDCONV_EINVAL;
+  }
+  if (d->batch <= 0 || d->groups <= 0 || d->group_channels <= 0) {
+    set_error("dcnv4: batch, groups and group_channels must be positive (%d, %d, %d)", d->batch, d->groups, d->group_channels);
+    return MDCONV_EINVAL;
+  }
+  for (int a = 0; a < 2; ++a) {
+    if (d->in_sz[a] <= 0 || d->k_sz[a] <= 0 || d->stride[a] <= 0 || d->dil[a] <= 0 || d->pad[a] < 0) {
+      set_error("dcnv4: bad geometry on axis %d (in_sz=%d, k_sz=%d, stride=%d, pad=%d, dil=%d)", a, d->in_sz[a], d->k_sz[a],
+                d->stride[a], d->pad[a], d->dil[a]);
+      return MDCONV_EINVAL;
+    }
+    const long long span = (long long)d->dil[a] * (d->k_sz[a] - 1) + 1;
+    if ((long long)d->in_sz[a] + 2LL * d->pad[a] < span) {
+      set_error("dcnv4: the output extent on axis %d is below 1 (in_sz=%d, pad=%d, dilated kernel %lld)", a, d->in_sz[a],
+                d->pad[a], span);
+      return MDCONV_EINVAL;
+    }
+  }
+  if (d->remove_center != 0 && d->remove_center != 1) {
+    set_error("dcnv4: remove_center must be 0 or 1, is %d", d->remove_center);
+    return MDCONV_EINVAL;
+  }
+  if (d->remove_center && (d->k_sz[0] % 2 == 0 || d->k_sz[1] % 2 == 0 || (d->k_sz[0] == 1 && d->k_sz[1] == 1))) {
+    set_error("dcnv4: remove_center needs an odd kernel with a tap left (%d x %d)", d->k_sz[0], d->k_sz[1]);
+    return MDCONV_EINVAL;
+  }
+  if (d->accumulate != 0 && d->accumulate != 1) {
+    set_error("dcnv4: accumulate must be 0 or 1, is %d", d->accumulate);
+    return MDCONV_EINVAL;
+  }
+  if (d->flags & ~(MDCONV_FLAG_DETERMINISTIC | MDCONV_FLAG_NO_GRAD_INPUT)) {
+    set_error("dcnv4: unknown bits 0x%x in flags; the flags are MDCONV_FLAG_DETERMINISTIC (1) and MDCONV_FLAG_NO_GRAD_INPUT (4)",
+              (unsigned)(d->flags & ~(MDCONV_FLAG_DETERMINISTIC | MDCONV_FLAG_NO_GRAD_INPUT)));
+    return MDCONV_EINVAL;
+  }
+  if (!(d->offset_scale == d->offset_scale) || d->offset_scale - d->offset_scale != 0.f) {
+    set_error("dcnv4: offset_scale is not finite");
+    return MDCONV_EINVAL;
+  }
+  return MDCONV_OK;
+}
+static int dcn4_refuse(const char *why) {
+  set_error("dcnv4: outside the shape rule of the operator: %s", why);
+  return MDCONV_EUNSUPPORTED;
+}
+
 // ---- multi-scale deformable attention (msda_plan.hpp): the descriptor's own validation; the shape rule is msda_plan's ----
 static int msda_validate(const mdconv_msda_desc *d) {
   if (!d) {
@@ -1039,6 +1099,69 @@ int mdconv_dcnv3_backward(const mdconv_dcnv3_desc *d, const void *input, const v
   t.input = input; t.offset = offset; t.mask = mask; t.grad_output = grad_output;
   t.grad_input = grad_input; t.grad_offset = grad_offset; t.grad_mask = grad_mask;
   return dcn3_backward(p, t, workspace, (hipStream_t)stream);
+}
+
+int mdconv_dcnv4_out_size(const mdconv_dcnv4_desc *d, int axis) {
+  if (!d || axis < 0 || axis > 1 || d->stride[axis] <= 0) return -1;
+  return (d->in_sz[axis] + 2 * d->pad[axis] - (d->dil[axis] * (d->k_sz[axis] - 1) + 1)) / d->stride[axis] + 1;
+}
+
+int mdconv_dcnv4_offset_mask_len(const mdconv_dcnv4_desc *d) {
+  g_err[0] = 0;
+  if (dcn4_validate(d)) return -1;
+  const long long K = (long long)d->k_sz[0] * d->k_sz[1] - d->remove_center;   // below 2^62
+  if (K >= (1LL << 31) / 3 / d->groups) {   // G * K * 3 + 7 stays below 2^31
+    set_error("dcnv4: a row of offset_mask has 2^31 elements or more");
+    return -1;
+  }
+  return (int)dcn4_row_len(d->groups, K);
+}
+
+size_t mdconv_dcnv4_workspace_bytes(const mdconv_dcnv4_desc *d, int backward) {
+  Dcn4Plan p;
+  const char *why;
+  g_err[0] = 0;
+  if (dcn4_validate(d)) return 0;
+  if (!dcn4_plan(d, backward != 0, &p, &why)) {
+    dcn4_refuse(why);
+    return 0;
+  }
+  return p.total;
+}
+
+int mdconv_dcnv4_forward(const mdconv_dcnv4_desc *d, const void *input, const void *offset_mask, void *output,
+                         void *workspace, size_t workspace_bytes, void *stream) {
+  g_err[0] = 0;
+  int rc = dcn4_validate(d);
+  if (rc) return rc;
+  if ((rc = require(input, "input")) || (rc = require(offset_mask, "offset_mask")) || (rc = require(output, "output")))
+    return rc;
+  Dcn4Plan p;
+  const char *why;
+  if (!dcn4_plan(d, false, &p, &why)) return dcn4_refuse(why);
+  if ((rc = check_ws(workspace, workspace_bytes, p.total))) return rc;
+  Dcn4Tensors t = {};
+  t.input = input; t.offset_mask = offset_mask; t.output = output;
+  return dcn4_forward(p, t, (hipStream_t)stream);
+}
+
+int mdconv_dcnv4_backward(const mdconv_dcnv4_desc *d, const void *input, const void *offset_mask, const void *grad_output,
+                          void *grad_input, void *grad_offset_mask, void *workspace, size_t workspace_bytes, void *stream) {
+  g_err[0] = 0;
+  int rc = dcn4_validate(d);
+  if (rc) return rc;
+  if ((rc = require(input, "input")) || (rc = require(offset_mask, "offset_mask")) ||
+      (rc = require(grad_output, "grad_output")) || (rc = require(grad_offset_mask, "grad_offset_mask")))
+    return rc;
+  if (!(d->flags & MDCONV_FLAG_NO_GRAD_INPUT) && (rc = require(grad_input, "grad_input"))) return rc;
+  Dcn4Plan p;
+  const char *why;
+  if (!dcn4_plan(d, true, &p, &why)) return dcn4_refuse(why);
+  if ((rc = check_ws(workspace, workspace_bytes, p.total))) return rc;
+  Dcn4Tensors t = {};
+  t.input = input; t.offset_mask = offset_mask; t.grad_output = grad_output;
+  t.grad_input = grad_input; t.grad_offset_mask = grad_offset_mask;
+  return dcn4_backward(p, t, workspace, (hipStream_t)stream);
 }
 
 int mdconv_msda_value_len(const mdconv_msda_desc *d) {

@@ -73,12 +73,20 @@ struct MsdaOp {
     for (int i = 1; i < MDCONV_MSDA_MAX_LEVELS; ++i)
       if (l == i) { H = g.lvH[i]; W = g.lvW[i]; start = g.lvS[i]; }
   }
-  // the sample of element e = pair * K + tap of the coordinate tensors, in the pixel coordinates of its level
-  template <int CT> static __device__ __forceinline__ void position(const void *loc, int e, int H, int W, SampSample &s) {
-    const float x = samp_ld<CT>(loc, 2 * e) * (float)W - 0.5f;
-    const float y = samp_ld<CT>(loc, 2 * e + 1) * (float)H - 0.5f;
+  // the sample whose x is element ec of sampling_locations (y follows), in the pixel coordinates of its level
+  template <int CT> static __device__ __forceinline__ void position(const void *loc, int ec, int H, int W, SampSample &s) {
+    const float x = samp_ld<CT>(loc, ec) * (float)W - 0.5f;
+    const float y = samp_ld<CT>(loc, ec + 1) * (float)H - 0.5f;
     samp_sample(y, x, H, W, s);
   }
+  // sampling_locations [.., M, L, P, 2] and attention_weights [.., M, L, P]: element e = pair * K + tap of the weights,
+  // twice that of the locations
+  static __device__ __forceinline__ int coord_index(const Geom &g, const Ctx &, int pair, int tap, int xy) {
+    return 2 * (pair * g.K + tap) + xy;
+  }
+  static __device__ __forceinline__ int factor_index(const Geom &g, const Ctx &, int pair, int tap) { return pair * g.K + tap; }
+  static __device__ __forceinline__ int list_factor_index(const Geom &, int id) { return id; }
+  template <int CT> static __device__ __forceinline__ void finish_pair(const Geom &, const Ctx &, const SampLane &, void *) {}
   // fx, fy: the extents of the tap's level, W for x and H for y (the positions are normalised)
   template <int CT>
   static __device__ __forceinline__ void build_tap(const Geom &g, const Ctx &pair_byte, int pair, int tap, bool on, const void *loc,
@@ -90,12 +98,12 @@ struct MsdaOp {
     level(g, tap / g.P, H, W, start);
     fx = (float)W;
     fy = (float)H;
-    const int e = pair * g.K + tap;
+    const int ec = coord_index(g, pair_byte, pair, tap, 0), ef = factor_index(g, pair_byte, pair, tap);
     SampSample s;
-    position<CT>(loc, e, H, W, s);
+    position<CT>(loc, ec, H, W, s);
     t.lx = s.lx;
     t.ly = s.ly;
-    t.m = samp_ld<CT>(attn, e);
+    t.m = samp_ld<CT>(attn, ef);
 #pragma unroll
     for (int ci = 0; ci < 4; ++ci)
       if (samp_corner_read(s, ci, H, W)) t.off[ci] = pair_byte + (start + samp_corner_pixel(s, ci, W)) * g.C * g.ln.esz;
@@ -109,7 +117,7 @@ struct MsdaOp {
     it.seg = n * g.M + m;
     it.tap = tap; it.q = q; it.rows_out = g.Lq;
     level(g, tap / g.P, it.H, it.W, it.row0);
-    position<CT>(loc, id, it.H, it.W, it.s);
+    position<CT>(loc, 2 * id, it.H, it.W, it.s);
   }
 };
 #endif  // __HIPCC__

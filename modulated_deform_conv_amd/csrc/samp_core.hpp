@@ -13,8 +13,16 @@
 //   Op::Geom                       the kernel argument (POD, by value); it has K, D, acc and the lane geometry `ln`
 //   Op::npairs(g), Op::sampled_bytes(g)
 //   Op::Ctx, Op::ctx(g, pair)      what the taps of a pair have in common
-//   Op::build_tap<CT>(...)         the SampTap of (pair, tap), and the factors fx, fy of the x and y gradient sums
+//   Op::coord_index(g, cx, pair, tap, xy)   the element of `coord` that holds x (xy = 0) / y (xy = 1) of (pair, tap)
+//   Op::factor_index(g, cx, pair, tap)   the element of `factor` that holds the factor of (pair, tap)
+//   Op::build_tap<CT>(...)         the SampTap of (pair, tap), read from those two elements, and the factors fx, fy of the x
+//                                  and y gradient sums
+//   Op::finish_pair<CT>(...)       what the coordinate backward owes the gradient tensors beyond the taps (row padding)
 //   Op::list_rows(g), Op::list_item<CT>(g, id, coord, it)   the scatter lists: targets per segment, and sample id -> SampItem
+//   Op::list_factor_index(g, id)   factor_index by sample id = pair * K + tap
+// The policy owns the addressing: the kernels never form an element index themselves, and the gradients go to the elements
+// their forward values came from.  `coord` and `factor` may therefore be ONE tensor (the packed offset_mask rows of
+// Dcn4Op), and so may grad_coord and grad_factor; see the qualifiers of samp_bwd_coord_kernel.
 #pragma once
 #include "host_util.hpp"
 #include "mfma_tile.hpp"   // raw buffer loads
@@ -226,6 +234,13 @@ __global__ __launch_bounds__(256) void samp_fwd_kernel(typename Op::Geom g, cons
 // butterfly inside the wave: a fixed order, every lane ends with the same bits.  Lane j keeps the sums of tap t0 + j, so after
 // VL taps each lane stores one factor gradient and one (x, y) pair -- times the factor and the operator's fx, fy -- next to
 // its neighbours', in the coordinate type and in the caller's write mode.
+// On `__restrict__` now that coord / factor, and grad_coord / grad_factor, may each be ONE tensor: the qualifier promises that
+// an OBJECT modified during the call is reached through one of the qualified pointers only -- it speaks of the elements
+// accessed, not of the allocations.  coord and factor are only read, so for them it promises nothing aliasing could break.
+// Of the gradient tensor every element is reached through exactly one pointer: an (x, y) element (Op::coord_index) through
+// grad_coord, a factor element (Op::factor_index) through grad_factor, row padding (Op::finish_pair) through grad_coord; the
+// two index sets of a policy are disjoint, accumulate mode reads an element through the pointer that then writes it, and
+// samp_st stores exactly the element's 2 or 4 bytes.  So the promise holds and the qualifiers stay.
 template <class Op, int DT, int CT>
 __global__ __launch_bounds__(256) void samp_bwd_coord_kernel(typename Op::Geom g, const void *__restrict__ sampled,
                                                               const void *__restrict__ coord, const void *__restrict__ factor,
@@ -288,12 +303,12 @@ __global__ __launch_bounds__(256) void samp_bwd_coord_kernel(typename Op::Geom g
       }
     }
     if (my_on) {
-      const int e = ln.pair * g.K + my_tap;
-      samp_st<CT>(grad_factor, e, r_m, g.acc != 0);
-      samp_st<CT>(grad_coord, 2 * e, r_x, g.acc != 0);
-      samp_st<CT>(grad_coord, 2 * e + 1, r_y, g.acc != 0);
+      samp_st<CT>(grad_factor, Op::factor_index(g, cx, ln.pair, my_tap), r_m, g.acc != 0);
+      samp_st<CT>(grad_coord, Op::coord_index(g, cx, ln.pair, my_tap, 0), r_x, g.acc != 0);
+      samp_st<CT>(grad_coord, Op::coord_index(g, cx, ln.pair, my_tap, 1), r_y, g.acc != 0);
     }
   }
+  Op::template finish_pair<CT>(g, cx, ln, grad_coord);
 }
 
 // ---- scatter lists of the sampled tensor's gradient (scatter_lists_build, mdconv_common.hpp) ----
@@ -305,8 +320,9 @@ struct SampItem {
   int seg, row0;  // the segment, and the row of pixel (0, 0) inside it
   int tap, q, rows_out;   // q: the sample's row of grad_output inside its image, of rows_out
 };
-// thread = sample, in the order of `coord` and `factor`, so both are read coalesced.  FILL false: count the entries per
-// target; true: after the scan, take slots from the back of each list (the counters run down to zero) and write the entries.
+// thread = sample, in the order of `coord` and `factor` (which may be one tensor; both are only read), so both are read
+// coalesced.  FILL false: count the entries per target; true: after the scan, take slots from the back of each list (the
+// counters run down to zero) and write the entries.
 template <class Op, int CT, bool FILL>
 __global__ __launch_bounds__(256) void samp_list_kernel(typename Op::Geom g, const void *__restrict__ coord,
                                                          const void *__restrict__ factor, int *__restrict__ cnt,
@@ -315,7 +331,7 @@ __global__ __launch_bounds__(256) void samp_list_kernel(typename Op::Geom g, con
   const int total = Op::npairs(g) * g.K;   // elements of `factor`: below 2^30
   const int id = blockIdx.x * 256 + threadIdx.x;
   if (id >= total) return;
-  const float f = FILL ? samp_ld<CT>(factor, id) : 1.f;
+  const float f = FILL ? samp_ld<CT>(factor, Op::list_factor_index(g, id)) : 1.f;
   SampItem it;
   Op::template list_item<CT>(g, id, coord, it);
   const int rows = Op::list_rows(g);

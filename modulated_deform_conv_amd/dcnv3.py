@@ -178,7 +178,7 @@ class DCNv3(nn.Module):
     Everything but the core operator is a framework operator.  Module and parameter names follow the published block
     (``dw_conv.0``, ``dw_conv.1.1``, ``offset``, ``mask``, ``input_proj``, ``output_proj``) so that a checkpoint can load --
     written from memory of that code and UNPINNED against it; the ``center_feature_scale`` and
-    ``remove_center`` variants are not provided."""
+    ``remove_center`` variants are not provided (``remove_center`` is an option of the DCNv4 operator, ``dcnv4.py``)."""
 
     def __init__(self, channels=64, kernel_size=3, dw_kernel_size=None, stride=1, pad=1, dilation=1, group=4,
                  offset_scale=1.0):
