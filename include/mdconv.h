@@ -536,6 +536,72 @@ int mdconv_dcnv4_forward(const mdconv_dcnv4_desc *d, const void *input, const vo
 int mdconv_dcnv4_backward(const mdconv_dcnv4_desc *d, const void *input, const void *offset_mask, const void *grad_output,
                           void *grad_input, void *grad_offset_mask, void *workspace, size_t workspace_bytes, void *stream);
 
+/* --- Packed deformable attention: multi-scale deformable attention with one packed tensor and its softmax inside ----
+ * The second operator of the "DCNv4" package ("FlashDeformAttn"), which bears the relation to multi-scale deformable
+ * attention above that the DCNv4 operator bears to DCNv3: the locations and the attention LOGITS arrive in one tensor, as the
+ * linear layers produced them, and the softmax over the K = L*P taps of a (query, head) runs inside the operator.  An
+ * operator of its own with a descriptor of its own; nothing above changes.  N, M, D, Lq, L, P, S and `value` as for
+ * multi-scale deformable attention; every tensor dense and row-major:
+ *     value              [N, S, M, D]
+ *     sampling_loc_attn  [N, Lq, M, 3K]        (mdconv_fda_loc_attn_len; no padding columns)
+ *        row of a (query, head) = { (x, y) of tap 0, ..., (x, y) of tap K-1, logit of tap 0, ..., logit of tap K-1 }
+ *        tap = l*P + p;  x at 2*tap, y at 2*tap + 1 (normalised, as above), logit at 2K + tap
+ *     output             [N, Lq, M*D]
+ *     a[t] = exp(logit[t] - max_s logit[s]) / sum_s exp(logit[s] - max_s logit[s])        (fp32)
+ *     out[n,q,m,:] = sum_t a[t] * bilinear(value[n, start_l + ., m, :], y_t, x_t)
+ *     pixel coordinates, level starts, the gate (-1 < loc < size) and the corner rule: exactly those of multi-scale
+ *     deformable attention above
+ *  - The logits must be finite.  They may be large: the maximum is subtracted before the exponential.
+ *  - The backward returns grad_value and grad_sampling_loc_attn in the layouts of value and sampling_loc_attn: the location
+ *    gradients are those of multi-scale deformable attention with a[t] as the weight, the logit gradient is
+ *    a[t] * (g[t] - sum_s a[s] g[s]) with g[t] the gradient that operator returns for the weight of tap t.  It takes no
+ *    `output`: the sum is taken from fp32 sums inside the call.  `accumulate` is the write mode of mdconv_desc.accumulate.
+ *  - dtype (MDCONV_F32, MDCONV_F16 or MDCONV_BF16) is the type of value, output, grad_output and grad_value; coord_dtype is
+ *    the type of sampling_loc_attn and its gradient: equal to dtype, or MDCONV_F32.  All arithmetic is fp32, the softmax
+ *    included, each result is rounded once.
+ *  - Shape rule (else MDCONV_EUNSUPPORTED, with the rule in the error message, before anything is launched): that of
+ *    multi-scale deformable attention -- D a multiple of 4 for fp32 and of 8 for 16-bit values, every tensor below 2^31
+ *    bytes, L*P <= 4096, and for a backward with grad_value N*M <= 65535 and L*P*Lq*4 below 2^31 -- with sampling_loc_attn,
+ *    N*Lq*M*3K elements, among the tensors.
+ *  - flags: MDCONV_FLAG_DETERMINISTIC and MDCONV_FLAG_NO_GRAD_INPUT only (the latter: no grad_value); any other bit is
+ *    MDCONV_EINVAL.  No result is summed with floating-point atomics: output and grad_sampling_loc_attn are bit-identical
+ *    from call to call, grad_value is with MDCONV_FLAG_DETERMINISTIC and agrees to rounding otherwise.  With
+ *    MDCONV_FLAG_NO_GRAD_INPUT grad_value may be NULL and is never touched; grad_sampling_loc_attn is bit for bit that of the
+ *    full call.  Forwards ignore both flags.
+ *  - A call checks in this order: the descriptor (MDCONV_EINVAL), the pointers (MDCONV_ENULL), the shape rule
+ *    (MDCONV_EUNSUPPORTED), the workspace (MDCONV_EWORKSPACE: size and 16-byte alignment, as above).
+ *  - The workspace figure is exact, 0 for the forward, and honours both flags: a backward with grad_value takes the scatter
+ *    lists of multi-scale deformable attention for the same shape plus 8 bytes per (query, head).  A call is a plain chain of
+ *    kernels on the caller's stream: no second stream, no host synchronisation; it captures into a HIP graph.
+ *  Written from memory of the published operator and UNPINNED against its code. */
+typedef struct mdconv_fda_desc {
+  int dtype;           /* value, output, grad_output, grad_value: MDCONV_F32 / MDCONV_F16 / MDCONV_BF16 */
+  int coord_dtype;     /* sampling_loc_attn and its gradient: `dtype` or MDCONV_F32 */
+  int batch;           /* N */
+  int heads;           /* M */
+  int head_channels;   /* D */
+  int queries;         /* Lq */
+  int levels;          /* L, 1..MDCONV_MSDA_MAX_LEVELS */
+  int points;          /* P */
+  int level_sz[MDCONV_MSDA_MAX_LEVELS][2];  /* (H_l, W_l) of the first `levels` rows; the others are ignored */
+  int accumulate;      /* backward write mode: 1 = add to grad_*, 0 = overwrite */
+  int flags;           /* MDCONV_FLAG_DETERMINISTIC | MDCONV_FLAG_NO_GRAD_INPUT */
+} mdconv_fda_desc;
+/* `mdconv_fda_desc d = MDCONV_FDA_DESC_INIT;` then fill in the shape (fp32, accumulate, no flags) */
+#define MDCONV_FDA_DESC_INIT { 0, 0, 0, 0, 0, 0, 0, 0, {{0, 0}}, 1, 0 }
+
+/* S, the rows of `value` per image: the sum of H_l*W_l over the levels; -1 for a bad descriptor. */
+int mdconv_fda_value_len(const mdconv_fda_desc *d);
+/* 3K = 3*L*P, the elements of sampling_loc_attn per (query, head); -1 for a bad descriptor. */
+int mdconv_fda_loc_attn_len(const mdconv_fda_desc *d);
+/* Scratch bytes of the forward (backward = 0: always 0) or the backward (backward = 1) of `d`; 0 for a descriptor that is
+ * invalid or outside the shape rule. */
+size_t mdconv_fda_workspace_bytes(const mdconv_fda_desc *d, int backward);
+int mdconv_fda_forward(const mdconv_fda_desc *d, const void *value, const void *sampling_loc_attn, void *output,
+                       void *workspace, size_t workspace_bytes, void *stream);
+int mdconv_fda_backward(const mdconv_fda_desc *d, const void *value, const void *sampling_loc_attn, const void *grad_output,
+                        void *grad_value, void *grad_sampling_loc_attn, void *workspace, size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -14,6 +14,11 @@ behind the reference's own operator surface.
     modulated_deform_conv_amd.dcnv4                    the DCNv4 operator (channels-last, one packed offset_mask tensor in
                                                        the values' dtype or fp32, remove_center): DCNv4Function,
                                                        dcnv4_core, dcnv4_forward / _backward, DCNv4 -- also exported here
+    modulated_deform_conv_amd.fda                      packed deformable attention (one packed tensor of locations and
+                                                       attention logits per (query, head), the softmax inside the
+                                                       operator): FlashDeformAttnFunction, flash_deform_attn,
+                                                       flash_deform_attn_forward / _backward, FlashDeformAttn,
+                                                       pack_loc_attn / unpack_loc_attn -- also exported here
     modulated_deform_conv_amd.distributed              batch-sharded multi-GPU helper (RCCL)
 
 All compute runs in libmdconv_hip.so (hand-written HIP, C ABI in include/mdconv.h); there is no
@@ -26,11 +31,13 @@ __version__ = "0.1.0"
 _DCNV3 = ("DCNv3Function", "dcnv3_core", "DCNv3")
 _MSDA = ("ms_deform_attn_forward", "ms_deform_attn_backward", "MSDeformAttnFunction", "ms_deform_attn", "MSDeformAttn")
 _DCNV4 = ("dcnv4_forward", "dcnv4_backward", "DCNv4Function", "dcnv4_core", "DCNv4")
-__all__ = list(_DCNV3 + _MSDA + _DCNV4)
+_FDA = ("flash_deform_attn_forward", "flash_deform_attn_backward", "FlashDeformAttnFunction", "flash_deform_attn",
+        "FlashDeformAttn", "pack_loc_attn", "unpack_loc_attn")
+__all__ = list(_DCNV3 + _MSDA + _DCNV4 + _FDA)
 
 
 def __getattr__(name):
-    # the DCNv3, MSDA and DCNv4 names resolve on first use, so importing the package stays as light as before
+    # the DCNv3, MSDA, DCNv4 and packed-attention names resolve on first use, so importing the package stays as light as before
     if name in _DCNV3:
         from . import dcnv3
         return getattr(dcnv3, name)
@@ -40,4 +47,7 @@ def __getattr__(name):
     if name in _DCNV4:
         from . import dcnv4
         return getattr(dcnv4, name)
+    if name in _FDA:
+        from . import fda
+        return getattr(fda, name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

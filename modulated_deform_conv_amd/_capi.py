@@ -38,6 +38,7 @@ EXPORTS = (
     "mdconv_msda_value_len", "mdconv_msda_workspace_bytes", "mdconv_msda_forward", "mdconv_msda_backward",
     "mdconv_dcnv4_out_size", "mdconv_dcnv4_offset_mask_len", "mdconv_dcnv4_workspace_bytes", "mdconv_dcnv4_forward",
     "mdconv_dcnv4_backward",
+    "mdconv_fda_value_len", "mdconv_fda_loc_attn_len", "mdconv_fda_workspace_bytes", "mdconv_fda_forward", "mdconv_fda_backward",
 )
 
 
@@ -91,6 +92,12 @@ class MdconvMsdaDesc(ctypes.Structure):
                 ("accumulate", ctypes.c_int), ("flags", ctypes.c_int)]
 
 
+class MdconvFdaDesc(ctypes.Structure):
+    """Mirror of ``struct mdconv_fda_desc`` (include/mdconv.h, "Packed deformable attention"): the fields of
+    ``MdconvMsdaDesc``; ``level_sz`` rows are (H, W)."""
+    _fields_ = list(MdconvMsdaDesc._fields_)
+
+
 _lib = None
 
 
@@ -141,7 +148,7 @@ def lib():
             L.mdconv_planned_kernels.argtypes = [ctypes.c_void_p, ctypes.c_int]
         missing = (() if has_math_query else ("mdconv_math_bf16_used",)) + (() if has_layout_query else ("mdconv_result_layout_supported",))
         missing += () if has_plan_query else ("mdconv_planned_kernels",)
-        missing += tuple(n for n in EXPORTS if n.startswith(("mdconv_dcnv3_", "mdconv_msda_", "mdconv_dcnv4_")) and not hasattr(L, n))
+        missing += tuple(n for n in EXPORTS if n.startswith(("mdconv_dcnv3_", "mdconv_msda_", "mdconv_dcnv4_", "mdconv_fda_")) and not hasattr(L, n))
         for name in EXPORTS[11:]:
             if name not in missing:
                 getattr(L, name).restype = ctypes.c_int
@@ -161,6 +168,12 @@ def lib():
             L.mdconv_dcnv4_offset_mask_len.argtypes = [ctypes.c_void_p]
             L.mdconv_dcnv4_workspace_bytes.restype = ctypes.c_size_t
             L.mdconv_dcnv4_workspace_bytes.argtypes = [ctypes.c_void_p, ctypes.c_int]
+        # (likewise a build from before packed deformable attention: fda.py raises there)
+        if hasattr(L, "mdconv_fda_workspace_bytes"):
+            L.mdconv_fda_value_len.argtypes = [ctypes.c_void_p]
+            L.mdconv_fda_loc_attn_len.argtypes = [ctypes.c_void_p]
+            L.mdconv_fda_workspace_bytes.restype = ctypes.c_size_t
+            L.mdconv_fda_workspace_bytes.argtypes = [ctypes.c_void_p, ctypes.c_int]
         if L.mdconv_abi_version() != ABI_VERSION:
             raise ImportError("libmdconv_hip.so ABI version mismatch")
         _lib = L

@@ -48,7 +48,7 @@ struct Dcn3Pix {   // what the taps of one (output pixel, group) have in common
 };
 
 // The operator policy of the sampling core: coord = offset (x, y per tap), factor = mask, sampled tensor = input.
-struct Dcn3Op {
+struct Dcn3Op : SampPlainFactor {
   typedef Dcn3Geom Geom;
   typedef Dcn3Pix Ctx;
   static __host__ __device__ __forceinline__ int npairs(const Geom &g) { return g.N * g.G; }

@@ -48,7 +48,7 @@ struct Dcn4Pix : Dcn3Pix {
 
 // The operator policy of the sampling core: coord = factor = offset_mask, sampled tensor = input.  Pairs, context, positions
 // and lists are Dcn3Op's; what differs is where a (pair, tap) lives in the row, and which kernel-grid position it has.
-struct Dcn4Op {
+struct Dcn4Op : SampPlainFactor {
   typedef Dcn4Geom Geom;
   typedef Dcn4Pix Ctx;
   static __host__ __device__ __forceinline__ int npairs(const Geom &g) { return Dcn3Op::npairs(g); }

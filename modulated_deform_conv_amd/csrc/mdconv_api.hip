@@ -17,6 +17,7 @@
 #include "dcn3_plan.hpp"
 #include "dcn4_plan.hpp"
 #include "msda_plan.hpp"
+#include "fda_plan.hpp"
 #include "dw_plan.hpp"
 #include "hp_plan.hpp"
 #include "mfma_plan.hpp"
@@ -785,48 +786,55 @@ static int dcn4_refuse(const char *why) {
   return MDCONV_EUNSUPPORTED;
 }
 
-// ---- multi-scale deformable attention (msda_plan.hpp): the descriptor's own validation; the shape rule is msda_plan's ----
-static int msda_validate(const mdconv_msda_desc *d) {
+// ---- multi-scale deformable attention (msda_plan.hpp) and packed deformable attention (fda_plan.hpp), whose descriptors have
+// the same fields: the descriptor's own validation under the operator's name; the shape rules are msda_plan's / fda_plan's ----
+template <class Desc> static int attn_validate(const Desc *d, const char *op) {
   if (!d) {
     set_error("descriptor pointer is NULL");
     return MDCONV_EINVAL;
   }
   if (d->dtype != MDCONV_F32 && d->dtype != MDCONV_F16 && d->dtype != MDCONV_BF16) {
-    set_error("msda: dtype %d is not MDCONV_F32, MDCONV_F16 or MDCONV_BF16 (the dtype flags do not apply)", d->dtype);
+    set_error("%s: dtype %d is not MDCONV_F32, MDCONV_F16 or MDCONV_BF16 (the dtype flags do not apply)", op, d->dtype);
     return MDCONV_EINVAL;
   }
   if (d->coord_dtype != d->dtype && d->coord_dtype != MDCONV_F32) {
-    set_error("msda: coord_dtype %d is neither dtype (%d) nor MDCONV_F32", d->coord_dtype, d->dtype);
+    set_error("%s: coord_dtype %d is neither dtype (%d) nor MDCONV_F32", op, d->coord_dtype, d->dtype);
     return MDCONV_EINVAL;
   }
   if (d->batch <= 0 || d->heads <= 0 || d->head_channels <= 0 || d->queries <= 0 || d->points <= 0) {
-    set_error("msda: batch, heads, head_channels, queries and points must be positive (%d, %d, %d, %d, %d)", d->batch, d->heads,
+    set_error("%s: batch, heads, head_channels, queries and points must be positive (%d, %d, %d, %d, %d)", op, d->batch, d->heads,
               d->head_channels, d->queries, d->points);
     return MDCONV_EINVAL;
   }
   if (d->levels < 1 || d->levels > MDCONV_MSDA_MAX_LEVELS) {
-    set_error("msda: levels must be 1..%d, is %d", MDCONV_MSDA_MAX_LEVELS, d->levels);
+    set_error("%s: levels must be 1..%d, is %d", op, MDCONV_MSDA_MAX_LEVELS, d->levels);
     return MDCONV_EINVAL;
   }
   for (int l = 0; l < d->levels; ++l) {
     if (d->level_sz[l][0] <= 0 || d->level_sz[l][1] <= 0) {
-      set_error("msda: level %d has a non-positive extent (%d x %d)", l, d->level_sz[l][0], d->level_sz[l][1]);
+      set_error("%s: level %d has a non-positive extent (%d x %d)", op, l, d->level_sz[l][0], d->level_sz[l][1]);
       return MDCONV_EINVAL;
     }
   }
   if (d->accumulate != 0 && d->accumulate != 1) {
-    set_error("msda: accumulate must be 0 or 1, is %d", d->accumulate);
+    set_error("%s: accumulate must be 0 or 1, is %d", op, d->accumulate);
     return MDCONV_EINVAL;
   }
   if (d->flags & ~(MDCONV_FLAG_DETERMINISTIC | MDCONV_FLAG_NO_GRAD_INPUT)) {
-    set_error("msda: unknown bits 0x%x in flags; the flags are MDCONV_FLAG_DETERMINISTIC (1) and MDCONV_FLAG_NO_GRAD_INPUT (4)",
+    set_error("%s: unknown bits 0x%x in flags; the flags are MDCONV_FLAG_DETERMINISTIC (1) and MDCONV_FLAG_NO_GRAD_INPUT (4)", op,
               (unsigned)(d->flags & ~(MDCONV_FLAG_DETERMINISTIC | MDCONV_FLAG_NO_GRAD_INPUT)));
     return MDCONV_EINVAL;
   }
   return MDCONV_OK;
 }
+static int msda_validate(const mdconv_msda_desc *d) { return attn_validate(d, "msda"); }
+static int fda_validate(const mdconv_fda_desc *d) { return attn_validate(d, "fda"); }
 static int msda_refuse(const char *why) {
   set_error("msda: outside the shape rule of the operator: %s", why);
+  return MDCONV_EUNSUPPORTED;
+}
+static int fda_refuse(const char *why) {
+  set_error("fda: outside the shape rule of the operator: %s", why);
   return MDCONV_EUNSUPPORTED;
 }
 
@@ -1226,6 +1234,76 @@ int mdconv_msda_backward(const mdconv_msda_desc *d, const void *value, const voi
   t.value = value; t.loc = sampling_locations; t.attn = attention_weights; t.grad_output = grad_output;
   t.grad_value = grad_value; t.grad_loc = grad_sampling_locations; t.grad_attn = grad_attention_weights;
   return msda_backward(p, t, workspace, (hipStream_t)stream);
+}
+
+int mdconv_fda_value_len(const mdconv_fda_desc *d) {
+  g_err[0] = 0;
+  if (fda_validate(d)) return -1;
+  long long S = 0;
+  for (int l = 0; l < d->levels; ++l) S += (long long)d->level_sz[l][0] * d->level_sz[l][1];   // (8 products below 2^62)
+  if (S >= (1LL << 31)) {
+    set_error("fda: the levels have 2^31 rows or more");
+    return -1;
+  }
+  return (int)S;
+}
+
+int mdconv_fda_loc_attn_len(const mdconv_fda_desc *d) {
+  g_err[0] = 0;
+  if (fda_validate(d)) return -1;
+  const long long len = 3LL * d->levels * d->points;
+  if (len >= (1LL << 31)) {
+    set_error("fda: a row of sampling_loc_attn has 2^31 elements or more");
+    return -1;
+  }
+  return (int)len;
+}
+
+size_t mdconv_fda_workspace_bytes(const mdconv_fda_desc *d, int backward) {
+  FdaPlan p;
+  const char *why;
+  g_err[0] = 0;
+  if (fda_validate(d)) return 0;
+  if (!fda_plan(d, backward != 0, &p, &why)) {
+    fda_refuse(why);
+    return 0;
+  }
+  return p.total;
+}
+
+int mdconv_fda_forward(const mdconv_fda_desc *d, const void *value, const void *sampling_loc_attn, void *output,
+                       void *workspace, size_t workspace_bytes, void *stream) {
+  g_err[0] = 0;
+  int rc = fda_validate(d);
+  if (rc) return rc;
+  if ((rc = require(value, "value")) || (rc = require(sampling_loc_attn, "sampling_loc_attn")) || (rc = require(output, "output")))
+    return rc;
+  FdaPlan p;
+  const char *why;
+  if (!fda_plan(d, false, &p, &why)) return fda_refuse(why);
+  if ((rc = check_ws(workspace, workspace_bytes, p.total))) return rc;
+  FdaTensors t = {};
+  t.value = value; t.loc_attn = sampling_loc_attn; t.output = output;
+  return fda_forward(p, t, (hipStream_t)stream);
+}
+
+int mdconv_fda_backward(const mdconv_fda_desc *d, const void *value, const void *sampling_loc_attn, const void *grad_output,
+                        void *grad_value, void *grad_sampling_loc_attn, void *workspace, size_t workspace_bytes, void *stream) {
+  g_err[0] = 0;
+  int rc = fda_validate(d);
+  if (rc) return rc;
+  if ((rc = require(value, "value")) || (rc = require(sampling_loc_attn, "sampling_loc_attn")) ||
+      (rc = require(grad_output, "grad_output")) || (rc = require(grad_sampling_loc_attn, "grad_sampling_loc_attn")))
+    return rc;
+  if (!(d->flags & MDCONV_FLAG_NO_GRAD_INPUT) && (rc = require(grad_value, "grad_value"))) return rc;
+  FdaPlan p;
+  const char *why;
+  if (!fda_plan(d, true, &p, &why)) return fda_refuse(why);
+  if ((rc = check_ws(workspace, workspace_bytes, p.total))) return rc;
+  FdaTensors t = {};
+  t.value = value; t.loc_attn = sampling_loc_attn; t.grad_output = grad_output;
+  t.grad_value = grad_value; t.grad_loc_attn = grad_sampling_loc_attn;
+  return fda_backward(p, t, workspace, (hipStream_t)stream);
 }
 
 }  // extern "C"

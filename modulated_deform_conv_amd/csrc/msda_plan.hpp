@@ -54,7 +54,7 @@ int msda_backward(const MsdaPlan &p, const MsdaTensors &t, void *ws, hipStream_t
 #ifdef __HIPCC__
 // The operator policy of the sampling core: coord = sampling_locations, factor = attention_weights, sampled tensor = value.
 // What the taps of a pair have in common (Ctx): the byte offset of (image n, value row 0, head m) in `value`.
-struct MsdaOp {
+struct MsdaOp : SampPlainFactor {
   typedef MsdaGeom Geom;
   typedef int Ctx;
   static __host__ __device__ __forceinline__ int npairs(const Geom &g) { return g.npairs; }
@@ -94,11 +94,17 @@ struct MsdaOp {
     samp_tap_clear(t);
     fx = fy = 1.f;
     if (!on) return;
+    tap_state<CT>(g, pair_byte, tap, loc, coord_index(g, pair_byte, pair, tap, 0), attn, factor_index(g, pair_byte, pair, tap), t,
+                  fx, fy);
+  }
+  // the state of tap `tap` (which names its level) from the elements ec (its x; y follows) and ef (its factor)
+  template <int CT>
+  static __device__ __forceinline__ void tap_state(const Geom &g, const Ctx &pair_byte, int tap, const void *loc, int ec,
+                                                   const void *attn, int ef, SampTap &t, float &fx, float &fy) {
     int H, W, start;
     level(g, tap / g.P, H, W, start);
     fx = (float)W;
     fy = (float)H;
-    const int ec = coord_index(g, pair_byte, pair, tap, 0), ef = factor_index(g, pair_byte, pair, tap);
     SampSample s;
     position<CT>(loc, ec, H, W, s);
     t.lx = s.lx;
@@ -108,16 +114,22 @@ struct MsdaOp {
     for (int ci = 0; ci < 4; ++ci)
       if (samp_corner_read(s, ci, H, W)) t.off[ci] = pair_byte + (start + samp_corner_pixel(s, ci, W)) * g.C * g.ln.esz;
   }
-  // sample id = pair * K + tap; lists per (image, head, value row over all S rows of the concatenated levels).  (The segment
-  // and the key words are stated before the level select: after it the fill instance takes 28 VGPRs instead of 26.)
-  template <int CT> static __device__ __forceinline__ void list_item(const Geom &g, int id, const void *loc, SampItem &it) {
-    const int pair = id / g.K, tap = id - pair * g.K;
+  // the item of tap `tap` of `pair` from the element ec that holds its x; lists per (image, head, value row over all S rows of
+  // the concatenated levels).  (The segment and the key words are stated before the level select: after it the fill instance
+  // takes 28 VGPRs instead of 26.)
+  template <int CT>
+  static __device__ __forceinline__ void list_item_at(const Geom &g, int pair, int tap, const void *loc, int ec, SampItem &it) {
     const int nq = pair / g.M, m = pair - nq * g.M;
     const int n = nq / g.Lq, q = nq - n * g.Lq;
     it.seg = n * g.M + m;
     it.tap = tap; it.q = q; it.rows_out = g.Lq;
     level(g, tap / g.P, it.H, it.W, it.row0);
-    position<CT>(loc, 2 * id, it.H, it.W, it.s);
+    position<CT>(loc, ec, it.H, it.W, it.s);
+  }
+  // sample id = pair * K + tap
+  template <int CT> static __device__ __forceinline__ void list_item(const Geom &g, int id, const void *loc, SampItem &it) {
+    const int pair = id / g.K, tap = id - pair * g.K;
+    list_item_at<CT>(g, pair, tap, loc, 2 * id, it);
   }
 };
 #endif  // __HIPCC__

@@ -9,7 +9,7 @@
 // most 64) are adjacent and the pairs of a pixel follow each other, so a wave's stores and each of its corner loads are
 // contiguous 16-byte pieces.  Heads of more than 64 vectors (D > 256 fp32) take `rounds` > 1 passes over the vectors.
 //
-// An operator policy `Op` (Dcn3Op, MsdaOp) supplies only what differs:
+// An operator policy `Op` (Dcn3Op, MsdaOp, Dcn4Op, FdaOp) supplies only what differs:
 //   Op::Geom                       the kernel argument (POD, by value); it has K, D, acc and the lane geometry `ln`
 //   Op::npairs(g), Op::sampled_bytes(g)
 //   Op::Ctx, Op::ctx(g, pair)      what the taps of a pair have in common
@@ -23,6 +23,12 @@
 // The policy owns the addressing: the kernels never form an element index themselves, and the gradients go to the elements
 // their forward values came from.  `coord` and `factor` may therefore be ONE tensor (the packed offset_mask rows of
 // Dcn4Op), and so may grad_coord and grad_factor; see the qualifiers of samp_bwd_coord_kernel.
+// A policy whose factor is a FUNCTION of the stored elements of its pair (FdaOp: a softmax over the pair's logits) also has
+//   Op::begin_pair<CT>(g, cx, ln, factor)   the pair's statistics into its context, taken by the pair's lanes together
+//   Op::kPairSum, Op::factor_grad(a, gsum, s_pair)   the stored gradient of (pair, tap) from the tap's factor a, the sum
+//                                  gsum the coordinate backward holds for it, and s_pair = sum over the pair's taps of a * gsum
+//   Op::list_factor(g, id, raw)    the factor of sample id from its stored element
+// and every other policy inherits the identities of SampPlainFactor.
 #pragma once
 #include "host_util.hpp"
 #include "mfma_tile.hpp"   // raw buffer loads
@@ -183,6 +189,16 @@ __device__ __forceinline__ SampTap samp_tap_from(const SampTap &mine, int src) {
   return t;
 }
 
+// What a policy inherits whose factor IS the stored element (a mask, an attention weight): no statistics, the factor's
+// gradient is the sum the coordinate backward holds, and the lists take the element as it stands.
+struct SampPlainFactor {
+  static constexpr bool kPairSum = false;
+  template <int CT, class G, class C>
+  static __device__ __forceinline__ void begin_pair(const G &, C &, const SampLane &, const void *) {}
+  static __device__ __forceinline__ float factor_grad(float, float gsum, float) { return gsum; }
+  template <class G> static __device__ __forceinline__ float list_factor(const G &, int, float raw) { return raw; }
+};
+
 // ---- forward ----
 // Taps outside: the VL lanes of a pair build the sampling state of VL consecutive taps at once -- lane j the state of tap
 // t0 + j, from one coordinate pair and one factor -- and then walk those taps together, each state broadcast from the lane that
@@ -194,7 +210,8 @@ __global__ __launch_bounds__(256) void samp_fwd_kernel(typename Op::Geom g, cons
                                                         void *__restrict__ output) {
   constexpr int NV = SampVec<DT>::NV;
   const SampLane ln = samp_lane_of(g.ln.lgVL, Op::npairs(g));
-  const typename Op::Ctx cx = Op::ctx(g, ln.pair);
+  typename Op::Ctx cx = Op::ctx(g, ln.pair);
+  Op::template begin_pair<CT>(g, cx, ln, factor);
   const rsrc_t r_in = make_rsrc(sampled, Op::sampled_bytes(g));
   for (int rd = 0; rd < g.ln.rounds; ++rd) {   // one round unless a head has more than 64 vectors
     const int v = rd * g.ln.VL + ln.j;
@@ -227,13 +244,66 @@ __global__ __launch_bounds__(256) void samp_fwd_kernel(typename Op::Geom g, cons
   }
 }
 
+// ---- the pair sum of a policy with kPairSum ----
+// s_pair = sum over the taps of the pair of factor x (the weighted dot products of the tap), which is the dot product of the
+// pair's grad_output row with its output row in fp32 -- taken from fp32 sums of this call, never from a stored (rounded)
+// output.  A walk over the taps before the walk of samp_bwd_coord_kernel, with that kernel's loads and none of its
+// derivative arithmetic: a lane adds up factor x its own partial dot products over every tap and round, and ONE butterfly
+// over the pair's lanes ends it, so every lane of the pair returns the same bits.
+template <class Op, int DT, int CT>
+__device__ __forceinline__ float samp_pair_sum(const typename Op::Geom &g, const typename Op::Ctx &cx, const SampLane &ln,
+                                               const rsrc_t &r_in, const rsrc_t &r_go, unsigned go_row,
+                                               const float (&go0)[SampVec<DT>::NV], const void *coord, const void *factor) {
+  constexpr int NV = SampVec<DT>::NV;
+  float sum = 0.f;
+  for (int t0 = 0; t0 < g.K; t0 += g.ln.VL) {
+    SampTap mine;
+    float fx, fy;
+    Op::template build_tap<CT>(g, cx, ln.pair, t0 + ln.j, ln.live && t0 + ln.j < g.K, coord, factor, mine, fx, fy);
+    const int nt = min(g.ln.VL, g.K - t0);
+    for (int jj = 0; jj < nt; ++jj) {
+      const SampTap t = g.ln.VL > 1 ? samp_tap_from(mine, ln.first + jj) : mine;
+      float s_m = 0.f;
+      for (int rd = 0; rd < g.ln.rounds; ++rd) {
+        const int v = rd * g.ln.VL + ln.j;
+        const bool on = ln.live && v < g.ln.V;
+        const unsigned vbyte = on ? (unsigned)v * 16u : (unsigned)kSampOob;
+        float go[NV];
+        if (rd == 0) {
+#pragma unroll
+          for (int i = 0; i < NV; ++i) go[i] = go0[i];
+        } else {
+          samp_unpack<DT>(buf_load4(r_go, (int)min(go_row + vbyte, (unsigned)kSampOob), 0), go);
+        }
+        float4 raw[4];
+#pragma unroll
+        for (int ci = 0; ci < 4; ++ci) raw[ci] = buf_load4(r_in, (int)min((unsigned)t.off[ci] + vbyte, (unsigned)kSampOob), 0);
+#pragma unroll
+        for (int ci = 0; ci < 4; ++ci) {
+          float x[NV];
+          samp_unpack<DT>(raw[ci], x);
+          float dot = 0.f;
+#pragma unroll
+          for (int i = 0; i < NV; ++i) dot = fmaf(go[i], x[i], dot);
+          s_m = fmaf(samp_corner_weight(t.lx, t.ly, ci), dot, s_m);
+        }
+      }
+      sum = fmaf(t.m, s_m, sum);
+    }
+  }
+  for (int d = g.ln.VL >> 1; d >= 1; d >>= 1) sum += __shfl_xor(sum, d, 64);
+  return sum;
+}
+
 // ---- coordinate gradients, without atomics ----
 // The lane mapping and the tap walk of the forward.  Per (pair, tap) a lane takes the dot products of its grad_output vector
 // with the four corner vectors in-lane, weighs them three ways -- the bilinear weights (the factor's gradient), their
 // derivatives along x and along y (the coordinates' gradient) -- and the three sums over the pair's lanes are taken by an xor
 // butterfly inside the wave: a fixed order, every lane ends with the same bits.  Lane j keeps the sums of tap t0 + j, so after
 // VL taps each lane stores one factor gradient and one (x, y) pair -- times the factor and the operator's fx, fy -- next to
-// its neighbours', in the coordinate type and in the caller's write mode.
+// its neighbours', in the coordinate type and in the caller's write mode.  What is stored as the factor gradient is
+// Op::factor_grad(factor, sum, s_pair): the sum itself for a plain factor, and for a policy with kPairSum a function of the
+// pair sum as well, which samp_pair_sum takes in a walk of its own before this one.
 // On `__restrict__` now that coord / factor, and grad_coord / grad_factor, may each be ONE tensor: the qualifier promises that
 // an OBJECT modified during the call is reached through one of the qualified pointers only -- it speaks of the elements
 // accessed, not of the allocations.  coord and factor are only read, so for them it promises nothing aliasing could break.
@@ -248,12 +318,15 @@ __global__ __launch_bounds__(256) void samp_bwd_coord_kernel(typename Op::Geom g
                                                               void *__restrict__ grad_factor) {
   constexpr int NV = SampVec<DT>::NV;
   const SampLane ln = samp_lane_of(g.ln.lgVL, Op::npairs(g));
-  const typename Op::Ctx cx = Op::ctx(g, ln.pair);
+  typename Op::Ctx cx = Op::ctx(g, ln.pair);
+  Op::template begin_pair<CT>(g, cx, ln, factor);
   const rsrc_t r_in = make_rsrc(sampled, Op::sampled_bytes(g));
   const rsrc_t r_go = make_rsrc(grad_output, (size_t)Op::npairs(g) * g.D * g.ln.esz);
   const unsigned go_row = (unsigned)ln.pair * (unsigned)g.ln.V * 16u;   // the pair's channel row of grad_output
   float go0[NV];   // the first round's vector (the only one unless a head has more than 64 vectors)
   samp_unpack<DT>(buf_load4(r_go, ln.live && ln.j < g.ln.V ? (int)(go_row + (unsigned)ln.j * 16u) : kSampOob, 0), go0);
+  float s_pair = 0.f;
+  if (Op::kPairSum) s_pair = samp_pair_sum<Op, DT, CT>(g, cx, ln, r_in, r_go, go_row, go0, coord, factor);
   for (int t0 = 0; t0 < g.K; t0 += g.ln.VL) {
     const int my_tap = t0 + ln.j;
     const bool my_on = ln.live && my_tap < g.K;
@@ -297,7 +370,7 @@ __global__ __launch_bounds__(256) void samp_bwd_coord_kernel(typename Op::Geom g
         s_y += __shfl_xor(s_y, d, 64);
       }
       if (jj == ln.j) {   // t is `mine`
-        r_m = s_m;
+        r_m = Op::factor_grad(t.m, s_m, s_pair);
         r_x = s_x * (t.m * fx);
         r_y = s_y * (t.m * fy);
       }
@@ -331,7 +404,7 @@ __global__ __launch_bounds__(256) void samp_list_kernel(typename Op::Geom g, con
   const int total = Op::npairs(g) * g.K;   // elements of `factor`: below 2^30
   const int id = blockIdx.x * 256 + threadIdx.x;
   if (id >= total) return;
-  const float f = FILL ? samp_ld<CT>(factor, Op::list_factor_index(g, id)) : 1.f;
+  const float f = FILL ? Op::list_factor(g, id, samp_ld<CT>(factor, Op::list_factor_index(g, id))) : 1.f;
   SampItem it;
   Op::template list_item<CT>(g, id, coord, it);
   const int rows = Op::list_rows(g);
