@@ -363,6 +363,11 @@ int mdconv_modulated_deform_conv3d_backward(const mdconv_desc *d, const void *in
  *     out[b,ho,wo,g,d] = sum_tap mask[b,ho,wo,g,tap] * bilinear(input[b,:,:,g,d], loc_h, loc_w)
  *  - bilinear reads the four neighbours of (loc_h, loc_w); a neighbour outside the image contributes zero and is never
  *    loaded.  A sample with loc <= -1 or loc >= size on either axis contributes nothing, to the output and to every gradient.
+ *  - On the lattice (loc_h or loc_w a whole number) the interpolant has a kink and the derivative is a convention: the cell
+ *    is floor(loc) and the fractional part loc - floor(loc) = 0 belongs to it, so grad_offset is the RIGHT-SIDED derivative --
+ *    along x the difference of the neighbours at x0 + 1 and x0 (a neighbour outside the image counting as zero), weighted
+ *    along y -- and grad_input goes to the low neighbours alone.  A gated-out sample has gradient exactly zero in
+ *    grad_offset and grad_mask, also at loc == -1 and at loc == size exactly, where a step inwards would read the image.
  *  - The backward returns grad_input, grad_offset (which carries the factor offset_scale) and grad_mask in the layouts of
  *    input, offset and mask; `accumulate` is the write mode of mdconv_desc.accumulate.
  *  - dtype: MDCONV_F32, MDCONV_F16 or MDCONV_BF16, one type for all tensors of a call (no dtype flags); coordinates,
@@ -420,7 +425,11 @@ int mdconv_dcnv3_backward(const mdconv_dcnv3_desc *d, const void *input, const v
  *  - start_l is the cumulative sum of the extents before level l: the level starts are not an input.
  *  - bilinear reads the four neighbours of (y, x); a neighbour outside the level contributes zero and is never loaded.  A
  *    sample with x <= -1, y <= -1, x >= W_l or y >= H_l contributes nothing, to the output and to every gradient (the gate
- *    of the DCNv3 core operator; it equals grid_sample with zero padding and align_corners = false).
+ *    of the DCNv3 core operator).  The OUTPUT equals grid_sample with zero padding and align_corners = false everywhere, and
+ *    so do the gradients off the lattice and away from the edge of the gate.  On the lattice the derivative is that
+ *    operator's convention: the right-sided one of the cell floor(x), floor(y); and a gated-out sample has gradient exactly
+ *    zero in grad_sampling_locations and grad_attention_weights, also at x == -1 and x == W_l exactly -- at x == -1
+ *    grid_sample returns a non-zero derivative (its interpolant rises into column 0 there), this operator returns zero.
  *  - The backward returns grad_value, grad_sampling_locations (which carries the factors W_l for x and H_l for y) and
  *    grad_attention_weights in the layouts of their forward tensors; `accumulate` is the write mode of mdconv_desc.accumulate.
  *  - dtype (MDCONV_F32, MDCONV_F16 or MDCONV_BF16) is the type of value, output, grad_output and grad_value; coord_dtype is
@@ -480,8 +489,9 @@ int mdconv_msda_backward(const mdconv_msda_desc *d, const void *value, const voi
  *     K = kh*kw - (remove_center ? 1 : 0)
  *     kernel-grid tap u = i*kh + j, i in [0, kw) the kernel's WIDTH index, j in [0, kh) its height index (as in DCNv3)
  *     with remove_center the grid tap (kh*kw - 1)/2 is skipped: tensor tap t maps to u = t + (t >= (kh*kw - 1)/2)
- *     Ho, Wo, c_h, c_w, loc_h, loc_w, the gate (-1 < loc < size) and the corner rule: exactly those of the DCNv3 core
- *     operator above, with (i, j) taken from u
+ *     Ho, Wo, c_h, c_w, loc_h, loc_w, the gate (-1 < loc < size), the corner rule and the derivative on the lattice (the
+ *     right-sided one of the cell floor(loc); exactly zero for a gated-out sample, loc == -1 and loc == size included):
+ *     exactly those of the DCNv3 core operator above, with (i, j) taken from u
  *     out[b,ho,wo,g,:] = sum_t mask[t] * bilinear(input[b,:,:,g,:], loc_h(t), loc_w(t))
  *  - The padding columns of offset_mask are never read into any result (they may hold NaN).  The backward returns grad_input
  *    and grad_offset_mask in the layouts of input and offset_mask (the offset gradients carry the factor offset_scale);
@@ -549,8 +559,9 @@ int mdconv_dcnv4_backward(const mdconv_dcnv4_desc *d, const void *input, const v
  *     output             [N, Lq, M*D]
  *     a[t] = exp(logit[t] - max_s logit[s]) / sum_s exp(logit[s] - max_s logit[s])        (fp32)
  *     out[n,q,m,:] = sum_t a[t] * bilinear(value[n, start_l + ., m, :], y_t, x_t)
- *     pixel coordinates, level starts, the gate (-1 < loc < size) and the corner rule: exactly those of multi-scale
- *     deformable attention above
+ *     pixel coordinates, level starts, the gate (-1 < loc < size), the corner rule and the derivative on the lattice (the
+ *     right-sided one of the cell floor(loc); a gated-out tap has location gradients of exactly zero, loc == -1 and
+ *     loc == size included, and g[t] = 0 in the logit gradient below): exactly those of multi-scale deformable attention above
  *  - The logits must be finite.  They may be large: the maximum is subtracted before the exponential.
  *  - The backward returns grad_value and grad_sampling_loc_attn in the layouts of value and sampling_loc_attn: the location
  *    gradients are those of multi-scale deformable attention with a[t] as the weight, the logit gradient is

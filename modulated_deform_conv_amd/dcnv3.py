@@ -96,17 +96,18 @@ def dcnv3_forward(input, offset, mask, kernel, stride, pad, dilation, group, gro
 
 
 def dcnv3_backward(input, offset, mask, grad_output, kernel, stride, pad, dilation, group, group_channels, offset_scale,
-                   grads=None, need_grad_input=True, deterministic=None):
+                   grads=None, need_grad_input=True, deterministic=None, accumulate=None):
     """The backward entry point.  ``grads`` = (grad_input | None, grad_offset, grad_mask): caller-allocated buffers the
     gradients are ADDED to; without it fresh tensors are written.  ``need_grad_input`` false: grad_input is neither computed
     nor allocated (``MDCONV_FLAG_NO_GRAD_INPUT``) and None is returned there.  ``deterministic`` None follows
-    ``_capi.deterministic_mode()``.  Returns (grad_input | None, grad_offset, grad_mask)."""
+    ``_capi.deterministic_mode()``.  ``accumulate`` false with ``grads``: the caller's buffers are overwritten instead.
+    Returns (grad_input | None, grad_offset, grad_mask)."""
     if not input.is_cuda:
         raise NotImplementedError
     det = _capi.deterministic_mode() if deterministic is None else bool(deterministic)
     flags = (_capi.FLAG_DETERMINISTIC if det else 0) | (0 if need_grad_input else _capi.FLAG_NO_GRAD_INPUT)
-    d = _desc(input, kernel, stride, pad, dilation, group, group_channels, offset_scale, accumulate=int(grads is not None),
-              flags=flags)
+    d = _desc(input, kernel, stride, pad, dilation, group, group_channels, offset_scale,
+              accumulate=int(grads is not None if accumulate is None else bool(accumulate)), flags=flags)
     _check(d, input, offset, mask, grad_output=grad_output)
     if grads is None:
         grads = (torch.empty_like(input) if need_grad_input else None, torch.empty_like(offset), torch.empty_like(mask))

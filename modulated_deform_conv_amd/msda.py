@@ -122,17 +122,19 @@ def ms_deform_attn_forward(value, spatial_shapes, sampling_locations, attention_
 
 
 def ms_deform_attn_backward(value, spatial_shapes, sampling_locations, attention_weights, grad_output, grads=None,
-                            need_grad_value=True, deterministic=None):
+                            need_grad_value=True, deterministic=None, accumulate=None):
     """The backward entry point.  ``grads`` = (grad_value | None, grad_sampling_locations, grad_attention_weights):
     caller-allocated buffers the gradients are ADDED to; without it fresh tensors are written.  ``need_grad_value`` false:
     grad_value is neither computed nor allocated (``MDCONV_FLAG_NO_GRAD_INPUT``) and None is returned there.
-    ``deterministic`` None follows ``_capi.deterministic_mode()``.  Returns the three gradients in that order."""
+    ``deterministic`` None follows ``_capi.deterministic_mode()``.  ``accumulate`` false with ``grads``: the caller's
+    buffers are overwritten instead.  Returns the three gradients in that order."""
     if not value.is_cuda:
         raise NotImplementedError
     shapes = _shapes(spatial_shapes)
     det = _capi.deterministic_mode() if deterministic is None else bool(deterministic)
     flags = (_capi.FLAG_DETERMINISTIC if det else 0) | (0 if need_grad_value else _capi.FLAG_NO_GRAD_INPUT)
-    d = _desc(value, sampling_locations, shapes, accumulate=int(grads is not None), flags=flags)
+    d = _desc(value, sampling_locations, shapes,
+              accumulate=int(grads is not None if accumulate is None else bool(accumulate)), flags=flags)
     _check(d, shapes, value, sampling_locations, attention_weights, grad_output=grad_output)
     if grads is None:
         grads = (torch.empty_like(value) if need_grad_value else None, torch.empty_like(sampling_locations),

@@ -143,3 +143,28 @@ def make_inputs(B, G, D, H, W, kernel, stride=1, pad=0, dilation=1, offset_scale
     om = pack(off, m, G, K, padding)
     assert min_lattice_distance(om, H, W, *geo[:4], G, offset_scale, remove_center) >= MARGIN
     return x, om, go, geo
+
+
+def gate_of(offset_mask, H, W, kernel, stride, pad, dilation, group, offset_scale, remove_center=False):
+    """[B, Ho, Wo, G, K] bool: the sample passes the gate -1 < loc < size on both axes."""
+    off, _ = unpack(offset_mask, group, taps(kernel, remove_center))
+    loc_h, loc_w = positions(off, H, W, kernel, stride, pad, dilation, group, offset_scale, remove_center)
+    return (loc_h > -1) & (loc_w > -1) & (loc_h < H) & (loc_w < W)
+
+
+def make_lattice_inputs(mode, B, G, D, H, W, kernel, stride=1, pad=0, dilation=1, offset_scale=1.0, remove_center=False,
+                        dtype=torch.float32, coord_dtype=None, seed=0, nan_padding=False):
+    """CPU tensors (input, offset_mask, grad_output) and the geometry tuple, as ``make_inputs`` draws them, with sampling
+    positions on the lattice: the modes and the asserted conditions of ``tests.dcnv3_ref.lattice_offsets``."""
+    from tests.dcnv3_ref import lattice_offsets
+    cdt = dtype if coord_dtype is None else coord_dtype
+    gen = torch.Generator().manual_seed(seed)
+    K = taps(kernel, remove_center)
+    Ho, Wo = out_hw(H, W, kernel, stride, pad, dilation)
+    geo = (_pair(kernel), _pair(stride), _pair(pad), _pair(dilation), G, D, float(offset_scale), bool(remove_center))
+    x = torch.randn(B, H, W, G * D, generator=gen).to(dtype)
+    m = torch.randn(B, Ho, Wo, G * K, generator=gen).to(cdt)
+    go = torch.randn(B, Ho, Wo, G * D, generator=gen).to(dtype)
+    off, _ = lattice_offsets(mode, (B, Ho, Wo, G * K * 2), offset_scale,
+                             lambda o: positions(o, H, W, *geo[:4], G, offset_scale, remove_center), H, W, cdt, gen)
+    return x, pack(off, m, G, K, float("nan") if nan_padding else 0.0), go, geo

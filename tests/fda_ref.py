@@ -58,3 +58,13 @@ def make_inputs(N, M, D, shapes, Lq, P, dtype=torch.float32, coord_dtype=None, s
     gen = torch.Generator().manual_seed(seed + 1000)
     logits = (torch.randn(N, Lq, M, len(shapes), P, generator=gen) * 3 + shift).to(coord_dtype)
     return value, pack(loc, logits), go
+
+
+def make_lattice_inputs(N, M, D, shapes, P, dtype=torch.float32, coord_dtype=None, seed=0, shift=0.0):
+    """CPU tensors (value, sampling_loc_attn, grad_output) on top of ``msda_ref.make_lattice_inputs`` -- every pixel
+    coordinate an integer, its asserted conditions -- with the logits drawn as ``make_inputs`` draws them."""
+    coord_dtype = dtype if coord_dtype is None else coord_dtype
+    value, loc, _, go = MR.make_lattice_inputs(N, M, D, shapes, P, dtype=dtype, coord_dtype=coord_dtype, seed=seed)
+    gen = torch.Generator().manual_seed(seed + 1000)
+    logits = (torch.randn(N, loc.shape[1], M, len(shapes), P, generator=gen) * 3 + shift).to(coord_dtype)
+    return value, pack(loc, logits), go

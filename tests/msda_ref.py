@@ -60,9 +60,9 @@ def msda_direct(value, shapes, loc, attn):
     Lq, L, P = loc.shape[1], loc.shape[3], loc.shape[4]
     v, a = value.double(), attn.double()
     starts, _ = level_starts(shapes)
-    n_idx = torch.arange(N).view(N, 1, 1, 1).expand(N, Lq, M, P)
-    m_idx = torch.arange(M).view(1, 1, M, 1).expand(N, Lq, M, P)
-    out = torch.zeros(N, Lq, M, D, dtype=torch.float64)
+    n_idx = torch.arange(N, device=value.device).view(N, 1, 1, 1).expand(N, Lq, M, P)
+    m_idx = torch.arange(M, device=value.device).view(1, 1, M, 1).expand(N, Lq, M, P)
+    out = torch.zeros(N, Lq, M, D, dtype=torch.float64, device=value.device)
     for l, (h, w) in enumerate(shapes):
         x = loc[:, :, :, l, :, 0].double() * w - 0.5   # [N, Lq, M, P]
         y = loc[:, :, :, l, :, 1].double() * h - 0.5
@@ -109,4 +109,67 @@ def make_inputs(N, M, D, shapes, Lq, P, dtype=torch.float32, coord_dtype=None, s
             break
         loc = torch.where(near, loc.double() + 0.23 / wh, loc.double()).to(coord_dtype)
     assert min_lattice_distance(loc, shapes) >= MARGIN
+    return value, loc, attn, go
+
+
+# ---- on the lattice -------------------------------------------------------------------------------------------------
+# At an integer pixel coordinate the operator's derivative is a convention (include/mdconv.h): the right-sided one of the
+# cell floor(loc), and zero for a sample the gate leaves out, x == -1 and x == size included.  ``msda_ref`` is no reference
+# there (``F.grid_sample`` rounds to either side of the integer and has no gate at -1); ``msda_direct`` is.
+def gate_of(loc, shapes):
+    """[N, Lq, M, L, P] bool: the sample passes the gate -1 < x < W_l, -1 < y < H_l."""
+    x, y = pixel_positions(loc, shapes)
+    wh = torch.tensor([[w, h] for h, w in shapes], dtype=torch.float64)[None, None, None, :, None, :]
+    return (x > -1) & (y > -1) & (x < wh[..., 0]) & (y < wh[..., 1])
+
+
+def lattice_points(h, w, ulp_inside=False):
+    """Normalised (x, y) of every pixel coordinate (ix, iy), ix = -1 .. w, iy = -1 .. h -- both edges of the gate and one
+    step beyond -- on a level of power-of-two extents, where (i + 0.5) / size and back are exact.  ``ulp_inside`` (fp32
+    coordinates): plus x = -1 + one ulp and y = -1 + one ulp, which read column / row 0 with weight 2^-24 at full slope."""
+    assert h & (h - 1) == 0 and w & (w - 1) == 0, "power-of-two extents only: elsewhere loc * size - 0.5 is not exact"
+    pts = [((ix + 0.5) / w, (iy + 0.5) / h) for ix in range(-1, w + 1) for iy in range(-1, h + 1)]
+    if ulp_inside:
+        just_inside = torch.nextafter(torch.tensor(-1.0), torch.tensor(0.0)).item()
+        pts += [((just_inside + 0.5) / w, (min(1, h - 1) + 0.5) / h), ((min(1, w - 1) + 0.5) / w, (just_inside + 0.5) / h)]
+    return pts
+
+
+def make_lattice_inputs(N, M, D, shapes, P, dtype=torch.float32, coord_dtype=None, seed=0):
+    """CPU tensors (value, sampling_locations, attention_weights, grad_output) as ``make_inputs`` draws them, every pixel
+    coordinate an integer: point 0 of (query q, head m, level l) walks ``lattice_points`` of the level (index q + 3 m), the
+    other points sit on pixels inside the level.  Lq is what the longest enumeration needs.  fp32 coordinates add the two
+    "one ulp inside -1" points per level.  Asserted, as conditions on the inputs: distance 0 everywhere but at those
+    points, at least half of the samples inside the gate, and per level a coordinate at -1, at size - 1 and at size."""
+    coord_dtype = dtype if coord_dtype is None else coord_dtype
+    gen = torch.Generator().manual_seed(seed)
+    L = len(shapes)
+    _, S = level_starts(shapes)
+    pts = [lattice_points(h, w, coord_dtype == torch.float32) for h, w in shapes]
+    Lq = max(len(p) for p in pts)
+    value = torch.randn(N, S, M, D, generator=gen).to(dtype)
+    go = torch.randn(N, Lq, M * D, generator=gen).to(dtype)
+    attn = F.softmax(torch.randn(N, Lq, M, L * P, generator=gen), -1).view(N, Lq, M, L, P).to(coord_dtype)
+    loc = torch.zeros(N, Lq, M, L, P, 2, dtype=torch.float64)
+    for l, (h, w) in enumerate(shapes):
+        for q in range(Lq):
+            for m in range(M):
+                loc[:, q, m, l, 0] = torch.tensor(pts[l][(q + 3 * m) % len(pts[l])], dtype=torch.float64)
+        if P > 1:
+            ix = torch.randint(0, w, (N, Lq, M, P - 1), generator=gen)
+            iy = torch.randint(0, h, (N, Lq, M, P - 1), generator=gen)
+            loc[:, :, :, l, 1:, 0] = (ix + 0.5) / w
+            loc[:, :, :, l, 1:, 1] = (iy + 0.5) / h
+    assert torch.equal(loc.to(coord_dtype).double(), loc), "the locations are exact in the coordinate dtype"
+    loc = loc.to(coord_dtype)
+    x, y = pixel_positions(loc, shapes)
+    pix = torch.stack([x, y], -1)
+    off = (pix - pix.round()).abs() != 0
+    n_ulp = 2 * L * N * M * -(-Lq // min(len(p) for p in pts)) if coord_dtype == torch.float32 else 0
+    assert int(off.sum()) <= n_ulp and float((pix - pix.round()).abs().max()) <= 2.0 ** -24
+    assert float(gate_of(loc, shapes).double().mean()) >= 0.5
+    for l, (h, w) in enumerate(shapes):
+        for a, size in ((0, w), (1, h)):
+            c = pix[:, :, :, l, :, a]
+            assert bool((c == -1).any()) and bool((c == size - 1).any()) and bool((c == size).any()), (l, a)
     return value, loc, attn, go

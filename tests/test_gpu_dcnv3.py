@@ -96,7 +96,8 @@ def test_samples_wholly_outside():
 
 
 def test_forward_at_integer_positions():
-    """Corner weights exactly 0 / 1 and the loc < size edge.  Forward only: the bilinear kink sits on the lattice."""
+    """Corner weights exactly 0 / 1 and the loc < size edge.  Forward only: ``dcnv3_ref`` (``F.grid_sample``) is no reference
+    for the gradients on the lattice; the backward there is tests/test_gpu_lattice.py, against ``dcnv3_direct``."""
     from modulated_deform_conv_amd import dcnv3
     for name in ("one_lane", "rect_5x3"):
         kw = dict(CASES[name])

@@ -177,8 +177,8 @@ def test_shape_checks_name_the_row_length():
 
 
 def test_forward_at_integer_positions():
-    """Corner weights exactly 0 / 1 and the loc < size edge.  Forward only: the bilinear kink sits on the lattice, and a
-    gradient test needs inputs that keep the margin."""
+    """Corner weights exactly 0 / 1 and the loc < size edge.  Forward only; the backward on the lattice -- the right-sided
+    derivative, exact zeros outside the gate -- is tests/test_gpu_lattice.py."""
     from modulated_deform_conv_amd import dcnv4
     for name in ("one_lane", "rect_rc"):
         kw = dict(CASES[name])

@@ -18,8 +18,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def test_parity_with_lane_per_pixel_16bit_kernels_forced():
     env = dict(os.environ, MDCONV_HP_FWD="1", MDCONV_HP_BWD="1")
-    r = subprocess.run([sys.executable, "-m", "pytest", "tests/test_gpu_hp.py", "-m", "gpu", "-q", "-x",
-                        "-k", "test_hp_fp16 or test_hp_bf16 or accumulate_and_overwrite or non_finite"],
+    r = subprocess.run([sys.executable, "-m", "pytest", "tests/test_gpu_hp.py", "tests/test_gpu_lattice_conv.py", "-m", "gpu", "-q", "-x",
+                        "-k", "test_hp_fp16 or test_hp_bf16 or accumulate_and_overwrite or non_finite or lattice_16bit"],
                        cwd=ROOT, env=env, capture_output=True, text=True, timeout=1200)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-2000:]
     assert " passed" in r.stdout
@@ -30,8 +30,8 @@ def test_parity_with_the_pixel_stationary_backward_forced():
     per CU); MDCONV_HP_BWD=4 keeps hp_bwd3 wherever it is supported, so that every instance the case list reaches -- staged
     slabs, A fragments from global memory, 1 / 2 / 4 deformable groups of 16-128 channels -- is compared with the oracle."""
     env = dict(os.environ, MDCONV_HP_BWD="4")
-    r = subprocess.run([sys.executable, "-m", "pytest", "tests/test_gpu_hp.py", "tests/test_gpu_fuzz.py", "-m", "gpu", "-q", "-x",
-                        "-k", "test_hp_fp16 or test_hp_bf16 or accumulate_and_overwrite or 16bit_random_shapes"],
+    r = subprocess.run([sys.executable, "-m", "pytest", "tests/test_gpu_hp.py", "tests/test_gpu_fuzz.py", "tests/test_gpu_lattice_conv.py", "-m", "gpu",
+                        "-q", "-x", "-k", "test_hp_fp16 or test_hp_bf16 or accumulate_and_overwrite or 16bit_random_shapes or lattice_16bit"],
                        cwd=ROOT, env=env, capture_output=True, text=True, timeout=1800)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-2000:]
     assert " passed" in r.stdout

@@ -126,7 +126,8 @@ def test_samples_wholly_outside():
 def test_forward_at_integer_positions():
     """Corner weights exactly 0 / 1 and both edges of the gate: locations (i + 0.5) / size on power-of-two extents give
     the pixel coordinate i exactly, i = -1 (gated out) .. size (gated out), with x = W - 1 inside, and x = -1 + one ulp,
-    which reads column 0 with weight 2^-24.  Forward only: the bilinear kink sits on the lattice."""
+    which reads column 0 with weight 2^-24.  Forward only: ``msda_ref`` (``F.grid_sample``) is no reference for the gradients
+    on the lattice; the backward at these locations is tests/test_gpu_lattice.py, against ``msda_direct``."""
     from modulated_deform_conv_amd import msda
     shapes = [(8, 4), (2, 2)]
     N, M, D, P = 1, 2, 4, 2
