@@ -200,6 +200,10 @@ typedef struct mdconv_desc {
  *    GRAD_INPUT_CHANNELS_LAST adds nothing. */
 #define MDCONV_FLAG_OUTPUT_CHANNELS_LAST 64
 #define MDCONV_FLAG_GRAD_INPUT_CHANNELS_LAST 128
+/* MDCONV_FLAG_SOFTMAX -- a flag of the DCNv4 operator's descriptor (mdconv_dcnv4_desc.flags, below) ALONE: the masks of the
+ * packed row are logits and the operator takes their softmax itself.  Every other descriptor -- this one (reserved[4]), DCNv3,
+ * multi-scale and packed deformable attention -- refuses the bit as unknown (MDCONV_EINVAL). */
+#define MDCONV_FLAG_SOFTMAX 256
 #define MDCONV_DESC_FLAGS(d) ((d)->reserved[4])
 
 /* Initialiser of a v2 descriptor: `mdconv_desc d = MDCONV_DESC_INIT(2);` then fill in the shape.
@@ -479,7 +483,7 @@ int mdconv_msda_backward(const mdconv_msda_desc *d, const void *value, const voi
 
 /* --- DCNv4 operator: the DCNv3 core operator's sampling with one packed coordinate tensor ----------
  * The sampling operator of the "DCNv4" block, the successor of DCNv3: no weight, no bias, no softmax over the taps -- the
- * masks are whatever the linear layer before it produced, of any sign and size.  An operator of its own with a descriptor of
+ * masks are whatever the linear layer before it produced, of any sign and size -- unless MDCONV_FLAG_SOFTMAX asks for one.  An operator of its own with a descriptor of
  * its own; nothing above changes.  2-D only.  G groups of D channels; every tensor dense and row-major:
  *     input        [B, H,  W,  G*D]          output  [B, Ho, Wo, G*D]
  *     offset_mask  [B, Ho, Wo, OM]           OM = ceil(G*K*3 / 8) * 8        (mdconv_dcnv4_offset_mask_len)
@@ -505,13 +509,30 @@ int mdconv_msda_backward(const mdconv_msda_desc *d, const void *value, const voi
  *  - Shape rule (else MDCONV_EUNSUPPORTED, with the rule in the error message, before anything is launched): D a multiple
  *    of 4 for fp32 and of 8 for 16-bit values (rows of 16 bytes), every tensor -- offset_mask included -- below 2^31 bytes,
  *    K <= 4096, and for a backward with grad_input B*G <= 65535 and K*Ho*Wo*4 below 2^31.
- *  - flags: MDCONV_FLAG_DETERMINISTIC and MDCONV_FLAG_NO_GRAD_INPUT only; any other bit is MDCONV_EINVAL.  No result is
+ *  - flags: MDCONV_FLAG_DETERMINISTIC, MDCONV_FLAG_NO_GRAD_INPUT and MDCONV_FLAG_SOFTMAX (next item) only; any other bit is
+ *    MDCONV_EINVAL.  No result is
  *    summed with floating-point atomics: output and grad_offset_mask are bit-identical from call to call, grad_input is with
  *    MDCONV_FLAG_DETERMINISTIC and agrees to rounding otherwise.  With MDCONV_FLAG_NO_GRAD_INPUT grad_input may be NULL and
  *    is never touched; grad_offset_mask is bit for bit that of the full call.  Forwards ignore both flags.
+ *  - MDCONV_FLAG_SOFTMAX (256; this descriptor only): the K mask elements of a group are LOGITS, and the weight of tap t is
+ *        a[t] = exp(logit[t] - max) / sum_s exp(logit[s] - max)         (fp32, the maximum subtracted: any finite logits)
+ *    in the place of mask[t] above -- DCNv3's softmax over the masks of a group, inside the operator; nothing of the size of
+ *    the masks is materialised.  The softmax runs over ALL K tensor taps of the (output pixel, group) -- K = kh*kw - 1 with
+ *    remove_center.  Taps the gate drops are included: they count in the normaliser and add nothing to the output, which is
+ *    what a framework softmax in front of the operator does.  The padding columns stay unread.  Gradients: with g[t] the
+ *    gradient the mask of tap t has without the flag and S = sum_s a[s] g[s], the logit's gradient is a[t] * (g[t] - S);
+ *    a gated-out tap therefore has the logit gradient -a[t] * S, not zero, and offset gradients of exactly zero; when every
+ *    tap of a pair is gated out all its gradients are exactly zero; with K = 1 the weight is exactly 1 and the logit
+ *    gradient exactly 0.  S is taken from fp32 sums of the call, never from a stored output.  The forward honours this flag
+ *    (and ignores the other two, as before).  Everything else -- shape rule, order of checks, write modes, the padding of
+ *    grad_offset_mask, no floating-point atomics, determinism, one stream, HIP graphs -- is as without the flag.  Workspace:
+ *    a backward with grad_input has the figure without the flag plus 8 * B*Ho*Wo*G bytes rounded up to a 256-byte slot (the
+ *    pairs' softmax statistics, behind the lists); with MDCONV_FLAG_NO_GRAD_INPUT it is 0 and nothing is stored; the
+ *    forward's is 0.  The compile-time `softmax` switch of the published kernels is what this flag is modelled on, from
+ *    memory and UNPINNED like the rest.
  *  - A call checks in this order: the descriptor (MDCONV_EINVAL), the pointers (MDCONV_ENULL), the shape rule
  *    (MDCONV_EUNSUPPORTED), the workspace (MDCONV_EWORKSPACE: size and 16-byte alignment, as above).
- *  - The workspace figure is exact, 0 for the forward, honours both flags and does not depend on coord_dtype.  A call is a
+ *  - The workspace figure is exact, 0 for the forward, honours the flags and does not depend on coord_dtype.  A call is a
  *    plain chain of kernels on the caller's stream: no second stream, no host synchronisation; it captures into a HIP graph.
  *  Written from memory of the published operator and UNPINNED against its code. */
 typedef struct mdconv_dcnv4_desc {
@@ -528,7 +549,7 @@ typedef struct mdconv_dcnv4_desc {
   float offset_scale;
   int remove_center;   /* 1 = the centre tap of the (odd) kernel is left out: K = kh*kw - 1 */
   int accumulate;      /* backward write mode: 1 = add to grad_*, 0 = overwrite */
-  int flags;           /* MDCONV_FLAG_DETERMINISTIC | MDCONV_FLAG_NO_GRAD_INPUT */
+  int flags;           /* MDCONV_FLAG_DETERMINISTIC | MDCONV_FLAG_NO_GRAD_INPUT | MDCONV_FLAG_SOFTMAX */
 } mdconv_dcnv4_desc;
 /* `mdconv_dcnv4_desc d = MDCONV_DCNV4_DESC_INIT;` then fill in the shape (fp32, stride 1, no padding, dilation 1,
  * offset_scale 1, the full kernel, accumulate, no flags) */

@@ -6,13 +6,15 @@ behind the reference's own operator surface.
     modulated_deform_conv_amd.ops                      torch.library ops mdconv::deform_conv[_backward]
                                                        (fake kernels: torch.compile / export)
     modulated_deform_conv_amd.dcnv3                    the DCNv3 core operator (channels-last, fp32 / fp16 / bf16):
-                                                       DCNv3Function, dcnv3_core, DCNv3 -- also exported here
+                                                       DCNv3Function, dcnv3_core, DCNv3, and DCNv3Fused (the same block
+                                                       on the DCNv4 operator with its in-kernel softmax) -- also exported
+                                                       here
     modulated_deform_conv_amd.msda                     multi-scale deformable attention (channels-last, fp32 / fp16 /
                                                        bf16, coordinates in the same type or fp32): MSDeformAttnFunction,
                                                        ms_deform_attn, ms_deform_attn_forward / _backward, MSDeformAttn
                                                        -- also exported here
     modulated_deform_conv_amd.dcnv4                    the DCNv4 operator (channels-last, one packed offset_mask tensor in
-                                                       the values' dtype or fp32, remove_center): DCNv4Function,
+                                                       the values' dtype or fp32, remove_center, softmax): DCNv4Function,
                                                        dcnv4_core, dcnv4_forward / _backward, DCNv4 -- also exported here
     modulated_deform_conv_amd.fda                      packed deformable attention (one packed tensor of locations and
                                                        attention logits per (query, head), the softmax inside the
@@ -28,7 +30,7 @@ from . import _capi  # noqa: F401  (does not load the library until first use)
 
 __version__ = "0.1.0"
 
-_DCNV3 = ("DCNv3Function", "dcnv3_core", "DCNv3")
+_DCNV3 = ("DCNv3Function", "dcnv3_core", "DCNv3", "DCNv3Fused")
 _MSDA = ("ms_deform_attn_forward", "ms_deform_attn_backward", "MSDeformAttnFunction", "ms_deform_attn", "MSDeformAttn")
 _DCNV4 = ("dcnv4_forward", "dcnv4_backward", "DCNv4Function", "dcnv4_core", "DCNv4")
 _FDA = ("flash_deform_attn_forward", "flash_deform_attn_backward", "FlashDeformAttnFunction", "flash_deform_attn",

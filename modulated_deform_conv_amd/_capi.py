@@ -22,6 +22,7 @@ FLAG_NO_GRAD_WEIGHT = 8  # MDCONV_FLAG_NO_GRAD_WEIGHT: the backward leaves grad_
 FLAG_MATH_BF16 = 32      # MDCONV_FLAG_MATH_BF16: fp32 tensors may run on the bf16 matrix kernels (value 16 stays invalid)
 FLAG_OUTPUT_CHANNELS_LAST = 64        # MDCONV_FLAG_OUTPUT_CHANNELS_LAST: output (forward) / grad_output (backward) is channels-last
 FLAG_GRAD_INPUT_CHANNELS_LAST = 128   # MDCONV_FLAG_GRAD_INPUT_CHANNELS_LAST: the backward's grad_input is channels-last
+FLAG_SOFTMAX = 256       # MDCONV_FLAG_SOFTMAX: MdconvDcnv4Desc.flags alone -- the masks are logits, softmax over the taps in-kernel
 
 EXPORTS = (
     "mdconv_abi_version", "mdconv_last_error", "mdconv_out_size", "mdconv_workspace_bytes",

@@ -1,6 +1,7 @@
 // dcn4_host.hip -- plan and execution of the DCNv4 operator (dcn4_plan.hpp): the sampling core's kernels (samp_core.hpp)
-// instantiated with Dcn4Op, offset_mask in the values' type or in fp32.  offset_mask is both the core's `coord` and its
-// `factor`, grad_offset_mask both gradient tensors; the gather is the one every sampling operator shares.
+// instantiated with Dcn4Op -- and, for MDCONV_FLAG_SOFTMAX, with Dcn4SoftOp --, offset_mask in the values' type or in fp32.
+// offset_mask is both the core's `coord` and its `factor`, grad_offset_mask both gradient tensors; the gather is the one
+// every sampling operator shares.
 #include "dcn4_plan.hpp"
 
 namespace mdconv {
@@ -69,17 +70,60 @@ bool dcn4_plan(const mdconv_dcnv4_desc *d, bool backward, Dcn4Plan *p, const cha
   q.backward = backward;
   q.det = backward && (d->flags & MDCONV_FLAG_DETERMINISTIC);
   q.skip_input = skip_input;
+  q.softmax = (d->flags & MDCONV_FLAG_SOFTMAX) != 0;
+  q.off_stats = 0;
   q.total = 0;
   if (backward && !skip_input) {
     Bump ws;
     q.lists = scatter_lists_take(ws, g.B * g.G, g.S_i, seg_stride, q.det);
+    // (fda_plan's rule: the list kernels take a tap's weight from the statistics the coordinate kernel stored)
+    if (q.softmax) q.off_stats = ws.take((size_t)Dcn4Op::npairs(g) * sizeof(float2));
     q.total = ws.off;
   }
   *p = q;
   return true;
 }
 
+// the geometry of the softmax kernels: the plan's, and where the statistics go (nullptr: nobody will read them)
+static Dcn4SoftGeom dcn4_soft_geom(const Dcn4Plan &p, void *stats) {
+  Dcn4SoftGeom g;
+  (Dcn4Geom &)g = p.g;
+  g.stats = (float2 *)stats;
+  return g;
+}
+
+static int dcn4_soft_backward(const Dcn4Plan &p, const Dcn4Tensors &t, void *ws, hipStream_t stream) {
+  const ScatterLists &L = p.lists;
+  int rc;
+  // (the coordinate kernel stores the pairs' softmax statistics for the list kernels, which run behind it on the stream)
+  const Dcn4SoftGeom g = dcn4_soft_geom(p, p.skip_input ? nullptr : (char *)ws + p.off_stats);
+#define DCN4_BWD(DT, CT)                                                                                             \
+  samp_bwd_coord_launch<Dcn4SoftOp, DT, CT>(g, t.input, t.offset_mask, t.offset_mask, t.grad_output, t.grad_offset_mask, \
+                                            t.grad_offset_mask, stream)
+  DCN4_DISPATCH(p, DCN4_BWD);
+#undef DCN4_BWD
+  if ((rc = check_launch("dcn4_soft_bwd_coord"))) return rc;
+  if (p.skip_input) return MDCONV_OK;
+  rc = scatter_lists_build(L, ws, p.det, stream, [&](bool fill, int *cnt, const int *rowptr, void *entries) {
+#define DCN4_LIST(CT) \
+  samp_list_launch<Dcn4SoftOp, CT>(g, fill, t.offset_mask, t.offset_mask, cnt, rowptr, entries, L.seg_stride, stream)
+    DCN4_DISPATCH_CT(p, DCN4_LIST);
+#undef DCN4_LIST
+  });
+  if (rc) return rc;
+  const SampGather ga = {g.B, g.S_i, g.S_o, g.G, g.D, g.C, g.ln, g.acc};
+  return samp_gather_launch(ga, p.dtype, L.seg_stride, t.grad_output, (const int *)((char *)ws + L.off_rowptr),
+                            (char *)ws + L.off_entries, t.grad_input, stream);
+}
+
 int dcn4_forward(const Dcn4Plan &p, const Dcn4Tensors &t, hipStream_t stream) {
+  if (p.softmax) {
+    const Dcn4SoftGeom sg = dcn4_soft_geom(p, nullptr);
+#define DCN4_FWD(DT, CT) samp_fwd_launch<Dcn4SoftOp, DT, CT>(sg, t.input, t.offset_mask, t.offset_mask, t.output, stream)
+    DCN4_DISPATCH(p, DCN4_FWD);
+#undef DCN4_FWD
+    return check_launch("dcn4_soft_fwd");
+  }
 #define DCN4_FWD(DT, CT) samp_fwd_launch<Dcn4Op, DT, CT>(p.g, t.input, t.offset_mask, t.offset_mask, t.output, stream)
   DCN4_DISPATCH(p, DCN4_FWD);
 #undef DCN4_FWD
@@ -87,6 +131,7 @@ int dcn4_forward(const Dcn4Plan &p, const Dcn4Tensors &t, hipStream_t stream) {
 }
 
 int dcn4_backward(const Dcn4Plan &p, const Dcn4Tensors &t, void *ws, hipStream_t stream) {
+  if (p.softmax) return dcn4_soft_backward(p, t, ws, stream);
   const Dcn4Geom &g = p.g;
   const ScatterLists &L = p.lists;
   int rc;

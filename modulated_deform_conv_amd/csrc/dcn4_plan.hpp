@@ -5,8 +5,18 @@
 // positions and lists, with the addressing of the packed row.  A call is planned ONCE, like its siblings: dcn4_plan() decides
 // whether the family takes it and lays its workspace out, the byte count reported to the caller is the plan's `total`, and
 // dcn4_forward / dcn4_backward take the plan.
+//
+// With MDCONV_FLAG_SOFTMAX the masks are LOGITS and the operator takes their softmax itself -- DCNv3's softmax over the K
+// masks of a group, inside the kernel: the policy Dcn4SoftOp below, which is to Dcn4Op what FdaOp is to MsdaOp.  Semantics:
+//  - the softmax runs over ALL K tensor taps of the (output pixel, group); with remove_center K = kh * kw - 1;
+//  - taps the gate drops are included: they count in the normaliser and add nothing to the output, which is what a framework
+//    softmax in front of the operator does.  Such a tap's logit gradient is -a[t] * S (S: the pair sum), not zero; its offset
+//    gradients are exactly zero; when every tap of a pair is gated out, S = 0 and all gradients of the pair are exactly zero;
+//  - with K = 1 the weight is exactly 1 and the logit gradient exactly 0;
+//  - the padding columns of the row stay unread.
 #pragma once
 #include "dcn3_plan.hpp"
+#include "fda_plan.hpp"   // fda_weight: THE weight of a tap from (logit, max, 1 / sum)
 
 namespace mdconv {
 
@@ -15,6 +25,11 @@ struct Dcn4Geom : Dcn3Geom {
   int OM;       // elements per row of offset_mask: G * 3K rounded up to a multiple of 8
   int K3;       // 3 * K: the elements of a group
   int center;   // tensor taps from this one on sit one kernel-grid position further (remove_center); else K: none does
+};
+
+// ... and with the softmax, where the per-pair statistics go
+struct Dcn4SoftGeom : Dcn4Geom {
+  float2 *stats;   // backward with grad_input: (max, 1 / sum) per pair, in the workspace; else nullptr
 };
 
 struct Dcn4Tensors {
@@ -28,7 +43,9 @@ struct Dcn4Plan {
   bool backward;
   bool det;                 // MDCONV_FLAG_DETERMINISTIC: the lists are sorted before the gather
   bool skip_input;          // MDCONV_FLAG_NO_GRAD_INPUT: no lists, no sort, no gather, no workspace
+  bool softmax;             // MDCONV_FLAG_SOFTMAX: the masks are logits (Dcn4SoftOp)
   ScatterLists lists;       // grad_input: per (image, group) a segment of S_i lists, K * S_o * 4 entries
+  size_t off_stats;         // softmax: 8 bytes per pair behind the lists
   size_t total;             // workspace bytes
 };
 
@@ -101,6 +118,75 @@ struct Dcn4Op : SampPlainFactor {
     const int pair = id / g.K, tap = id - pair * g.K;
     const int ex = group_elem(g, pair) + 2 * tap;
     Dcn3Op::list_item_at<CT>(g, pair, tap, grid_tap(g, tap), om, ex, ex + 1, it);
+  }
+};
+
+// What the taps of a pair have in common under the softmax: Dcn4Op's, and the statistics of the pair's K logits.
+struct Dcn4SoftPix : Dcn4Pix {
+  float mx, inv;   // the largest logit of the pair, and 1 / sum exp(logit - mx)
+};
+
+// The policy of MDCONV_FLAG_SOFTMAX: pairs, context, grid_tap, the three index functions, positions, the gate, the padding
+// rule and the list items are Dcn4Op's, called; what differs is that the factor of a tap is the softmax weight of its logit
+// (fda_weight, the one function the forward, the coordinate backward and the list kernel share).
+struct Dcn4SoftOp {
+  typedef Dcn4SoftGeom Geom;
+  typedef Dcn4SoftPix Ctx;
+  static constexpr bool kPairSum = true;
+  static __host__ __device__ __forceinline__ int npairs(const Geom &g) { return Dcn4Op::npairs(g); }
+  static __device__ __forceinline__ size_t sampled_bytes(const Geom &g) { return Dcn4Op::sampled_bytes(g); }
+  static __device__ __forceinline__ int list_rows(const Geom &g) { return Dcn4Op::list_rows(g); }
+
+  static __device__ __forceinline__ Ctx ctx(const Geom &g, int pair) {
+    Ctx p;
+    (Dcn4Pix &)p = Dcn4Op::ctx(g, pair);
+    p.mx = 0.f;
+    p.inv = 1.f;
+    return p;
+  }
+  static __device__ __forceinline__ int coord_index(const Geom &g, const Ctx &px, int pair, int tap, int xy) {
+    return Dcn4Op::coord_index(g, px, pair, tap, xy);
+  }
+  static __device__ __forceinline__ int factor_index(const Geom &g, const Ctx &px, int pair, int tap) {
+    return Dcn4Op::factor_index(g, px, pair, tap);
+  }
+  static __device__ __forceinline__ int list_factor_index(const Geom &g, int id) { return Dcn4Op::list_factor_index(g, id); }
+  // The statistics of the pair's softmax, by the pair's VL lanes together: lane j takes the logits j, j + VL, ... below K
+  // -- a lane with none (K < VL) enters neither the maximum nor the sum, and the row's padding is never read -- and two xor
+  // butterflies leave every lane with the same bits.  fp32 and max-subtracted: the largest term of the sum is exactly 1.
+  // Where the lists will need them (g.stats) the pair's lane 0 stores the two.
+  template <int CT>
+  static __device__ __forceinline__ void begin_pair(const Geom &g, Ctx &cx, const SampLane &ln, const void *om) {
+    const int e0 = cx.grp_elem + 2 * g.K;
+    float mx = -INFINITY;
+    for (int tap = ln.j; tap < g.K; tap += g.ln.VL) mx = fmaxf(mx, samp_ld<CT>(om, e0 + tap));
+    for (int d = g.ln.VL >> 1; d >= 1; d >>= 1) mx = fmaxf(mx, __shfl_xor(mx, d, 64));
+    float sum = 0.f;
+    for (int tap = ln.j; tap < g.K; tap += g.ln.VL) sum += expf(samp_ld<CT>(om, e0 + tap) - mx);
+    for (int d = g.ln.VL >> 1; d >= 1; d >>= 1) sum += __shfl_xor(sum, d, 64);
+    cx.mx = mx;
+    cx.inv = 1.f / sum;
+    if (g.stats && ln.live && ln.j == 0) g.stats[ln.pair] = make_float2(cx.mx, cx.inv);
+  }
+  template <int CT>
+  static __device__ __forceinline__ void build_tap(const Geom &g, const Ctx &cx, int pair, int tap, bool on, const void *om,
+                                                   const void *, SampTap &t, float &fx, float &fy) {
+    Dcn4Op::build_tap<CT>(g, cx, pair, tap, on, om, om, t, fx, fy);
+    if (on) t.m = fda_weight(t.m, cx.mx, cx.inv);   // (Dcn4Op left the logit there; a gated-out tap keeps its weight)
+  }
+  // d(sum_s a[s] g[s]) / d(logit t) = a[t] * (g[t] - sum_s a[s] g[s])
+  static __device__ __forceinline__ float factor_grad(float a, float gsum, float s_pair) { return a * (gsum - s_pair); }
+  template <int CT>
+  static __device__ __forceinline__ void finish_pair(const Geom &g, const Ctx &cx, const SampLane &ln, void *grad_om) {
+    Dcn4Op::finish_pair<CT>(g, cx, ln, grad_om);
+  }
+  // thread = sample: the weight from the statistics the coordinate kernel stored, not from a reduction per thread
+  static __device__ __forceinline__ float list_factor(const Geom &g, int id, float logit) {
+    const float2 st = g.stats[id / g.K];
+    return fda_weight(logit, st.x, st.y);
+  }
+  template <int CT> static __device__ __forceinline__ void list_item(const Geom &g, int id, const void *om, SampItem &it) {
+    Dcn4Op::list_item<CT>(g, id, om, it);
   }
 };
 #endif  // __HIPCC__

@@ -770,9 +770,10 @@ static int dcn4_validate(const mdconv_dcnv4_desc *d) {
     set_error("dcnv4: accumulate must be 0 or 1, is %d", d->accumulate);
     return MDCONV_EINVAL;
   }
-  if (d->flags & ~(MDCONV_FLAG_DETERMINISTIC | MDCONV_FLAG_NO_GRAD_INPUT)) {
-    set_error("dcnv4: unknown bits 0x%x in flags; the flags are MDCONV_FLAG_DETERMINISTIC (1) and MDCONV_FLAG_NO_GRAD_INPUT (4)",
-              (unsigned)(d->flags & ~(MDCONV_FLAG_DETERMINISTIC | MDCONV_FLAG_NO_GRAD_INPUT)));
+  const int dcn4_flags = MDCONV_FLAG_DETERMINISTIC | MDCONV_FLAG_NO_GRAD_INPUT | MDCONV_FLAG_SOFTMAX;
+  if (d->flags & ~dcn4_flags) {
+    set_error("dcnv4: unknown bits 0x%x in flags; the flags are MDCONV_FLAG_DETERMINISTIC (1), MDCONV_FLAG_NO_GRAD_INPUT (4) "
+              "and MDCONV_FLAG_SOFTMAX (256)", (unsigned)(d->flags & ~dcn4_flags));
     return MDCONV_EINVAL;
   }
   if (!(d->offset_scale == d->offset_scale) || d->offset_scale - d->offset_scale != 0.f) {

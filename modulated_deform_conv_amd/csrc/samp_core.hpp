@@ -9,7 +9,7 @@
 // most 64) are adjacent and the pairs of a pixel follow each other, so a wave's stores and each of its corner loads are
 // contiguous 16-byte pieces.  Heads of more than 64 vectors (D > 256 fp32) take `rounds` > 1 passes over the vectors.
 //
-// An operator policy `Op` (Dcn3Op, MsdaOp, Dcn4Op, FdaOp) supplies only what differs:
+// An operator policy `Op` (Dcn3Op, MsdaOp, Dcn4Op, FdaOp, Dcn4SoftOp) supplies only what differs:
 //   Op::Geom                       the kernel argument (POD, by value); it has K, D, acc and the lane geometry `ln`
 //   Op::npairs(g), Op::sampled_bytes(g)
 //   Op::Ctx, Op::ctx(g, pair)      what the taps of a pair have in common
@@ -23,7 +23,8 @@
 // The policy owns the addressing: the kernels never form an element index themselves, and the gradients go to the elements
 // their forward values came from.  `coord` and `factor` may therefore be ONE tensor (the packed offset_mask rows of
 // Dcn4Op), and so may grad_coord and grad_factor; see the qualifiers of samp_bwd_coord_kernel.
-// A policy whose factor is a FUNCTION of the stored elements of its pair (FdaOp: a softmax over the pair's logits) also has
+// A policy whose factor is a FUNCTION of the stored elements of its pair (FdaOp, Dcn4SoftOp: a softmax over the pair's
+// logits) also has
 //   Op::begin_pair<CT>(g, cx, ln, factor)   the pair's statistics into its context, taken by the pair's lanes together
 //   Op::kPairSum, Op::factor_grad(a, gsum, s_pair)   the stored gradient of (pair, tap) from the tap's factor a, the sum
 //                                  gsum the coordinate backward holds for it, and s_pair = sum over the pair's taps of a * gsum

@@ -4,6 +4,8 @@
     DCNv3Function   autograd.Function over mdconv_dcnv3_forward / mdconv_dcnv3_backward
     dcnv3_core      the functional form
     DCNv3           nn.Module: the block around the operator, composed from framework operators
+    DCNv3Fused      the same block, parameters and checkpoints on the DCNv4 operator with its in-kernel softmax (dcnv4.py):
+                    one linear layer for offsets and mask logits, no framework softmax
 
 The operator has no weight: ``input [B, H, W, G*D]``, ``offset [B, Ho, Wo, G*K*2]`` ((x, y) per tap, taps width-major),
 ``mask [B, Ho, Wo, G*K]`` -> ``output [B, Ho, Wo, G*D]``, fp32 / fp16 / bf16, one dtype per call.  CPU tensors raise
@@ -21,7 +23,7 @@ from torch.nn.modules.utils import _pair
 
 from . import _capi
 
-__all__ = ["DCNv3Function", "dcnv3_core", "DCNv3"]
+__all__ = ["DCNv3Function", "dcnv3_core", "DCNv3", "DCNv3Fused"]
 
 _DTYPES = {torch.float32: _capi.F32, torch.float16: _capi.F16, torch.bfloat16: _capi.BF16}
 
@@ -223,3 +225,47 @@ class DCNv3(nn.Module):
     def extra_repr(self):
         return "channels=%d, kernel_size=%d, stride=%d, pad=%d, dilation=%d, group=%d, offset_scale=%g" % (
             self.channels, self.kernel_size, self.stride, self.pad, self.dilation, self.group, self.offset_scale)
+
+
+class DCNv3Fused(DCNv3):
+    """``DCNv3`` with the constructor, parameters, initialisation and ``state_dict`` keys of ``DCNv3`` -- the same
+    checkpoints load -- on the DCNv4 operator with ``softmax=True``: what ``FlashDeformAttn`` is to ``MSDeformAttn``.  The
+    forward gathers ONE packed weight ``[OM, C]`` and bias ``[OM]`` from ``offset.weight / bias`` and ``mask.weight / bias``
+    through a fixed row index (``pack_index``: per group the 2K offset rows, then the K mask rows, then zero rows for the
+    row's padding; autograd carries the gradients back to both parameters), runs one ``F.linear`` whose output is the
+    operator's packed row as it stands, and calls ``dcnv4_core(..., softmax=True)``: no framework softmax, no
+    activation-sized concatenation, no cast of a materialised mask.  Under autocast the packed row has the autocast dtype
+    and the softmax is taken in fp32 inside the kernels."""
+
+    def __init__(self, *args, **kwargs):
+        super().__init__(*args, **kwargs)
+        from .dcnv4 import dcnv4_core
+        self._core = dcnv4_core
+        # (not persistent: the state_dict keys are DCNv3's)
+        self.register_buffer("pack_index", self.make_pack_index(self.group, self.kernel_size * self.kernel_size),
+                             persistent=False)
+
+    @staticmethod
+    def make_pack_index(group, K):
+        """Rows of ``cat([offset rows (G*K*2), mask rows (G*K), one zero row])`` in the order of the packed row."""
+        om = (group * K * 3 + 7) // 8 * 8
+        idx = []
+        for g in range(group):
+            idx += range(g * 2 * K, (g + 1) * 2 * K)
+            idx += range(group * 2 * K + g * K, group * 2 * K + (g + 1) * K)
+        idx += [group * 3 * K] * (om - group * 3 * K)
+        return torch.tensor(idx, dtype=torch.long)
+
+    def packed_linear(self):
+        """(weight [OM, C], bias [OM]) of the one linear layer; tiny tensors, differentiable to the four parameters."""
+        w = torch.cat([self.offset.weight, self.mask.weight, self.offset.weight.new_zeros(1, self.channels)], 0)
+        b = torch.cat([self.offset.bias, self.mask.bias, self.offset.bias.new_zeros(1)], 0)
+        return w.index_select(0, self.pack_index), b.index_select(0, self.pack_index)
+
+    def forward(self, input):
+        x = self.input_proj(input)
+        x1 = self.dw_conv(input.permute(0, 3, 1, 2))
+        offset_mask = F.linear(x1, *self.packed_linear())
+        x = self._core(x, offset_mask, self.kernel_size, self.stride, self.pad, self.dilation, self.group,
+                       self.group_channels, self.offset_scale, False, softmax=True)
+        return self.output_proj(x)

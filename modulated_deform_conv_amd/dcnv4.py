@@ -6,10 +6,11 @@
     dcnv4_core      the functional form
     DCNv4           nn.Module: the block around the operator, composed from framework operators
 
-The operator has no weight and no softmax: ``input [B, H, W, G*D]``, ``offset_mask [B, Ho, Wo, OM]`` -> ``output
-[B, Ho, Wo, G*D]``.  A row of ``offset_mask`` holds, per group, the (x, y) offsets of the K taps and then their K masks,
-and is padded to ``OM = ceil(G*K*3 / 8) * 8`` elements (``offset_mask_len``); ``K = kh*kw``, minus one with
-``remove_center``.  ``input`` is fp32 / fp16 / bf16; ``offset_mask`` has its dtype or is fp32.  CPU tensors raise
+The operator has no weight and, by default, no softmax: ``input [B, H, W, G*D]``, ``offset_mask [B, Ho, Wo, OM]`` ->
+``output [B, Ho, Wo, G*D]``.  A row of ``offset_mask`` holds, per group, the (x, y) offsets of the K taps and then their K
+masks, and is padded to ``OM = ceil(G*K*3 / 8) * 8`` elements (``offset_mask_len``); ``K = kh*kw``, minus one with
+``remove_center``.  With ``softmax=True`` (``MDCONV_FLAG_SOFTMAX``) the K masks of a group are logits and the kernels take
+their softmax themselves -- DCNv3's softmax over the taps, over all K tensor taps, gated-out ones included.  ``input`` is fp32 / fp16 / bf16; ``offset_mask`` has its dtype or is fp32.  CPU tensors raise
 ``NotImplementedError``: there is no CPU or PyTorch fallback.
 """
 import ctypes
@@ -98,11 +99,13 @@ def _run(fn_name, d, backward, args_before_ws, input):
 
 
 def dcnv4_forward(input, offset_mask, kernel, stride, pad, dilation, group, group_channels, offset_scale,
-                  remove_center=False, output=None):
-    """The forward entry point on dense CUDA tensors; allocates ``output`` unless it is given."""
+                  remove_center=False, output=None, softmax=False):
+    """The forward entry point on dense CUDA tensors; allocates ``output`` unless it is given.  ``softmax``: the masks are
+    logits (``MDCONV_FLAG_SOFTMAX``)."""
     if not input.is_cuda:
         raise NotImplementedError
-    d = _desc(input, offset_mask, kernel, stride, pad, dilation, group, group_channels, offset_scale, remove_center)
+    d = _desc(input, offset_mask, kernel, stride, pad, dilation, group, group_channels, offset_scale, remove_center,
+              flags=_capi.FLAG_SOFTMAX if softmax else 0)
     others = {} if output is None else dict(output=output)
     shape = _check(d, input, offset_mask, **others)
     if output is None:
@@ -112,17 +115,19 @@ def dcnv4_forward(input, offset_mask, kernel, stride, pad, dilation, group, grou
 
 
 def dcnv4_backward(input, offset_mask, grad_output, kernel, stride, pad, dilation, group, group_channels, offset_scale,
-                   remove_center=False, grads=None, need_grad_input=True, deterministic=None, accumulate=None):
+                   remove_center=False, grads=None, need_grad_input=True, deterministic=None, accumulate=None, softmax=False):
     """The backward entry point.  ``grads`` = (grad_input | None, grad_offset_mask): caller-allocated buffers the gradients
     are ADDED to (their padding columns stay untouched); without it fresh tensors are written, the padding columns of
     grad_offset_mask as zeros.  ``need_grad_input`` false: grad_input is neither computed nor allocated
     (``MDCONV_FLAG_NO_GRAD_INPUT``) and None is returned there.  ``deterministic`` None follows
     ``_capi.deterministic_mode()``.  ``accumulate`` false with ``grads``: the caller's buffers are overwritten instead.
+    ``softmax``: the masks are logits (``MDCONV_FLAG_SOFTMAX``), and their columns of grad_offset_mask the logits' gradients.
     Returns (grad_input | None, grad_offset_mask)."""
     if not input.is_cuda:
         raise NotImplementedError
     det = _capi.deterministic_mode() if deterministic is None else bool(deterministic)
     flags = (_capi.FLAG_DETERMINISTIC if det else 0) | (0 if need_grad_input else _capi.FLAG_NO_GRAD_INPUT)
+    flags |= _capi.FLAG_SOFTMAX if softmax else 0
     d = _desc(input, offset_mask, kernel, stride, pad, dilation, group, group_channels, offset_scale, remove_center,
               accumulate=int(grads is not None if accumulate is None else bool(accumulate)), flags=flags)
     _check(d, input, offset_mask, grad_output=grad_output)
@@ -141,19 +146,21 @@ def dcnv4_backward(input, offset_mask, grad_output, kernel, stride, pad, dilatio
 
 class DCNv4Function(Function):
     """``DCNv4Function.apply(input, offset_mask, kernel_h, kernel_w, stride_h, stride_w, pad_h, pad_w, dilation_h,
-    dilation_w, group, group_channels, offset_scale, im2col_step, remove_center)`` -- the argument order of the published
-    operator; ``im2col_step`` is accepted for signature parity and unused.  Under ``torch.autocast`` ``input`` runs in the
+    dilation_w, group, group_channels, offset_scale, im2col_step, remove_center[, softmax])`` -- the argument order of the
+    published operator, then the optional ``softmax`` (the masks are logits); ``im2col_step`` is accepted for signature
+    parity and unused.  Under ``torch.autocast`` ``input`` runs in the
     autocast dtype.  ``offset_mask`` keeps its dtype when that is the dtype ``input`` runs in or float32 (the mixed call)
     and is cast to the former otherwise.  The gradients go back in the dtypes the caller's tensors have."""
 
     @staticmethod
     @custom_fwd(device_type="cuda")
     def forward(ctx, input, offset_mask, kernel_h, kernel_w, stride_h, stride_w, pad_h, pad_w, dilation_h, dilation_w,
-                group, group_channels, offset_scale, im2col_step=256, remove_center=False):
+                group, group_channels, offset_scale, im2col_step=256, remove_center=False, softmax=False):
         if not input.is_cuda:
             raise NotImplementedError
         ctx.geo = ((kernel_h, kernel_w), (stride_h, stride_w), (pad_h, pad_w), (dilation_h, dilation_w), group,
                    group_channels, offset_scale, bool(remove_center))
+        ctx.softmax = bool(softmax)
         ctx.in_dtypes = (input.dtype, offset_mask.dtype)
         if torch.is_autocast_enabled("cuda"):
             input = input.to(torch.get_autocast_dtype("cuda"))
@@ -162,7 +169,7 @@ class DCNv4Function(Function):
         input, offset_mask = input.contiguous(), offset_mask.contiguous()
         if any(ctx.needs_input_grad[:2]):
             ctx.save_for_backward(input, offset_mask)
-        return dcnv4_forward(input, offset_mask, *ctx.geo)
+        return dcnv4_forward(input, offset_mask, *ctx.geo, softmax=ctx.softmax)
 
     @staticmethod
     @custom_bwd(device_type="cuda")
@@ -173,29 +180,32 @@ class DCNv4Function(Function):
         input, offset_mask = ctx.saved_tensors
         grad_output = grad_output.to(input.dtype).contiguous()
         # selective backward: grad_input is neither computed nor allocated when `input` needs no gradient
-        grads = dcnv4_backward(input, offset_mask, grad_output, *ctx.geo, need_grad_input=bool(ctx.needs_input_grad[0]))
+        grads = dcnv4_backward(input, offset_mask, grad_output, *ctx.geo, need_grad_input=bool(ctx.needs_input_grad[0]),
+                               softmax=ctx.softmax)
         back = lambda g, dt: g if g is None or g.dtype == dt else g.to(dt)
-        return tuple(back(g, dt) for g, dt in zip(grads, ctx.in_dtypes)) + (None,) * 13
+        return tuple(back(g, dt) for g, dt in zip(grads, ctx.in_dtypes)) + (None,) * 14
 
 
-def dcnv4_core(input, offset_mask, kernel, stride, pad, dilation, group, group_channels, offset_scale, remove_center=False):
-    """Functional form; ``kernel``, ``stride``, ``pad`` and ``dilation`` are ints or (h, w) pairs."""
+def dcnv4_core(input, offset_mask, kernel, stride, pad, dilation, group, group_channels, offset_scale, remove_center=False,
+               softmax=False):
+    """Functional form; ``kernel``, ``stride``, ``pad`` and ``dilation`` are ints or (h, w) pairs.  ``softmax``: the K masks
+    of a group are logits and the operator takes their softmax."""
     (kh, kw), (sh, sw), (ph, pw), (dh, dw) = (_pair(v) for v in (kernel, stride, pad, dilation))
     return DCNv4Function.apply(input, offset_mask, kh, kw, sh, sw, ph, pw, dh, dw, group, group_channels, offset_scale, 256,
-                               remove_center)
+                               remove_center, softmax)
 
 
 class DCNv4(nn.Module):
     """The DCNv4 block on ``[N, L, C]`` token tensors with ``shape=(H, W)``, ``L = H * W``: ``value_proj``, the
     ``offset_mask`` linear (on the tokens, or on a depthwise convolution ``offset_mask_dw`` of them when
-    ``dw_kernel_size`` is given) whose ``OM`` outputs are the operator's packed tensor as they are -- no softmax --, the
-    operator, ``output_proj`` (``output_bias`` false: without bias).  ``without_pointwise`` leaves both projections out.
+    ``dw_kernel_size`` is given) whose ``OM`` outputs are the operator's packed tensor as they are -- no softmax, or with
+    ``softmax=True`` the operator's own over the masks of a group --, the operator, ``output_proj`` (``output_bias`` false: without bias).  ``without_pointwise`` leaves both projections out.
     Everything but the operator is a framework operator.  ``offset_mask`` starts at zero, the projections with Xavier.
     Module and parameter names are written from memory of the published block and UNPINNED against it (INTEGRATION.md);
     its ``center_feature_scale`` variant is not provided."""
 
     def __init__(self, channels=64, kernel_size=3, stride=1, pad=1, dilation=1, group=4, offset_scale=1.0,
-                 dw_kernel_size=None, remove_center=False, output_bias=True, without_pointwise=False):
+                 dw_kernel_size=None, remove_center=False, output_bias=True, without_pointwise=False, softmax=False):
         super().__init__()
         if channels % group:
             raise ValueError("channels must be divisible by group, but got %d and %d" % (channels, group))
@@ -203,6 +213,7 @@ class DCNv4(nn.Module):
         self.stride, self.pad, self.dilation = stride, pad, dilation
         self.group, self.group_channels, self.offset_scale = group, channels // group, offset_scale
         self.remove_center, self.without_pointwise = bool(remove_center), bool(without_pointwise)
+        self.softmax = bool(softmax)
         if dw_kernel_size is not None:
             self.offset_mask_dw = nn.Conv2d(channels, channels, dw_kernel_size, stride=1, padding=(dw_kernel_size - 1) // 2,
                                             groups=channels)
@@ -237,12 +248,14 @@ class DCNv4(nn.Module):
         # (the operator's row is the linear layer's output as it stands; it needs the operator's output extent, which is
         # (H, W) for the block's stride-1 "same" geometry)
         offset_mask = self.offset_mask(tokens).reshape(N, H, W, -1)
+        # (the keyword is passed only when set: a core swapped in for the plain operator need not know it)
+        extra = dict(softmax=True) if self.softmax else {}
         x = self._core(x.reshape(N, H, W, C), offset_mask, self.kernel_size, self.stride, self.pad, self.dilation, self.group,
-                       self.group_channels, self.offset_scale, self.remove_center)
+                       self.group_channels, self.offset_scale, self.remove_center, **extra)
         x = x.reshape(N, -1, C)
         return x if self.without_pointwise else self.output_proj(x)
 
     def extra_repr(self):
-        return "channels=%d, kernel_size=%d, stride=%d, pad=%d, dilation=%d, group=%d, offset_scale=%g, remove_center=%s" % (
+        return "channels=%d, kernel_size=%d, stride=%d, pad=%d, dilation=%d, group=%d, offset_scale=%g, remove_center=%s%s" % (
             self.channels, self.kernel_size, self.stride, self.pad, self.dilation, self.group, self.offset_scale,
-            self.remove_center)
+            self.remove_center, ", softmax=True" if self.softmax else "")
