@@ -634,6 +634,83 @@ int mdconv_fda_forward(const mdconv_fda_desc *d, const void *value, const void *
 int mdconv_fda_backward(const mdconv_fda_desc *d, const void *value, const void *sampling_loc_attn, const void *grad_output,
                         void *grad_value, void *grad_sampling_loc_attn, void *workspace, size_t workspace_bytes, void *stream);
 
+/* --- Deformable RoI pooling: RoIAlign whose bins are shifted by a learnt offset, channels-last -------
+ * ("deform_roi_pool": the dpool / mdpool heads of Deformable ConvNets v1 / v2 detectors.)  An operator of its own with a
+ * descriptor of its own; nothing above changes.  B images of H x W pixels and C channels, R regions pooled into PH x PW bins;
+ * every tensor dense and row-major:
+ *     input    [B, H, W, C]         dtype
+ *     rois     [R, 5]               fp32 always: (batch index, x1, y1, x2, y2) in image coordinates
+ *     offset   [R, 2, PH, PW]       coord_dtype; plane 0 = x (width), plane 1 = y; absent with with_offset == 0 (pointer ignored)
+ *     output   [R, PH, PW, C]       dtype
+ *     b   = (int) rois[r,0]
+ *     x1s = x1*spatial_scale - 0.5  (y1s, x2s, y2s alike: no rounding, no minimum size)
+ *     rw  = x2s - x1s,  rh = y2s - y1s,  bw = rw / PW,  bh = rh / PH
+ *     gh  = sampling_ratio > 0 ? sampling_ratio : min(max(ceil(rh / PH), 0), max_grid)        (gw from rw / PW alike)
+ *     cnt = max(gh*gw, 1)
+ *     dx  = gamma * rw * offset[r,0,ph,pw],  dy = gamma * rh * offset[r,1,ph,pw]               (0 without offset)
+ *     y(iy) = y1s + dy + ph*bh + (iy + 0.5) * bh / gh,   x(ix) = x1s + dx + pw*bw + (ix + 0.5) * bw / gw
+ *     output[r,ph,pw,c] = (1/cnt) * sum_{iy<gh, ix<gw} bil(input[b,:,:,c], y(iy), x(ix))
+ *  - bil(y, x) is RoIAlign's sample: it contributes nothing, to the output and to every gradient, when y < -1, y > H, x < -1
+ *    or x > W.  Otherwise y = max(y, 0), y_lo = floor(y); if y_lo >= H-1 then y_lo = y_hi = H-1 and y = H-1, else
+ *    y_hi = y_lo + 1; the same for x; the value is the bilinear mix of the four (possibly coinciding) neighbours.  No element
+ *    outside the image is ever loaded.  All arithmetic is fp32, each result is rounded once.
+ *  - A RoI contributes NOTHING when its batch index is not an integer in [0, B) or any of its five numbers is not finite: its
+ *    output rows are zero, its grad_offset rows are exact zeros (overwrite) or untouched (accumulate), it adds nothing to
+ *    grad_input, and nothing is read through it.  A RoI with rh <= 0 or rw <= 0 under the adaptive rule (sampling_ratio == 0)
+ *    has no samples and gives zeros the same way.
+ *  - max_grid (1..16) is read only with sampling_ratio == 0: it bounds the workspace without reading `rois` on the host.
+ *    When no RoI of a call exceeds it the result is the published adaptive rule.
+ *  - The backward returns grad_input [B,H,W,C] (the four interpolation weights / cnt; coinciding corners add) and
+ *    grad_offset [R,2,PH,PW] = gamma*rw/cnt * sum_c grad_output[r,ph,pw,c] * sum_samples d bil/dx (rh and d/dy for plane 1);
+ *    rois get no gradient.  grad_offset is the derivative of the function the forward computes, in the lattice convention of
+ *    the operators above: the right-sided derivative of the cell floor(loc), exactly zero along an axis where the coordinate
+ *    is clamped (loc < 0 or loc >= size-1), exactly zero outside the gate.  `accumulate` is the backward's write mode
+ *    (mdconv_desc.accumulate); the forward writes every output row.
+ *  - dtype (MDCONV_F32, MDCONV_F16 or MDCONV_BF16) is the type of input, output, grad_output and grad_input; coord_dtype is
+ *    the type of offset and grad_offset: equal to dtype, or MDCONV_F32.
+ *  - Shape rule (else MDCONV_EUNSUPPORTED, with the rule in the error message, before anything is launched): C * element size
+ *    a multiple of 16, every tensor below 2^31 bytes, and R*PH*PW*Gcap*Gcap*4 below 2^31 with Gcap = sampling_ratio, or
+ *    max_grid when that is 0.
+ *  - flags: MDCONV_FLAG_DETERMINISTIC and MDCONV_FLAG_NO_GRAD_INPUT only; any other bit is MDCONV_EINVAL, and so is a
+ *    backward that has neither grad_offset (with_offset == 0) nor grad_input (MDCONV_FLAG_NO_GRAD_INPUT) to compute.  No
+ *    result is summed with floating-point atomics: output and grad_offset are bit-identical from call to call, grad_input is
+ *    with MDCONV_FLAG_DETERMINISTIC and agrees to rounding otherwise.  With MDCONV_FLAG_NO_GRAD_INPUT grad_input may be NULL
+ *    and is never touched, the workspace is 0, and grad_offset is bit for bit the full call's.  Forwards ignore both flags.
+ *  - A call checks in this order: the descriptor (MDCONV_EINVAL), the pointers (MDCONV_ENULL), the shape rule
+ *    (MDCONV_EUNSUPPORTED), the workspace (MDCONV_EWORKSPACE: size and 16-byte alignment, as above).
+ *  - The workspace figure is exact, 0 for the forward, independent of coord_dtype, and honours both flags.  A call is a plain
+ *    chain of kernels on the caller's stream: no second stream, no host synchronisation; it captures into a HIP graph.
+ *  Written from memory of the published operator and UNPINNED against its code; where the published kernels
+ *  are remembered to differ (the offset gradient in the clamped zones) this text is the specification. */
+typedef struct mdconv_droi_desc {
+  int dtype;           /* input, output, grad_output, grad_input: MDCONV_F32 / MDCONV_F16 / MDCONV_BF16 */
+  int coord_dtype;     /* offset and grad_offset: `dtype` or MDCONV_F32 */
+  int batch;           /* B */
+  int channels;        /* C */
+  int height, width;   /* H, W */
+  int rois;            /* R */
+  int pooled_h, pooled_w;   /* PH, PW */
+  int sampling_ratio;  /* 0 = adaptive (bounded by max_grid), else 1..16 samples per bin and axis */
+  int max_grid;        /* 1..16; read only with sampling_ratio == 0 */
+  float spatial_scale;
+  float gamma;
+  int with_offset;     /* 0 = plain RoIAlign sampling: offset and grad_offset are ignored */
+  int accumulate;      /* backward write mode: 1 = add to grad_*, 0 = overwrite */
+  int flags;           /* MDCONV_FLAG_DETERMINISTIC | MDCONV_FLAG_NO_GRAD_INPUT */
+} mdconv_droi_desc;
+/* `mdconv_droi_desc d = MDCONV_DROI_DESC_INIT;` then fill in the shape (fp32, adaptive grid up to 8, scale 1, gamma 0.1,
+ * with offset, accumulate, no flags) */
+#define MDCONV_DROI_DESC_INIT { 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 8, 1.0f, 0.1f, 1, 1, 0 }
+
+/* Scratch bytes of the forward (backward = 0: always 0) or the backward (backward = 1) of `d`; 0 for a descriptor that is
+ * invalid or outside the shape rule. */
+size_t mdconv_droi_workspace_bytes(const mdconv_droi_desc *d, int backward);
+int mdconv_droi_forward(const mdconv_droi_desc *d, const void *input, const void *rois, const void *offset, void *output,
+                        void *workspace, size_t workspace_bytes, void *stream);
+int mdconv_droi_backward(const mdconv_droi_desc *d, const void *input, const void *rois, const void *offset,
+                         const void *grad_output, void *grad_input, void *grad_offset, void *workspace,
+                         size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -21,6 +21,10 @@ behind the reference's own operator surface.
                                                        operator): FlashDeformAttnFunction, flash_deform_attn,
                                                        flash_deform_attn_forward / _backward, FlashDeformAttn,
                                                        pack_loc_attn / unpack_loc_attn -- also exported here
+    modulated_deform_conv_amd.droi                     deformable RoI pooling (channels-last kernels behind logical NCHW
+                                                       tensors, offsets in the same type or fp32): DeformRoIPoolFunction,
+                                                       deform_roi_pool, deform_roi_pool_forward / _backward, DeformRoIPool,
+                                                       DeformRoIPoolPack, ModulatedDeformRoIPoolPack -- also exported here
     modulated_deform_conv_amd.distributed              batch-sharded multi-GPU helper (RCCL)
 
 All compute runs in libmdconv_hip.so (hand-written HIP, C ABI in include/mdconv.h); there is no
@@ -35,7 +39,9 @@ _MSDA = ("ms_deform_attn_forward", "ms_deform_attn_backward", "MSDeformAttnFunct
 _DCNV4 = ("dcnv4_forward", "dcnv4_backward", "DCNv4Function", "dcnv4_core", "DCNv4")
 _FDA = ("flash_deform_attn_forward", "flash_deform_attn_backward", "FlashDeformAttnFunction", "flash_deform_attn",
         "FlashDeformAttn", "pack_loc_attn", "unpack_loc_attn")
-__all__ = list(_DCNV3 + _MSDA + _DCNV4 + _FDA)
+_DROI = ("deform_roi_pool_forward", "deform_roi_pool_backward", "DeformRoIPoolFunction", "deform_roi_pool", "DeformRoIPool",
+         "DeformRoIPoolPack", "ModulatedDeformRoIPoolPack")
+__all__ = list(_DCNV3 + _MSDA + _DCNV4 + _FDA + _DROI)
 
 
 def __getattr__(name):
@@ -52,4 +58,7 @@ def __getattr__(name):
     if name in _FDA:
         from . import fda
         return getattr(fda, name)
+    if name in _DROI:
+        from . import droi
+        return getattr(droi, name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

@@ -40,6 +40,7 @@ EXPORTS = (
     "mdconv_dcnv4_out_size", "mdconv_dcnv4_offset_mask_len", "mdconv_dcnv4_workspace_bytes", "mdconv_dcnv4_forward",
     "mdconv_dcnv4_backward",
     "mdconv_fda_value_len", "mdconv_fda_loc_attn_len", "mdconv_fda_workspace_bytes", "mdconv_fda_forward", "mdconv_fda_backward",
+    "mdconv_droi_workspace_bytes", "mdconv_droi_forward", "mdconv_droi_backward",
 )
 
 
@@ -99,6 +100,15 @@ class MdconvFdaDesc(ctypes.Structure):
     _fields_ = list(MdconvMsdaDesc._fields_)
 
 
+class MdconvDroiDesc(ctypes.Structure):
+    """Mirror of ``struct mdconv_droi_desc`` (include/mdconv.h, "Deformable RoI pooling")."""
+    _fields_ = [("dtype", ctypes.c_int), ("coord_dtype", ctypes.c_int), ("batch", ctypes.c_int), ("channels", ctypes.c_int),
+                ("height", ctypes.c_int), ("width", ctypes.c_int), ("rois", ctypes.c_int), ("pooled_h", ctypes.c_int),
+                ("pooled_w", ctypes.c_int), ("sampling_ratio", ctypes.c_int), ("max_grid", ctypes.c_int),
+                ("spatial_scale", ctypes.c_float), ("gamma", ctypes.c_float), ("with_offset", ctypes.c_int),
+                ("accumulate", ctypes.c_int), ("flags", ctypes.c_int)]
+
+
 _lib = None
 
 
@@ -149,7 +159,7 @@ def lib():
             L.mdconv_planned_kernels.argtypes = [ctypes.c_void_p, ctypes.c_int]
         missing = (() if has_math_query else ("mdconv_math_bf16_used",)) + (() if has_layout_query else ("mdconv_result_layout_supported",))
         missing += () if has_plan_query else ("mdconv_planned_kernels",)
-        missing += tuple(n for n in EXPORTS if n.startswith(("mdconv_dcnv3_", "mdconv_msda_", "mdconv_dcnv4_", "mdconv_fda_")) and not hasattr(L, n))
+        missing += tuple(n for n in EXPORTS if n.startswith(("mdconv_dcnv3_", "mdconv_msda_", "mdconv_dcnv4_", "mdconv_fda_", "mdconv_droi_")) and not hasattr(L, n))
         for name in EXPORTS[11:]:
             if name not in missing:
                 getattr(L, name).restype = ctypes.c_int
@@ -175,6 +185,10 @@ def lib():
             L.mdconv_fda_loc_attn_len.argtypes = [ctypes.c_void_p]
             L.mdconv_fda_workspace_bytes.restype = ctypes.c_size_t
             L.mdconv_fda_workspace_bytes.argtypes = [ctypes.c_void_p, ctypes.c_int]
+        # (likewise a build from before deformable RoI pooling: droi.py raises there)
+        if hasattr(L, "mdconv_droi_workspace_bytes"):
+            L.mdconv_droi_workspace_bytes.restype = ctypes.c_size_t
+            L.mdconv_droi_workspace_bytes.argtypes = [ctypes.c_void_p, ctypes.c_int]
         if L.mdconv_abi_version() != ABI_VERSION:
             raise ImportError("libmdconv_hip.so ABI version mismatch")
         _lib = L

@@ -18,6 +18,7 @@
 #include "dcn4_plan.hpp"
 #include "msda_plan.hpp"
 #include "fda_plan.hpp"
+#include "droi_plan.hpp"
 #include "dw_plan.hpp"
 #include "hp_plan.hpp"
 #include "mfma_plan.hpp"
@@ -839,6 +840,62 @@ static int fda_refuse(const char *why) {
   return MDCONV_EUNSUPPORTED;
 }
 
+// ---- deformable RoI pooling (droi_plan.hpp): the descriptor's own validation; the shape rule is droi_plan's ----
+static int droi_validate(const mdconv_droi_desc *d, bool backward) {
+  if (!d) {
+    set_error("descriptor pointer is NULL");
+    return MDCONV_EINVAL;
+  }
+  if (d->dtype != MDCONV_F32 && d->dtype != MDCONV_F16 && d->dtype != MDCONV_BF16) {
+    set_error("droi: dtype %d is not MDCONV_F32, MDCONV_F16 or MDCONV_BF16 (the dtype flags do not apply)", d->dtype);
+    return MDCONV_EINVAL;
+  }
+  if (d->coord_dtype != d->dtype && d->coord_dtype != MDCONV_F32) {
+    set_error("droi: coord_dtype %d is neither dtype (%d) nor MDCONV_F32", d->coord_dtype, d->dtype);
+    return MDCONV_EINVAL;
+  }
+  if (d->batch <= 0 || d->channels <= 0 || d->height <= 0 || d->width <= 0 || d->rois <= 0 || d->pooled_h <= 0 ||
+      d->pooled_w <= 0) {
+    set_error("droi: batch, channels, height, width, rois, pooled_h and pooled_w must be positive (%d, %d, %d, %d, %d, %d, %d)",
+              d->batch, d->channels, d->height, d->width, d->rois, d->pooled_h, d->pooled_w);
+    return MDCONV_EINVAL;
+  }
+  if (d->sampling_ratio < 0 || d->sampling_ratio > 16) {
+    set_error("droi: sampling_ratio must be 0 (adaptive) or 1..16, is %d", d->sampling_ratio);
+    return MDCONV_EINVAL;
+  }
+  if (d->max_grid < 1 || d->max_grid > 16) {
+    set_error("droi: max_grid must be 1..16, is %d", d->max_grid);
+    return MDCONV_EINVAL;
+  }
+  if (!(d->spatial_scale == d->spatial_scale) || d->spatial_scale - d->spatial_scale != 0.f) {
+    set_error("droi: spatial_scale is not finite");
+    return MDCONV_EINVAL;
+  }
+  if (!(d->gamma == d->gamma) || d->gamma - d->gamma != 0.f) {
+    set_error("droi: gamma is not finite");
+    return MDCONV_EINVAL;
+  }
+  if (d->accumulate != 0 && d->accumulate != 1) {
+    set_error("droi: accumulate must be 0 or 1, is %d", d->accumulate);
+    return MDCONV_EINVAL;
+  }
+  if (d->flags & ~(MDCONV_FLAG_DETERMINISTIC | MDCONV_FLAG_NO_GRAD_INPUT)) {
+    set_error("droi: unknown bits 0x%x in flags; the flags are MDCONV_FLAG_DETERMINISTIC (1) and MDCONV_FLAG_NO_GRAD_INPUT (4)",
+              (unsigned)(d->flags & ~(MDCONV_FLAG_DETERMINISTIC | MDCONV_FLAG_NO_GRAD_INPUT)));
+    return MDCONV_EINVAL;
+  }
+  if (backward && !d->with_offset && (d->flags & MDCONV_FLAG_NO_GRAD_INPUT)) {
+    set_error("droi: a backward with with_offset == 0 and MDCONV_FLAG_NO_GRAD_INPUT has nothing to compute");
+    return MDCONV_EINVAL;
+  }
+  return MDCONV_OK;
+}
+static int droi_refuse(const char *why) {
+  set_error("droi: outside the shape rule of the operator: %s", why);
+  return MDCONV_EUNSUPPORTED;
+}
+
 extern "C" {
 
 int mdconv_abi_version(void) { return MDCONV_ABI_VERSION; }
@@ -1305,6 +1362,53 @@ int mdconv_fda_backward(const mdconv_fda_desc *d, const void *value, const void 
   t.value = value; t.loc_attn = sampling_loc_attn; t.grad_output = grad_output;
   t.grad_value = grad_value; t.grad_loc_attn = grad_sampling_loc_attn;
   return fda_backward(p, t, workspace, (hipStream_t)stream);
+}
+
+size_t mdconv_droi_workspace_bytes(const mdconv_droi_desc *d, int backward) {
+  DroiPlan p;
+  const char *why;
+  g_err[0] = 0;
+  if (droi_validate(d, backward != 0)) return 0;
+  if (!droi_plan(d, backward != 0, &p, &why)) {
+    droi_refuse(why);
+    return 0;
+  }
+  return p.total;
+}
+
+int mdconv_droi_forward(const mdconv_droi_desc *d, const void *input, const void *rois, const void *offset, void *output,
+                        void *workspace, size_t workspace_bytes, void *stream) {
+  g_err[0] = 0;
+  int rc = droi_validate(d, false);
+  if (rc) return rc;
+  if ((rc = require(input, "input")) || (rc = require(rois, "rois")) || (rc = require(output, "output"))) return rc;
+  if (d->with_offset && (rc = require(offset, "offset"))) return rc;
+  DroiPlan p;
+  const char *why;
+  if (!droi_plan(d, false, &p, &why)) return droi_refuse(why);
+  if ((rc = check_ws(workspace, workspace_bytes, p.total))) return rc;
+  DroiTensors t = {};
+  t.input = input; t.rois = rois; t.offset = offset; t.output = output;
+  return droi_forward(p, t, (hipStream_t)stream);
+}
+
+int mdconv_droi_backward(const mdconv_droi_desc *d, const void *input, const void *rois, const void *offset,
+                         const void *grad_output, void *grad_input, void *grad_offset, void *workspace,
+                         size_t workspace_bytes, void *stream) {
+  g_err[0] = 0;
+  int rc = droi_validate(d, true);
+  if (rc) return rc;
+  if ((rc = require(input, "input")) || (rc = require(rois, "rois")) || (rc = require(grad_output, "grad_output"))) return rc;
+  if (d->with_offset && ((rc = require(offset, "offset")) || (rc = require(grad_offset, "grad_offset")))) return rc;
+  if (!(d->flags & MDCONV_FLAG_NO_GRAD_INPUT) && (rc = require(grad_input, "grad_input"))) return rc;
+  DroiPlan p;
+  const char *why;
+  if (!droi_plan(d, true, &p, &why)) return droi_refuse(why);
+  if ((rc = check_ws(workspace, workspace_bytes, p.total))) return rc;
+  DroiTensors t = {};
+  t.input = input; t.rois = rois; t.offset = offset; t.grad_output = grad_output;
+  t.grad_input = grad_input; t.grad_offset = grad_offset;
+  return droi_backward(p, t, workspace, (hipStream_t)stream);
 }
 
 }  // extern "C"
