@@ -481,6 +481,74 @@ int mdconv_msda_backward(const mdconv_msda_desc *d, const void *value, const voi
                          void *grad_sampling_locations, void *grad_attention_weights, void *workspace,
                          size_t workspace_bytes, void *stream);
 
+/* --- 3-D multi-scale deformable attention: the operator above over volumes ------------------------
+ * (Deformable transformer stages of volumetric and video models: CoTr-style 3-D deformable encoders for CT / MR volumes,
+ * spatio-temporal deformable attention over (T, H, W) feature pyramids.)  An operator of its own with a descriptor of its
+ * own and kernels of its own; nothing above changes.  N images, M heads of D channels, Lq queries, L levels
+ * (1..MDCONV_MSDA_MAX_LEVELS) of P points; every tensor dense and row-major:
+ *     value               [N, S, M, D]         S = sum_l T_l*H_l*W_l: the levels concatenated in order, each row-major
+ *                                              ((z*H_l + y)*W_l + x)
+ *     sampling_locations  [N, Lq, M, L, P, 3]  last axis (x, y, z), normalised: 0..1 spans the level (grid_sample's order
+ *                                              for 5-D inputs)
+ *     attention_weights   [N, Lq, M, L, P]
+ *     output              [N, Lq, M*D]
+ *     x = loc_x * W_l - 0.5,   y = loc_y * H_l - 0.5,   z = loc_z * T_l - 0.5       (voxel coordinates in level l)
+ *     out[n,q,m,:] = sum_{l,p} attn[n,q,m,l,p] * trilinear(value[n, start_l + ., m, :], z, y, x)
+ *  - start_l is the cumulative sum of the extents before level l: the level starts are not an input.
+ *  - trilinear reads the eight neighbours of (z, y, x); a neighbour outside the level contributes zero and is never loaded.
+ *    A sample with a coordinate <= -1 or >= size on any of the three axes contributes nothing, to the output and to every
+ *    gradient (the 2-D operator's gate on three axes).  The OUTPUT equals grid_sample (mode "bilinear", zero padding,
+ *    align_corners = false) on 5-D input everywhere, and so do the gradients off the lattice and away from the edge of the
+ *    gate.  On the lattice the derivative is the right-sided one of the cell floor(x), floor(y), floor(z); a gated-out
+ *    sample has gradient exactly zero in grad_sampling_locations and grad_attention_weights, -1 and size included.
+ *  - The backward returns grad_value, grad_sampling_locations (which carries the factors W_l for x, H_l for y and T_l for z)
+ *    and grad_attention_weights in the layouts of their forward tensors; `accumulate` is the write mode of
+ *    mdconv_desc.accumulate.
+ *  - dtype (MDCONV_F32, MDCONV_F16 or MDCONV_BF16) is the type of value, output, grad_output and grad_value; coord_dtype is
+ *    the type of sampling_locations, attention_weights and their gradients: equal to dtype, or MDCONV_F32 -- the five
+ *    pairings of the 2-D operator.  All arithmetic is fp32, each result is rounded once.
+ *  - Shape rule (else MDCONV_EUNSUPPORTED, with the rule in the error message, before anything is launched): D a multiple
+ *    of 4 for fp32 and of 8 for 16-bit values (rows of 16 bytes), T_l*H_l*W_l of every level and every tensor below 2^31
+ *    (rows, bytes), L*P <= 4096, and for a backward with grad_value N*M <= 65535 and L*P*Lq*8 below 2^31.
+ *  - flags: MDCONV_FLAG_DETERMINISTIC and MDCONV_FLAG_NO_GRAD_INPUT only (the latter: no grad_value); any other bit is
+ *    MDCONV_EINVAL.  No result is summed with floating-point atomics: output and the two coordinate gradients are
+ *    bit-identical from call to call, grad_value is with MDCONV_FLAG_DETERMINISTIC and agrees to rounding otherwise.  With
+ *    MDCONV_FLAG_NO_GRAD_INPUT grad_value may be NULL and is never touched; the other gradients are bit for bit those of the
+ *    full call.  Forwards ignore both flags.
+ *  - A call checks in this order: the descriptor (MDCONV_EINVAL), the pointers (MDCONV_ENULL), the shape rule
+ *    (MDCONV_EUNSUPPORTED), the workspace (MDCONV_EWORKSPACE: size and 16-byte alignment, as above).
+ *  - The workspace figure is exact, 0 for the forward, and honours both flags.  A call is a plain chain of kernels on the
+ *    caller's stream: no second stream, no host synchronisation; it captures into a HIP graph.
+ *  No published operator is the model: the published MSDeformAttn kernel is 2-D only, so fidelity to any published operator
+ *  is UNPINNED; the yardstick is the per-level grid_sample composition on 5-D tensors. */
+typedef struct mdconv_msda3d_desc {
+  int dtype;           /* value, output, grad_output, grad_value: MDCONV_F32 / MDCONV_F16 / MDCONV_BF16 */
+  int coord_dtype;     /* sampling_locations, attention_weights and their gradients: `dtype` or MDCONV_F32 */
+  int batch;           /* N */
+  int heads;           /* M */
+  int head_channels;   /* D */
+  int queries;         /* Lq */
+  int levels;          /* L, 1..MDCONV_MSDA_MAX_LEVELS */
+  int points;          /* P */
+  int level_sz[MDCONV_MSDA_MAX_LEVELS][3];  /* (T_l, H_l, W_l) of the first `levels` rows; the others are ignored */
+  int accumulate;      /* backward write mode: 1 = add to grad_*, 0 = overwrite */
+  int flags;           /* MDCONV_FLAG_DETERMINISTIC | MDCONV_FLAG_NO_GRAD_INPUT */
+} mdconv_msda3d_desc;
+/* `mdconv_msda3d_desc d = MDCONV_MSDA3D_DESC_INIT;` then fill in the shape (fp32, accumulate, no flags) */
+#define MDCONV_MSDA3D_DESC_INIT { 0, 0, 0, 0, 0, 0, 0, 0, {{0, 0, 0}}, 1, 0 }
+
+/* S, the rows of `value` per image: the sum of T_l*H_l*W_l over the levels; -1 for a bad descriptor. */
+int mdconv_msda3d_value_len(const mdconv_msda3d_desc *d);
+/* Scratch bytes of the forward (backward = 0: always 0) or the backward (backward = 1) of `d`; 0 for a descriptor that is
+ * invalid or outside the shape rule. */
+size_t mdconv_msda3d_workspace_bytes(const mdconv_msda3d_desc *d, int backward);
+int mdconv_msda3d_forward(const mdconv_msda3d_desc *d, const void *value, const void *sampling_locations,
+                          const void *attention_weights, void *output, void *workspace, size_t workspace_bytes, void *stream);
+int mdconv_msda3d_backward(const mdconv_msda3d_desc *d, const void *value, const void *sampling_locations,
+                           const void *attention_weights, const void *grad_output, void *grad_value,
+                           void *grad_sampling_locations, void *grad_attention_weights, void *workspace,
+                           size_t workspace_bytes, void *stream);
+
 /* --- DCNv4 operator: the DCNv3 core operator's sampling with one packed coordinate tensor ----------
  * The sampling operator of the "DCNv4" block, the successor of DCNv3: no weight, no bias, no softmax over the taps -- the
  * masks are whatever the linear layer before it produced, of any sign and size -- unless MDCONV_FLAG_SOFTMAX asks for one.  An operator of its own with a descriptor of

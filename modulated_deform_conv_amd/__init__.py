@@ -25,6 +25,11 @@ behind the reference's own operator surface.
                                                        tensors, offsets in the same type or fp32): DeformRoIPoolFunction,
                                                        deform_roi_pool, deform_roi_pool_forward / _backward, DeformRoIPool,
                                                        DeformRoIPoolPack, ModulatedDeformRoIPoolPack -- also exported here
+    modulated_deform_conv_amd.msda3d                   3-D multi-scale deformable attention over volumes (levels of
+                                                       (T, H, W), locations (x, y, z), kernels of its own):
+                                                       MSDeformAttn3DFunction, ms_deform_attn_3d,
+                                                       ms_deform_attn_3d_forward / _backward, MSDeformAttn3D -- also
+                                                       exported here
     modulated_deform_conv_amd.distributed              batch-sharded multi-GPU helper (RCCL)
 
 All compute runs in libmdconv_hip.so (hand-written HIP, C ABI in include/mdconv.h); there is no
@@ -41,7 +46,9 @@ _FDA = ("flash_deform_attn_forward", "flash_deform_attn_backward", "FlashDeformA
         "FlashDeformAttn", "pack_loc_attn", "unpack_loc_attn")
 _DROI = ("deform_roi_pool_forward", "deform_roi_pool_backward", "DeformRoIPoolFunction", "deform_roi_pool", "DeformRoIPool",
          "DeformRoIPoolPack", "ModulatedDeformRoIPoolPack")
-__all__ = list(_DCNV3 + _MSDA + _DCNV4 + _FDA + _DROI)
+_MSDA3D = ("ms_deform_attn_3d_forward", "ms_deform_attn_3d_backward", "MSDeformAttn3DFunction", "ms_deform_attn_3d",
+           "MSDeformAttn3D")
+__all__ = list(_DCNV3 + _MSDA + _DCNV4 + _FDA + _DROI + _MSDA3D)
 
 
 def __getattr__(name):
@@ -61,4 +68,7 @@ def __getattr__(name):
     if name in _DROI:
         from . import droi
         return getattr(droi, name)
+    if name in _MSDA3D:
+        from . import msda3d
+        return getattr(msda3d, name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

@@ -41,6 +41,7 @@ EXPORTS = (
     "mdconv_dcnv4_backward",
     "mdconv_fda_value_len", "mdconv_fda_loc_attn_len", "mdconv_fda_workspace_bytes", "mdconv_fda_forward", "mdconv_fda_backward",
     "mdconv_droi_workspace_bytes", "mdconv_droi_forward", "mdconv_droi_backward",
+    "mdconv_msda3d_value_len", "mdconv_msda3d_workspace_bytes", "mdconv_msda3d_forward", "mdconv_msda3d_backward",
 )
 
 
@@ -98,6 +99,12 @@ class MdconvFdaDesc(ctypes.Structure):
     """Mirror of ``struct mdconv_fda_desc`` (include/mdconv.h, "Packed deformable attention"): the fields of
     ``MdconvMsdaDesc``; ``level_sz`` rows are (H, W)."""
     _fields_ = list(MdconvMsdaDesc._fields_)
+
+
+class MdconvMsda3dDesc(ctypes.Structure):
+    """Mirror of ``struct mdconv_msda3d_desc`` (include/mdconv.h, "3-D multi-scale deformable attention"): the fields of
+    ``MdconvMsdaDesc`` with ``level_sz`` rows of (T, H, W)."""
+    _fields_ = [(n, (ctypes.c_int * 3) * MSDA_MAX_LEVELS) if n == "level_sz" else (n, t) for n, t in MdconvMsdaDesc._fields_]
 
 
 class MdconvDroiDesc(ctypes.Structure):
@@ -159,7 +166,7 @@ def lib():
             L.mdconv_planned_kernels.argtypes = [ctypes.c_void_p, ctypes.c_int]
         missing = (() if has_math_query else ("mdconv_math_bf16_used",)) + (() if has_layout_query else ("mdconv_result_layout_supported",))
         missing += () if has_plan_query else ("mdconv_planned_kernels",)
-        missing += tuple(n for n in EXPORTS if n.startswith(("mdconv_dcnv3_", "mdconv_msda_", "mdconv_dcnv4_", "mdconv_fda_", "mdconv_droi_")) and not hasattr(L, n))
+        missing += tuple(n for n in EXPORTS if n.startswith(("mdconv_dcnv3_", "mdconv_msda_", "mdconv_dcnv4_", "mdconv_fda_", "mdconv_droi_", "mdconv_msda3d_")) and not hasattr(L, n))
         for name in EXPORTS[11:]:
             if name not in missing:
                 getattr(L, name).restype = ctypes.c_int
@@ -189,6 +196,11 @@ def lib():
         if hasattr(L, "mdconv_droi_workspace_bytes"):
             L.mdconv_droi_workspace_bytes.restype = ctypes.c_size_t
             L.mdconv_droi_workspace_bytes.argtypes = [ctypes.c_void_p, ctypes.c_int]
+        # (likewise a build from before 3-D multi-scale deformable attention: msda3d.py raises there)
+        if hasattr(L, "mdconv_msda3d_workspace_bytes"):
+            L.mdconv_msda3d_value_len.argtypes = [ctypes.c_void_p]
+            L.mdconv_msda3d_workspace_bytes.restype = ctypes.c_size_t
+            L.mdconv_msda3d_workspace_bytes.argtypes = [ctypes.c_void_p, ctypes.c_int]
         if L.mdconv_abi_version() != ABI_VERSION:
             raise ImportError("libmdconv_hip.so ABI version mismatch")
         _lib = L

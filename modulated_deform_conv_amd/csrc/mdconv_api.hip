@@ -17,6 +17,7 @@
 #include "dcn3_plan.hpp"
 #include "dcn4_plan.hpp"
 #include "msda_plan.hpp"
+#include "msda3_plan.hpp"
 #include "fda_plan.hpp"
 #include "droi_plan.hpp"
 #include "dw_plan.hpp"
@@ -812,9 +813,14 @@ template <class Desc> static int attn_validate(const Desc *d, const char *op) {
     set_error("%s: levels must be 1..%d, is %d", op, MDCONV_MSDA_MAX_LEVELS, d->levels);
     return MDCONV_EINVAL;
   }
+  constexpr int kAxes = (int)(sizeof(d->level_sz[0]) / sizeof(int));   // 2: (H, W); 3: (T, H, W)
   for (int l = 0; l < d->levels; ++l) {
-    if (d->level_sz[l][0] <= 0 || d->level_sz[l][1] <= 0) {
-      set_error("%s: level %d has a non-positive extent (%d x %d)", op, l, d->level_sz[l][0], d->level_sz[l][1]);
+    const int *e = d->level_sz[l];
+    bool bad = false;
+    for (int a = 0; a < kAxes; ++a) bad = bad || e[a] <= 0;
+    if (bad) {
+      if (kAxes == 2) set_error("%s: level %d has a non-positive extent (%d x %d)", op, l, e[0], e[1]);
+      else set_error("%s: level %d has a non-positive extent (%d x %d x %d)", op, l, e[0], e[1], e[kAxes - 1]);
       return MDCONV_EINVAL;
     }
   }
@@ -831,8 +837,13 @@ template <class Desc> static int attn_validate(const Desc *d, const char *op) {
 }
 static int msda_validate(const mdconv_msda_desc *d) { return attn_validate(d, "msda"); }
 static int fda_validate(const mdconv_fda_desc *d) { return attn_validate(d, "fda"); }
+static int msda3d_validate(const mdconv_msda3d_desc *d) { return attn_validate(d, "msda3d"); }
 static int msda_refuse(const char *why) {
   set_error("msda: outside the shape rule of the operator: %s", why);
+  return MDCONV_EUNSUPPORTED;
+}
+static int msda3d_refuse(const char *why) {
+  set_error("msda3d: outside the shape rule of the operator: %s", why);
   return MDCONV_EUNSUPPORTED;
 }
 static int fda_refuse(const char *why) {
@@ -1292,6 +1303,75 @@ int mdconv_msda_backward(const mdconv_msda_desc *d, const void *value, const voi
   t.value = value; t.loc = sampling_locations; t.attn = attention_weights; t.grad_output = grad_output;
   t.grad_value = grad_value; t.grad_loc = grad_sampling_locations; t.grad_attn = grad_attention_weights;
   return msda_backward(p, t, workspace, (hipStream_t)stream);
+}
+
+int mdconv_msda3d_value_len(const mdconv_msda3d_desc *d) {
+  g_err[0] = 0;
+  if (msda3d_validate(d)) return -1;
+  long long S = 0;
+  bool big = false;
+  for (int l = 0; l < d->levels; ++l) {
+    const long long plane = (long long)d->level_sz[l][1] * d->level_sz[l][2];   // below 2^62
+    if (plane >= (1LL << 31)) big = true;
+    else S += plane * d->level_sz[l][0];   // (8 products below 2^62)
+  }
+  if (big || S >= (1LL << 31)) {
+    set_error("msda3d: the levels have 2^31 rows or more");
+    return -1;
+  }
+  return (int)S;
+}
+
+size_t mdconv_msda3d_workspace_bytes(const mdconv_msda3d_desc *d, int backward) {
+  Msda3Plan p;
+  const char *why;
+  g_err[0] = 0;
+  if (msda3d_validate(d)) return 0;
+  if (!msda3_plan(d, backward != 0, &p, &why)) {
+    msda3d_refuse(why);
+    return 0;
+  }
+  return p.total;
+}
+
+int mdconv_msda3d_forward(const mdconv_msda3d_desc *d, const void *value, const void *sampling_locations,
+                          const void *attention_weights, void *output, void *workspace, size_t workspace_bytes, void *stream) {
+  g_err[0] = 0;
+  int rc = msda3d_validate(d);
+  if (rc) return rc;
+  if ((rc = require(value, "value")) || (rc = require(sampling_locations, "sampling_locations")) ||
+      (rc = require(attention_weights, "attention_weights")) || (rc = require(output, "output")))
+    return rc;
+  Msda3Plan p;
+  const char *why;
+  if (!msda3_plan(d, false, &p, &why)) return msda3d_refuse(why);
+  if ((rc = check_ws(workspace, workspace_bytes, p.total))) return rc;
+  Msda3Tensors t = {};
+  t.value = value; t.loc = sampling_locations; t.attn = attention_weights; t.output = output;
+  return msda3_forward(p, t, (hipStream_t)stream);
+}
+
+int mdconv_msda3d_backward(const mdconv_msda3d_desc *d, const void *value, const void *sampling_locations,
+                           const void *attention_weights, const void *grad_output, void *grad_value,
+                           void *grad_sampling_locations, void *grad_attention_weights, void *workspace,
+                           size_t workspace_bytes, void *stream) {
+  g_err[0] = 0;
+  int rc = msda3d_validate(d);
+  if (rc) return rc;
+  if ((rc = require(value, "value")) || (rc = require(sampling_locations, "sampling_locations")) ||
+      (rc = require(attention_weights, "attention_weights")) || (rc = require(grad_output, "grad_output")) ||
+      (rc = require(grad_sampling_locations, "grad_sampling_locations")) ||
+      (rc = require(grad_attention_weights, "grad_attention_weights")))
+    return rc;
+  if (!(d->flags & MDCONV_FLAG_NO_GRAD_INPUT) && (rc = require(grad_value, "grad_value"))) return rc;
+  Msda3Plan p;
+  const char *why;
+  if (!msda3_plan(d, true, &p, &why)) return msda3d_refuse(why);
+  if ((rc = check_ws(workspace, workspace_bytes, p.total))) return rc;
+  Msda3Tensors t = {};
+  t.value = value; t.loc = sampling_locations; t.attn = attention_weights; t.grad_output = grad_output;
+  t.grad_value = grad_value; t.grad_loc = grad_sampling_locations; t.grad_attn = grad_attention_weights;
+  return msda3_backward(p, t, workspace, (hipStream_t)stream);
 }
 
 int mdconv_fda_value_len(const mdconv_fda_desc *d) {

@@ -1,0 +1,277 @@
+"""3-D multi-scale deformable attention on the MI355X-native backend: deformable attention over volumes and video
+pyramids on channels-last tensors (include/mdconv.h, "3-D multi-scale deformable attention"; INTEGRATION.md has the
+contract and what is unpinned).
+
+    ms_deform_attn_3d_forward / ms_deform_attn_3d_backward   the entry points on dense CUDA tensors
+    MSDeformAttn3DFunction   autograd.Function over mdconv_msda3d_forward / mdconv_msda3d_backward
+    ms_deform_attn_3d        the functional form
+    MSDeformAttn3D           nn.Module: the attention block around the operator, composed from framework operators
+
+``value [N, S, M, D]`` (the levels concatenated, each (z*H + y)*W + x), ``sampling_locations [N, Lq, M, L, P, 3]``
+((x, y, z), normalised), ``attention_weights [N, Lq, M, L, P]`` -> ``output [N, Lq, M*D]``; ``spatial_shapes`` rows are
+(T, H, W).  ``value`` is fp32 / fp16 / bf16; the two coordinate tensors have its dtype or are fp32.  CPU tensors raise
+``NotImplementedError``: there is no CPU or PyTorch fallback.
+"""
+import ctypes
+
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+from torch.autograd import Function
+from torch.autograd.function import once_differentiable
+
+from . import _capi
+
+__all__ = ["ms_deform_attn_3d_forward", "ms_deform_attn_3d_backward", "MSDeformAttn3DFunction", "ms_deform_attn_3d",
+           "MSDeformAttn3D"]
+
+_DTYPES = {torch.float32: _capi.F32, torch.float16: _capi.F16, torch.bfloat16: _capi.BF16}
+
+
+def _shapes(spatial_shapes):
+    """``spatial_shapes`` as a tuple of (T, H, W) ints.  A tensor is read with ``.tolist()``: for a CUDA tensor that is a
+    host synchronisation (and impossible during graph capture) -- pass host data to avoid it."""
+    if isinstance(spatial_shapes, torch.Tensor):
+        spatial_shapes = spatial_shapes.tolist()
+    shapes = tuple((int(t), int(h), int(w)) for t, h, w in spatial_shapes)
+    if not 1 <= len(shapes) <= _capi.MSDA_MAX_LEVELS:
+        raise ValueError("msda3d: 1..%d levels, got %d" % (_capi.MSDA_MAX_LEVELS, len(shapes)))
+    return shapes
+
+
+def _check_starts(shapes, level_start_index):
+    """``level_start_index`` is not an input of the operator (the starts are the cumulative sums); host data is checked
+    against them, a CUDA tensor is ignored rather than synchronised on."""
+    if level_start_index is None or (isinstance(level_start_index, torch.Tensor) and level_start_index.is_cuda):
+        return
+    got = [int(v) for v in (level_start_index.tolist() if isinstance(level_start_index, torch.Tensor) else level_start_index)]
+    want, s = [], 0
+    for t, h, w in shapes:
+        want.append(s)
+        s += t * h * w
+    if got != want:
+        raise ValueError("msda3d: level_start_index %s is not the cumulative sum %s of spatial_shapes" % (got, want))
+
+
+def _desc(value, loc, shapes, accumulate=1, flags=0):
+    if value.dtype not in _DTYPES or loc.dtype not in _DTYPES:
+        raise TypeError("msda3d: dtypes %s / %s are not float32, float16 or bfloat16" % (value.dtype, loc.dtype))
+    if value.dim() != 4 or loc.dim() != 6:
+        raise ValueError("msda3d: value must be [N, S, M, D] and sampling_locations [N, Lq, M, L, P, 3], got %s and %s" % (
+            tuple(value.shape), tuple(loc.shape)))
+    d = _capi.MdconvMsda3dDesc()
+    d.dtype, d.coord_dtype = _DTYPES[value.dtype], _DTYPES[loc.dtype]
+    d.batch, d.heads, d.head_channels = int(value.shape[0]), int(value.shape[2]), int(value.shape[3])
+    d.queries, d.levels, d.points = int(loc.shape[1]), len(shapes), int(loc.shape[4])
+    for l, (t, h, w) in enumerate(shapes):
+        d.level_sz[l][0], d.level_sz[l][1], d.level_sz[l][2] = t, h, w
+    d.accumulate, d.flags = int(accumulate), int(flags)
+    return d
+
+
+def _check(d, shapes, value, loc, attn, **others):
+    """Shapes, dtypes, devices and density of the tensors of a call; ``others`` have the shape of ``output``."""
+    N, M, D, Lq, L, P = d.batch, d.heads, d.head_channels, d.queries, d.levels, d.points
+    S = sum(t * h * w for t, h, w in shapes)
+    want = dict(value=(N, S, M, D), sampling_locations=(N, Lq, M, L, P, 3), attention_weights=(N, Lq, M, L, P))
+    want.update({k: (N, Lq, M * D) for k in others})
+    tensors = dict(value=value, sampling_locations=loc, attention_weights=attn, **others)
+    for name, t in tensors.items():
+        if tuple(t.shape) != want[name]:
+            raise ValueError("msda3d: %s must be %s, got %s" % (name, want[name], tuple(t.shape)))
+        like = loc if name in ("sampling_locations", "attention_weights") else value
+        if t.dtype != like.dtype or t.device != value.device:
+            raise ValueError("msda3d: %s is %s on %s; value is %s on %s and the coordinate tensors are %s (value, output and "
+                             "grad_output share one dtype, the two coordinate tensors another: the same, or float32)" % (
+                                 name, t.dtype, t.device, value.dtype, value.device, loc.dtype))
+        if not t.is_contiguous():
+            raise ValueError("msda3d: %s must be dense and row-major (contiguous)" % name)
+    if loc.dtype != value.dtype and loc.dtype != torch.float32:
+        raise ValueError("msda3d: the coordinate tensors are %s, value is %s: they must have value's dtype or float32" % (
+            loc.dtype, value.dtype))
+    return (N, Lq, M * D)
+
+
+def _ptr(t):
+    return ctypes.c_void_p(t.data_ptr() if t is not None else 0)
+
+
+def _run(fn_name, d, backward, args_before_ws, input):
+    L = _capi.lib()
+    with torch.cuda.device(input.device):
+        ws_bytes = L.mdconv_msda3d_workspace_bytes(ctypes.byref(d), int(backward))
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=input.device) if ws_bytes else None
+        stream = torch.cuda.current_stream().cuda_stream
+        rc = getattr(L, fn_name)(ctypes.byref(d), *args_before_ws, ctypes.c_void_p(ws.data_ptr() if ws is not None else 0),
+                                 ctypes.c_size_t(ws_bytes), ctypes.c_void_p(stream))
+    if rc != 0:
+        raise RuntimeError("%s failed (%d): %s" % (fn_name, rc, _capi.last_error()))
+
+
+def ms_deform_attn_3d_forward(value, spatial_shapes, sampling_locations, attention_weights, output=None):
+    """The forward entry point on dense CUDA tensors; allocates ``output`` unless it is given."""
+    if not value.is_cuda:
+        raise NotImplementedError
+    shapes = _shapes(spatial_shapes)
+    d = _desc(value, sampling_locations, shapes)
+    others = {} if output is None else dict(output=output)
+    shape = _check(d, shapes, value, sampling_locations, attention_weights, **others)
+    if output is None:
+        output = torch.empty(shape, dtype=value.dtype, device=value.device)
+    _run("mdconv_msda3d_forward", d, False, [_ptr(value), _ptr(sampling_locations), _ptr(attention_weights), _ptr(output)],
+         value)
+    return output
+
+
+def ms_deform_attn_3d_backward(value, spatial_shapes, sampling_locations, attention_weights, grad_output, grads=None,
+                               need_grad_value=True, deterministic=False, accumulate=None):
+    """The backward entry point.  ``grads`` = (grad_value | None, grad_sampling_locations, grad_attention_weights):
+    caller-allocated buffers the gradients are ADDED to; without it fresh tensors are written.  ``need_grad_value`` false:
+    grad_value is neither computed nor allocated (``MDCONV_FLAG_NO_GRAD_INPUT``) and None is returned there.
+    ``deterministic`` None follows ``_capi.deterministic_mode()``.  ``accumulate`` false with ``grads``: the caller's
+    buffers are overwritten instead.  Returns the three gradients in that order."""
+    if not value.is_cuda:
+        raise NotImplementedError
+    shapes = _shapes(spatial_shapes)
+    det = _capi.deterministic_mode() if deterministic is None else bool(deterministic)
+    flags = (_capi.FLAG_DETERMINISTIC if det else 0) | (0 if need_grad_value else _capi.FLAG_NO_GRAD_INPUT)
+    d = _desc(value, sampling_locations, shapes,
+              accumulate=int(grads is not None if accumulate is None else bool(accumulate)), flags=flags)
+    _check(d, shapes, value, sampling_locations, attention_weights, grad_output=grad_output)
+    if grads is None:
+        grads = (torch.empty_like(value) if need_grad_value else None, torch.empty_like(sampling_locations),
+                 torch.empty_like(attention_weights))
+    gv, gl, ga = grads
+    for name, g, like in (("grad_value", gv, value), ("grad_sampling_locations", gl, sampling_locations),
+                          ("grad_attention_weights", ga, attention_weights)):
+        if g is None and name == "grad_value" and not need_grad_value:
+            continue
+        if g is None or g.shape != like.shape or g.dtype != like.dtype or g.device != like.device or not g.is_contiguous():
+            raise ValueError("msda3d: %s must be a dense tensor of the shape, dtype and device of its forward tensor" % name)
+    _run("mdconv_msda3d_backward", d, True,
+         [_ptr(value), _ptr(sampling_locations), _ptr(attention_weights), _ptr(grad_output),
+          _ptr(gv if need_grad_value else None), _ptr(gl), _ptr(ga)], value)
+    return (gv if need_grad_value else None), gl, ga
+
+
+class MSDeformAttn3DFunction(Function):
+    """``MSDeformAttn3DFunction.apply(value, spatial_shapes, level_start_index, sampling_locations, attention_weights,
+    im2col_step)`` -- the argument order of ``MSDeformAttnFunction``; ``im2col_step`` is accepted for signature parity and
+    unused.  ``spatial_shapes`` is ``[L, 3]`` as (T, H, W), a sequence or a tensor; a CUDA tensor costs a ``.tolist()``
+    synchronisation per call and cannot be read during graph capture, so pass host data there.  ``level_start_index`` is
+    checked against the cumulative sums when it is host data (a wrong one raises ``ValueError``) and ignored otherwise.
+    Under ``torch.autocast`` ``value`` runs in the autocast dtype; coordinate tensors that are fp32 stay fp32 (the mixed
+    call), others run in the autocast dtype.  The gradients go back in the dtypes the caller's tensors have."""
+
+    @staticmethod
+    def forward(ctx, value, spatial_shapes, level_start_index, sampling_locations, attention_weights, im2col_step=64):
+        shapes = _shapes(spatial_shapes)
+        _check_starts(shapes, level_start_index)   # (before the device check: a wrong one is a ValueError on any device)
+        if not value.is_cuda:
+            raise NotImplementedError
+        ctx.shapes = shapes
+        ctx.in_dtypes = (value.dtype, sampling_locations.dtype, attention_weights.dtype)
+        if torch.is_autocast_enabled("cuda"):
+            value = value.to(torch.get_autocast_dtype("cuda"))
+        # one dtype for the two coordinate tensors: fp32 if either is (or if they disagree), else value's
+        cdt = value.dtype if sampling_locations.dtype == attention_weights.dtype == value.dtype else torch.float32
+        value = value.contiguous()
+        sampling_locations = sampling_locations.to(cdt).contiguous()
+        attention_weights = attention_weights.to(cdt).contiguous()
+        if any(ctx.needs_input_grad):
+            ctx.save_for_backward(value, sampling_locations, attention_weights)
+        return ms_deform_attn_3d_forward(value, shapes, sampling_locations, attention_weights)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_output):
+        if not grad_output.is_cuda:
+            raise NotImplementedError
+        value, loc, attn = ctx.saved_tensors
+        grad_output = grad_output.to(value.dtype).contiguous()
+        # selective backward: grad_value is neither computed nor allocated when `value` needs no gradient
+        gv, gl, ga = ms_deform_attn_3d_backward(value, ctx.shapes, loc, attn, grad_output,
+                                                need_grad_value=bool(ctx.needs_input_grad[0]), deterministic=None)
+        back = lambda g, dt: g if g is None or g.dtype == dt else g.to(dt)
+        dv, dl, da = ctx.in_dtypes
+        return back(gv, dv), None, None, back(gl, dl), back(ga, da), None
+
+
+def ms_deform_attn_3d(value, spatial_shapes, sampling_locations, attention_weights, level_start_index=None):
+    """Functional form of ``MSDeformAttn3DFunction``.  A ``value`` that needs no gradient runs the backward with
+    ``MDCONV_FLAG_NO_GRAD_INPUT``."""
+    return MSDeformAttn3DFunction.apply(value, spatial_shapes, level_start_index, sampling_locations, attention_weights, 64)
+
+
+class MSDeformAttn3D(nn.Module):
+    """The 3-D multi-scale deformable attention block: value projection, the ``sampling_offsets`` (``M*L*P*3`` outputs,
+    (x, y, z) per point) and ``attention_weights`` linears on the query (softmax over the L*P taps of a head), the core
+    operator, output projection.  Everything but the core operator is a framework operator; parameter names are those of
+    ``MSDeformAttn``.
+
+    Initialisation -- THIS PROJECT'S OWN, there is no published 3-D block to follow: ``sampling_offsets.weight`` and both
+    ``attention_weights`` tensors are zero (every tap starts with weight 1 / (L*P)), the projections are Xavier-uniform
+    with zero bias, and the bias of ``sampling_offsets`` is a directional one: head h looks along the h-th point of a
+    Fibonacci spiral on the unit sphere (z = 1 - (2h + 1) / M, azimuth h times the golden angle), scaled so that its largest
+    component is 1, and point p sits p + 1 steps along it, the same on every level."""
+
+    def __init__(self, d_model=256, n_levels=3, n_heads=8, n_points=4):
+        super().__init__()
+        if d_model % n_heads:
+            raise ValueError("d_model must be divisible by n_heads, but got %d and %d" % (d_model, n_heads))
+        self.im2col_step = 64
+        self.d_model, self.n_levels, self.n_heads, self.n_points = d_model, n_levels, n_heads, n_points
+        self.sampling_offsets = nn.Linear(d_model, n_heads * n_levels * n_points * 3)
+        self.attention_weights = nn.Linear(d_model, n_heads * n_levels * n_points)
+        self.value_proj = nn.Linear(d_model, d_model)
+        self.output_proj = nn.Linear(d_model, d_model)
+        self._core = ms_deform_attn_3d
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        nn.init.zeros_(self.sampling_offsets.weight)
+        h = torch.arange(self.n_heads, dtype=torch.float32)
+        z = 1.0 - (2.0 * h + 1.0) / self.n_heads
+        r = (1.0 - z * z).clamp_min(0.0).sqrt()
+        phi = h * 2.399963229728653   # the golden angle
+        grid = torch.stack([r * phi.cos(), r * phi.sin(), z], -1)
+        grid = (grid / grid.abs().max(-1, keepdim=True)[0]).view(self.n_heads, 1, 1, 3).repeat(1, self.n_levels, self.n_points, 1)
+        for i in range(self.n_points):
+            grid[:, :, i, :] *= i + 1
+        with torch.no_grad():
+            self.sampling_offsets.bias.copy_(grid.reshape(-1))
+        nn.init.zeros_(self.attention_weights.weight)
+        nn.init.zeros_(self.attention_weights.bias)
+        for lin in (self.value_proj, self.output_proj):
+            nn.init.xavier_uniform_(lin.weight)
+            nn.init.zeros_(lin.bias)
+
+    def forward(self, query, reference_points, input_flatten, input_spatial_shapes, input_level_start_index=None,
+                input_padding_mask=None):
+        """``query [N, Lq, C]``, ``reference_points [N, Lq, L, 3]`` (x, y, z), normalised; ``input_flatten [N, S, C]``;
+        ``input_spatial_shapes``: L rows (T, H, W), host data or a tensor (a CUDA tensor costs a synchronisation per
+        call); ``input_padding_mask [N, S]``: True where the value is padding.  The offsets are in voxels of their level:
+        they are normalised by (W_l, H_l, T_l)."""
+        N, Lq, _ = query.shape
+        S = input_flatten.shape[1]
+        shapes = _shapes(input_spatial_shapes)
+        if len(shapes) != self.n_levels or sum(t * h * w for t, h, w in shapes) != S:
+            raise ValueError("input_spatial_shapes %s does not describe %d levels of %d rows" % (shapes, self.n_levels, S))
+        M, L, P = self.n_heads, self.n_levels, self.n_points
+        value = self.value_proj(input_flatten)
+        if input_padding_mask is not None:
+            value = value.masked_fill(input_padding_mask[..., None], 0.0)
+        value = value.view(N, S, M, self.d_model // M)
+        offsets = self.sampling_offsets(query).float().view(N, Lq, M, L, P, 3)
+        # (softmax and the locations run in fp32 under autocast: the core then takes fp32 coordinates)
+        weights = F.softmax(self.attention_weights(query).float().view(N, Lq, M, L * P), -1).view(N, Lq, M, L, P)
+        ref = reference_points.float()
+        if ref.shape[-1] != 3:
+            raise ValueError("the last dimension of reference_points must be 3, but is %d" % ref.shape[-1])
+        whd = torch.tensor([[w, h, t] for t, h, w in shapes], dtype=torch.float32, device=query.device)   # (x, y, z) order
+        locations = ref[:, :, None, :, None, :] + offsets / whd[None, None, None, :, None, :]
+        out = self._core(value, shapes, locations, weights, input_level_start_index)
+        return self.output_proj(out)
+
+    def extra_repr(self):
+        return "d_model=%d, n_levels=%d, n_heads=%d, n_points=%d" % (self.d_model, self.n_levels, self.n_heads, self.n_points)
