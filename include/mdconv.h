@@ -366,7 +366,9 @@ int mdconv_modulated_deform_conv3d_backward(const mdconv_desc *d, const void *in
  *     loc_h = ho*stride_h - pad_h + c_h + (j*dil_h - c_h + off_y) * offset_scale
  *     out[b,ho,wo,g,d] = sum_tap mask[b,ho,wo,g,tap] * bilinear(input[b,:,:,g,d], loc_h, loc_w)
  *  - bilinear reads the four neighbours of (loc_h, loc_w); a neighbour outside the image contributes zero and is never
- *    loaded.  A sample with loc <= -1 or loc >= size on either axis contributes nothing, to the output and to every gradient.
+ *    loaded.  A sample contributes iff -1 < loc < size on every axis; a NaN or infinite coordinate (an offset that overflows
+ *    once scaled by offset_scale included) therefore contributes nothing, to the output and to every gradient, and has
+ *    gradient exactly zero.
  *  - On the lattice (loc_h or loc_w a whole number) the interpolant has a kink and the derivative is a convention: the cell
  *    is floor(loc) and the fractional part loc - floor(loc) = 0 belongs to it, so grad_offset is the RIGHT-SIDED derivative --
  *    along x the difference of the neighbours at x0 + 1 and x0 (a neighbour outside the image counting as zero), weighted
@@ -428,8 +430,9 @@ int mdconv_dcnv3_backward(const mdconv_dcnv3_desc *d, const void *input, const v
  *     out[n,q,m,:] = sum_{l,p} attn[n,q,m,l,p] * bilinear(value[n, start_l + ., m, :], y, x)
  *  - start_l is the cumulative sum of the extents before level l: the level starts are not an input.
  *  - bilinear reads the four neighbours of (y, x); a neighbour outside the level contributes zero and is never loaded.  A
- *    sample with x <= -1, y <= -1, x >= W_l or y >= H_l contributes nothing, to the output and to every gradient (the gate
- *    of the DCNv3 core operator).  The OUTPUT equals grid_sample with zero padding and align_corners = false everywhere, and
+ *    sample contributes iff -1 < x < W_l and -1 < y < H_l (the gate of the DCNv3 core operator); a NaN or infinite
+ *    coordinate (a location that overflows once scaled by the extent included) therefore contributes nothing, to the output
+ *    and to every gradient, and has gradient exactly zero.  For finite coordinates the OUTPUT equals grid_sample with zero padding and align_corners = false everywhere, and
  *    so do the gradients off the lattice and away from the edge of the gate.  On the lattice the derivative is that
  *    operator's convention: the right-sided one of the cell floor(x), floor(y); and a gated-out sample has gradient exactly
  *    zero in grad_sampling_locations and grad_attention_weights, also at x == -1 and x == W_l exactly -- at x == -1
@@ -496,8 +499,9 @@ int mdconv_msda_backward(const mdconv_msda_desc *d, const void *value, const voi
  *     out[n,q,m,:] = sum_{l,p} attn[n,q,m,l,p] * trilinear(value[n, start_l + ., m, :], z, y, x)
  *  - start_l is the cumulative sum of the extents before level l: the level starts are not an input.
  *  - trilinear reads the eight neighbours of (z, y, x); a neighbour outside the level contributes zero and is never loaded.
- *    A sample with a coordinate <= -1 or >= size on any of the three axes contributes nothing, to the output and to every
- *    gradient (the 2-D operator's gate on three axes).  The OUTPUT equals grid_sample (mode "bilinear", zero padding,
+ *    A sample contributes iff -1 < coordinate < size on every one of the three axes (the 2-D operator's gate on three axes); a
+ *    NaN or infinite coordinate therefore contributes nothing, to the output and to every gradient, and has gradient exactly
+ *    zero.  For finite coordinates the OUTPUT equals grid_sample (mode "bilinear", zero padding,
  *    align_corners = false) on 5-D input everywhere, and so do the gradients off the lattice and away from the edge of the
  *    gate.  On the lattice the derivative is the right-sided one of the cell floor(x), floor(y), floor(z); a gated-out
  *    sample has gradient exactly zero in grad_sampling_locations and grad_attention_weights, -1 and size included.
@@ -561,8 +565,10 @@ int mdconv_msda3d_backward(const mdconv_msda3d_desc *d, const void *value, const
  *     K = kh*kw - (remove_center ? 1 : 0)
  *     kernel-grid tap u = i*kh + j, i in [0, kw) the kernel's WIDTH index, j in [0, kh) its height index (as in DCNv3)
  *     with remove_center the grid tap (kh*kw - 1)/2 is skipped: tensor tap t maps to u = t + (t >= (kh*kw - 1)/2)
- *     Ho, Wo, c_h, c_w, loc_h, loc_w, the gate (-1 < loc < size), the corner rule and the derivative on the lattice (the
- *     right-sided one of the cell floor(loc); exactly zero for a gated-out sample, loc == -1 and loc == size included):
+ *     Ho, Wo, c_h, c_w, loc_h, loc_w, the gate (a sample contributes iff -1 < loc < size on every axis; a NaN or infinite
+ *     coordinate therefore contributes nothing and has gradient exactly zero), the corner rule and the derivative on the
+ *     lattice (the right-sided one of the cell floor(loc); exactly zero for a gated-out sample, loc == -1 and loc == size
+ *     included):
  *     exactly those of the DCNv3 core operator above, with (i, j) taken from u
  *     out[b,ho,wo,g,:] = sum_t mask[t] * bilinear(input[b,:,:,g,:], loc_h(t), loc_w(t))
  *  - The padding columns of offset_mask are never read into any result (they may hold NaN).  The backward returns grad_input
@@ -648,8 +654,9 @@ int mdconv_dcnv4_backward(const mdconv_dcnv4_desc *d, const void *input, const v
  *     output             [N, Lq, M*D]
  *     a[t] = exp(logit[t] - max_s logit[s]) / sum_s exp(logit[s] - max_s logit[s])        (fp32)
  *     out[n,q,m,:] = sum_t a[t] * bilinear(value[n, start_l + ., m, :], y_t, x_t)
- *     pixel coordinates, level starts, the gate (-1 < loc < size), the corner rule and the derivative on the lattice (the
- *     right-sided one of the cell floor(loc); a gated-out tap has location gradients of exactly zero, loc == -1 and
+ *     pixel coordinates, level starts, the gate (a tap contributes iff -1 < loc < size on every axis; a NaN or infinite
+ *     coordinate therefore contributes nothing and has gradient exactly zero), the corner rule and the derivative on the
+ *     lattice (the right-sided one of the cell floor(loc); a gated-out tap has location gradients of exactly zero, loc == -1 and
  *     loc == size included, and g[t] = 0 in the logit gradient below): exactly those of multi-scale deformable attention above
  *  - The logits must be finite.  They may be large: the maximum is subtracted before the exponential.
  *  - The backward returns grad_value and grad_sampling_loc_attn in the layouts of value and sampling_loc_attn: the location
@@ -718,8 +725,9 @@ int mdconv_fda_backward(const mdconv_fda_desc *d, const void *value, const void 
  *     dx  = gamma * rw * offset[r,0,ph,pw],  dy = gamma * rh * offset[r,1,ph,pw]               (0 without offset)
  *     y(iy) = y1s + dy + ph*bh + (iy + 0.5) * bh / gh,   x(ix) = x1s + dx + pw*bw + (ix + 0.5) * bw / gw
  *     output[r,ph,pw,c] = (1/cnt) * sum_{iy<gh, ix<gw} bil(input[b,:,:,c], y(iy), x(ix))
- *  - bil(y, x) is RoIAlign's sample: it contributes nothing, to the output and to every gradient, when y < -1, y > H, x < -1
- *    or x > W.  Otherwise y = max(y, 0), y_lo = floor(y); if y_lo >= H-1 then y_lo = y_hi = H-1 and y = H-1, else
+ *  - bil(y, x) is RoIAlign's sample: it contributes iff -1 <= y <= H and -1 <= x <= W (RoIAlign's gate is closed); a NaN or
+ *    infinite coordinate -- a NaN or infinite offset, or one that overflows once scaled by gamma * rw -- therefore contributes
+ *    nothing, to the output and to every gradient, and the grad_offset of its bin is exactly zero.  Otherwise y = max(y, 0), y_lo = floor(y); if y_lo >= H-1 then y_lo = y_hi = H-1 and y = H-1, else
  *    y_hi = y_lo + 1; the same for x; the value is the bilinear mix of the four (possibly coinciding) neighbours.  No element
  *    outside the image is ever loaded.  All arithmetic is fp32, each result is rounded once.
  *  - A RoI contributes NOTHING when its batch index is not an integer in [0, B) or any of its five numbers is not finite: its

@@ -21,21 +21,25 @@ def out_hw(H, W, kernel, stride, pad, dilation):
     return (H + 2 * ph - (dh * (kh - 1) + 1)) // sh + 1, (W + 2 * pw - (dw * (kw - 1) + 1)) // sw + 1
 
 
-def positions(offset, H, W, kernel, stride, pad, dilation, group, offset_scale):
-    """(loc_h, loc_w) [B, Ho, Wo, G, K] in input pixel coordinates, fp64, straight from the contract."""
+def positions(offset, H, W, kernel, stride, pad, dilation, group, offset_scale, position_dtype=None):
+    """(loc_h, loc_w) [B, Ho, Wo, G, K] in input pixel coordinates, fp64, straight from the contract.  ``position_dtype``
+    (``torch.float32``): the same sums evaluated in that type, one rounding per operation in the contract's order --
+    (tap + offset) * offset_scale, then + the pixel's base, which is a whole number -- and widened to fp64 again: what the
+    positions are worth once fp32 arithmetic has formed them (half an ulp of the coordinate: 3e-5 px at 683)."""
     (kh, kw), (sh, sw), (ph, pw), (dh, dw) = map(_pair, (kernel, stride, pad, dilation))
     B, Ho, Wo, _ = offset.shape
     K = kh * kw
-    off = offset.double().reshape(B, Ho, Wo, group, K, 2)
+    pdt = torch.float64 if position_dtype is None else position_dtype
+    off = offset.double().reshape(B, Ho, Wo, group, K, 2).to(pdt)
     c_h, c_w = (dh * (kh - 1)) >> 1, (dw * (kw - 1)) >> 1
-    i = torch.arange(kw, dtype=torch.float64).repeat_interleave(kh)   # tap = i * kh + j
-    j = torch.arange(kh, dtype=torch.float64).repeat(kw)
-    ho = torch.arange(Ho, dtype=torch.float64).view(1, Ho, 1, 1, 1)
-    wo = torch.arange(Wo, dtype=torch.float64).view(1, 1, Wo, 1, 1)
+    i = torch.arange(kw, dtype=pdt).repeat_interleave(kh)   # tap = i * kh + j
+    j = torch.arange(kh, dtype=pdt).repeat(kw)
+    ho = torch.arange(Ho, dtype=pdt).view(1, Ho, 1, 1, 1)
+    wo = torch.arange(Wo, dtype=pdt).view(1, 1, Wo, 1, 1)
     i, j = i.to(off.device), j.to(off.device)
     loc_w = wo.to(off.device) * sw - pw + c_w + (i * dw - c_w + off[..., 0]) * offset_scale
     loc_h = ho.to(off.device) * sh - ph + c_h + (j * dh - c_h + off[..., 1]) * offset_scale
-    return loc_h, loc_w
+    return loc_h.double(), loc_w.double()
 
 
 def min_lattice_distance(offset, H, W, kernel, stride, pad, dilation, group, offset_scale):
@@ -45,15 +49,15 @@ def min_lattice_distance(offset, H, W, kernel, stride, pad, dilation, group, off
     return (d - d.round()).abs().min().item()
 
 
-def dcnv3_ref(input, offset, mask, kernel, stride, pad, dilation, group, group_channels, offset_scale):
-    """fp64 restatement; differentiable.  Returns the result in the dtype of ``input``."""
+def dcnv3_ref(input, offset, mask, kernel, stride, pad, dilation, group, group_channels, offset_scale, position_dtype=None):
+    """fp64 restatement; differentiable.  Returns the result in the dtype of ``input``.  ``position_dtype``: see ``positions``."""
     (kh, kw), (sh, sw), (ph, pw), (dh, dw) = map(_pair, (kernel, stride, pad, dilation))
     B, H, W, C = input.shape
     G, D, K = group, group_channels, kh * kw
     Ho, Wo = out_hw(H, W, kernel, stride, pad, dilation)
     x = F.pad(input.double(), (0, 0, pw, pw, ph, ph))             # [B, H + 2 ph, W + 2 pw, C], zeros around
     Hp, Wp = H + 2 * ph, W + 2 * pw
-    loc_h, loc_w = positions(offset, H, W, kernel, stride, pad, dilation, group, offset_scale)
+    loc_h, loc_w = positions(offset, H, W, kernel, stride, pad, dilation, group, offset_scale, position_dtype)
     # pixel p of the padded image sits at (2 p + 1) / size - 1 (align_corners=False)
     gx = (2 * (loc_w + pw) + 1) / Wp - 1
     gy = (2 * (loc_h + ph) + 1) / Hp - 1
@@ -68,10 +72,10 @@ def dcnv3_ref(input, offset, mask, kernel, stride, pad, dilation, group, group_c
     return torch.cat(outs, -1).to(input.dtype)
 
 
-def dcnv3_ref_grads(input, offset, mask, grad_output, *geo):
+def dcnv3_ref_grads(input, offset, mask, grad_output, *geo, position_dtype=None):
     """(output, grad_input, grad_offset, grad_mask) in fp64 from the values the tensors hold."""
     x, o, m = (t.detach().double().cpu().requires_grad_(True) for t in (input, offset, mask))
-    out = dcnv3_ref(x, o, m, *geo)
+    out = dcnv3_ref(x, o, m, *geo, position_dtype=position_dtype)
     gi, goff, gm = torch.autograd.grad(out, (x, o, m), grad_output.detach().double().cpu())
     return out.detach(), gi, goff, gm
 
