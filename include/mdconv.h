@@ -19,6 +19,19 @@
  *  - `stream` is a hipStream_t (NULL = the null stream).  Calls are asynchronous on it.
  *  - `workspace` is caller-owned device scratch of at least mdconv_workspace_bytes() bytes,
  *    16-byte aligned; it may be NULL when that function returns 0.
+ *  - Pointer alignment.  Every tensor pointer has one of two classes (the audit behind them: DESIGN.md, "Pointer alignment"):
+ *    "element" -- aligned to the tensor's element (2, 4 or 8 bytes), which every dense view of a framework tensor is, at any
+ *    storage offset -- or "16-byte".  The eight entry points of this section take every tensor "element" (offset, mask and
+ *    their gradients: 4 bytes with MDCONV_SAMPLING_F32; grad_weight and grad_bias: 4 bytes with MDCONV_WGRAD_F32), with three
+ *    exceptions, the tensors the kernels move as channels-last vectors: `input` with MDCONV_LAYOUT_CHANNELS_LAST, the forward's
+ *    `output` with MDCONV_FLAG_OUTPUT_CHANNELS_LAST and `grad_input` with MDCONV_FLAG_GRAD_INPUT_CHANNELS_LAST are "16-byte".
+ *    (A channels-last `grad_output` stays "element"; the backward never reads `bias`: that pointer is not looked at.)  The
+ *    sampling operators further down take the sampled tensor, `output`, `grad_output` and the sampled tensor's gradient
+ *    "16-byte" and every coordinate tensor "element"; each states its rule.  A pointer below its class is MDCONV_EINVAL, with
+ *    the argument's name and the alignment in mdconv_last_error(): checked after the NULL checks (MDCONV_ENULL) and before the
+ *    shape rule, the routing refusals (MDCONV_EUNSUPPORTED) and the workspace (MDCONV_EWORKSPACE); nothing is launched.
+ *    Pointers a call ignores (a skipped gradient, `bias` without with_bias, `offset` without with_offset) are not checked.
+ *    Results do not depend on the alignment: DESIGN.md lists, per tensor, which are bit-identical at any address.
  *  - Backward entry points ACCUMULATE into every grad_* buffer, which is what the reference's
  *    caller-allocated entry points do (deformable_conv.cu:327-333; the Python wrapper zero-fills,
  *    modulated_deform_conv.py:53-56).  For the modulated-2D op, whose reference entry point
@@ -385,8 +398,10 @@ int mdconv_modulated_deform_conv3d_backward(const mdconv_desc *d, const void *in
  *    summed with floating-point atomics: output, grad_offset and grad_mask are bit-identical from call to call, grad_input
  *    is with MDCONV_FLAG_DETERMINISTIC and agrees to rounding otherwise.  With MDCONV_FLAG_NO_GRAD_INPUT grad_input may be
  *    NULL and is never touched; the other gradients are bit for bit those of the full call.  Forwards ignore both flags.
- *  - A call checks in this order: the descriptor (MDCONV_EINVAL), the pointers (MDCONV_ENULL), the shape rule
- *    (MDCONV_EUNSUPPORTED), the workspace (MDCONV_EWORKSPACE: size and 16-byte alignment, as above).
+ *  - Pointer alignment ("Pointer alignment" at the top of this header): input, output, grad_output and grad_input are 16-byte aligned; offset, mask and their gradients to their element.
+ *  - A call checks in this order: the descriptor (MDCONV_EINVAL), the pointers -- NULL (MDCONV_ENULL), then alignment
+ *    (MDCONV_EINVAL, naming the argument) --, the shape rule (MDCONV_EUNSUPPORTED), the workspace (MDCONV_EWORKSPACE: size and
+ *    16-byte alignment, as above).
  *  - The workspace figure is exact, 0 for the forward, and honours both flags.  A call is a plain chain of kernels on the
  *    caller's stream: no second stream, no host synchronisation; it captures into a HIP graph. */
 typedef struct mdconv_dcnv3_desc {
@@ -450,8 +465,11 @@ int mdconv_dcnv3_backward(const mdconv_dcnv3_desc *d, const void *input, const v
  *    bit-identical from call to call, grad_value is with MDCONV_FLAG_DETERMINISTIC and agrees to rounding otherwise.  With
  *    MDCONV_FLAG_NO_GRAD_INPUT grad_value may be NULL and is never touched; the other gradients are bit for bit those of the
  *    full call.  Forwards ignore both flags.
- *  - A call checks in this order: the descriptor (MDCONV_EINVAL), the pointers (MDCONV_ENULL), the shape rule
- *    (MDCONV_EUNSUPPORTED), the workspace (MDCONV_EWORKSPACE: size and 16-byte alignment, as above).
+ *  - Pointer alignment ("Pointer alignment" at the top of this header): value, output, grad_output and grad_value are 16-byte aligned; sampling_locations, attention_weights and their gradients to
+ *    their element (coord_dtype).
+ *  - A call checks in this order: the descriptor (MDCONV_EINVAL), the pointers -- NULL (MDCONV_ENULL), then alignment
+ *    (MDCONV_EINVAL, naming the argument) --, the shape rule (MDCONV_EUNSUPPORTED), the workspace (MDCONV_EWORKSPACE: size and
+ *    16-byte alignment, as above).
  *  - The workspace figure is exact, 0 for the forward, and honours both flags.  A call is a plain chain of kernels on the
  *    caller's stream: no second stream, no host synchronisation; it captures into a HIP graph.
  *  Written from memory of the published operator and UNPINNED against its code. */
@@ -519,8 +537,11 @@ int mdconv_msda_backward(const mdconv_msda_desc *d, const void *value, const voi
  *    bit-identical from call to call, grad_value is with MDCONV_FLAG_DETERMINISTIC and agrees to rounding otherwise.  With
  *    MDCONV_FLAG_NO_GRAD_INPUT grad_value may be NULL and is never touched; the other gradients are bit for bit those of the
  *    full call.  Forwards ignore both flags.
- *  - A call checks in this order: the descriptor (MDCONV_EINVAL), the pointers (MDCONV_ENULL), the shape rule
- *    (MDCONV_EUNSUPPORTED), the workspace (MDCONV_EWORKSPACE: size and 16-byte alignment, as above).
+ *  - Pointer alignment ("Pointer alignment" at the top of this header): value, output, grad_output and grad_value are 16-byte aligned; sampling_locations, attention_weights and their gradients to
+ *    their element (coord_dtype).
+ *  - A call checks in this order: the descriptor (MDCONV_EINVAL), the pointers -- NULL (MDCONV_ENULL), then alignment
+ *    (MDCONV_EINVAL, naming the argument) --, the shape rule (MDCONV_EUNSUPPORTED), the workspace (MDCONV_EWORKSPACE: size and
+ *    16-byte alignment, as above).
  *  - The workspace figure is exact, 0 for the forward, and honours both flags.  A call is a plain chain of kernels on the
  *    caller's stream: no second stream, no host synchronisation; it captures into a HIP graph.
  *  No published operator is the model: the published MSDeformAttn kernel is 2-D only, so fidelity to any published operator
@@ -604,8 +625,10 @@ int mdconv_msda3d_backward(const mdconv_msda3d_desc *d, const void *value, const
  *    pairs' softmax statistics, behind the lists); with MDCONV_FLAG_NO_GRAD_INPUT it is 0 and nothing is stored; the
  *    forward's is 0.  The compile-time `softmax` switch of the published kernels is what this flag is modelled on, from
  *    memory and UNPINNED like the rest.
- *  - A call checks in this order: the descriptor (MDCONV_EINVAL), the pointers (MDCONV_ENULL), the shape rule
- *    (MDCONV_EUNSUPPORTED), the workspace (MDCONV_EWORKSPACE: size and 16-byte alignment, as above).
+ *  - Pointer alignment ("Pointer alignment" at the top of this header): input, output, grad_output and grad_input are 16-byte aligned; offset_mask and its gradient to their element (coord_dtype).
+ *  - A call checks in this order: the descriptor (MDCONV_EINVAL), the pointers -- NULL (MDCONV_ENULL), then alignment
+ *    (MDCONV_EINVAL, naming the argument) --, the shape rule (MDCONV_EUNSUPPORTED), the workspace (MDCONV_EWORKSPACE: size and
+ *    16-byte alignment, as above).
  *  - The workspace figure is exact, 0 for the forward, honours the flags and does not depend on coord_dtype.  A call is a
  *    plain chain of kernels on the caller's stream: no second stream, no host synchronisation; it captures into a HIP graph.
  *  Written from memory of the published operator and UNPINNED against its code. */
@@ -675,8 +698,11 @@ int mdconv_dcnv4_backward(const mdconv_dcnv4_desc *d, const void *input, const v
  *    from call to call, grad_value is with MDCONV_FLAG_DETERMINISTIC and agrees to rounding otherwise.  With
  *    MDCONV_FLAG_NO_GRAD_INPUT grad_value may be NULL and is never touched; grad_sampling_loc_attn is bit for bit that of the
  *    full call.  Forwards ignore both flags.
- *  - A call checks in this order: the descriptor (MDCONV_EINVAL), the pointers (MDCONV_ENULL), the shape rule
- *    (MDCONV_EUNSUPPORTED), the workspace (MDCONV_EWORKSPACE: size and 16-byte alignment, as above).
+ *  - Pointer alignment ("Pointer alignment" at the top of this header): value, output, grad_output and grad_value are 16-byte aligned; sampling_loc_attn and its gradient to their element
+ *    (coord_dtype).
+ *  - A call checks in this order: the descriptor (MDCONV_EINVAL), the pointers -- NULL (MDCONV_ENULL), then alignment
+ *    (MDCONV_EINVAL, naming the argument) --, the shape rule (MDCONV_EUNSUPPORTED), the workspace (MDCONV_EWORKSPACE: size and
+ *    16-byte alignment, as above).
  *  - The workspace figure is exact, 0 for the forward, and honours both flags: a backward with grad_value takes the scatter
  *    lists of multi-scale deformable attention for the same shape plus 8 bytes per (query, head).  A call is a plain chain of
  *    kernels on the caller's stream: no second stream, no host synchronisation; it captures into a HIP graph.
@@ -752,8 +778,11 @@ int mdconv_fda_backward(const mdconv_fda_desc *d, const void *value, const void 
  *    result is summed with floating-point atomics: output and grad_offset are bit-identical from call to call, grad_input is
  *    with MDCONV_FLAG_DETERMINISTIC and agrees to rounding otherwise.  With MDCONV_FLAG_NO_GRAD_INPUT grad_input may be NULL
  *    and is never touched, the workspace is 0, and grad_offset is bit for bit the full call's.  Forwards ignore both flags.
- *  - A call checks in this order: the descriptor (MDCONV_EINVAL), the pointers (MDCONV_ENULL), the shape rule
- *    (MDCONV_EUNSUPPORTED), the workspace (MDCONV_EWORKSPACE: size and 16-byte alignment, as above).
+ *  - Pointer alignment ("Pointer alignment" at the top of this header): input, output, grad_output and grad_input are 16-byte aligned; rois to 4 bytes, offset and grad_offset to their element
+ *    (coord_dtype).
+ *  - A call checks in this order: the descriptor (MDCONV_EINVAL), the pointers -- NULL (MDCONV_ENULL), then alignment
+ *    (MDCONV_EINVAL, naming the argument) --, the shape rule (MDCONV_EUNSUPPORTED), the workspace (MDCONV_EWORKSPACE: size and
+ *    16-byte alignment, as above).
  *  - The workspace figure is exact, 0 for the forward, independent of coord_dtype, and honours both flags.  A call is a plain
  *    chain of kernels on the caller's stream: no second stream, no host synchronisation; it captures into a HIP graph.
  *  Written from memory of the published operator and UNPINNED against its code; where the published kernels

@@ -94,6 +94,8 @@ def _backward_layouts(d, input, grad_output, grad_input):
     if _cl_result(grad_input) and not got & _capi.FLAG_GRAD_INPUT_CHANNELS_LAST:
         final = grad_input
         grad_input = grad_input.contiguous() if d.accumulate else torch.empty_like(grad_input, memory_format=torch.contiguous_format)
+    if got & _capi.FLAG_GRAD_INPUT_CHANNELS_LAST:
+        _capi.require_aligned_result("MDCONV_CUDA", "grad_input", grad_input)   # stored as vectors: pointer class "16-byte"
     return grad_output, grad_input, final
 
 
@@ -167,8 +169,10 @@ def _layout(d, input, backward):
     layout (include/mdconv.h: mdconv_input_layout_supported -- the native 16-bit backward covers
     fewer shapes than the forward, and MDCONV_PATH / MDCONV_HP can switch those kernels off);
     otherwise the call runs on a contiguous copy, like any other PyTorch operator would."""
-    if input.is_contiguous() or _capi.lib().mdconv_input_layout_supported(ctypes.byref(d), 1, int(backward)):
-        return input
+    if input.is_contiguous():
+        return input   # (pointer class "element", include/mdconv.h: a view at any storage offset goes as it is)
+    if _capi.lib().mdconv_input_layout_supported(ctypes.byref(d), 1, int(backward)):
+        return _capi.aligned_input(input)   # the kernels gather 16-byte vectors from it: pointer class "16-byte", copied if below
     return input.contiguous()
 
 
@@ -312,8 +316,11 @@ def _forward(nd, modulated, fn_name, input, weight, bias, offset, mask, output, 
                                                         deformable_group, in_step, with_bias, False):
             fmt = torch.channels_last if nd == 2 else torch.channels_last_3d
         output = torch.empty((d.batch, d.c_out) + osz, dtype=input.dtype, device=input.device, memory_format=fmt)
-    if _cl_result(output) and not _result_flags(d, input, False, output):
-        final, output = output, torch.empty_like(output, memory_format=torch.contiguous_format)   # (the fallback: copied below)
+    if _cl_result(output):
+        if _result_flags(d, input, False, output):
+            _capi.require_aligned_result("MDCONV_CUDA", "output", output)   # stored as vectors: pointer class "16-byte"
+        else:
+            final, output = output, torch.empty_like(output, memory_format=torch.contiguous_format)   # (the fallback: copied below)
     args = [_ptr(input), _ptr(weight), _ptr(bias), _ptr(offset)]
     if modulated:
         args.append(_ptr(mask))

@@ -211,6 +211,28 @@ def last_error():
     return lib().mdconv_last_error().decode("utf-8", "replace")
 
 
+VECTOR_ALIGN = 16   # bytes: the "16-byte" pointer class of include/mdconv.h ("Pointer alignment")
+
+
+def aligned_input(t):
+    """A read-only tensor of the "16-byte" pointer class as the library takes it: `t` itself when its address is a multiple
+    of 16, else a fresh copy (the allocator's alignment) -- a dense view at an odd storage offset (a slice of a flat
+    parameter buffer, a piece of torch.split) is aligned to its element only.  "element"-class tensors need nothing: a
+    tensor's address is always a multiple of its element size."""
+    if t is None or t.numel() == 0 or t.data_ptr() % VECTOR_ALIGN == 0:
+        return t
+    import torch
+    return t.clone(memory_format=torch.preserve_format)
+
+
+def require_aligned_result(op, name, t):
+    """A caller-supplied result buffer of the "16-byte" pointer class must be 16-byte aligned: the library writes into the
+    caller's tensor, never into a silent temporary."""
+    if t is not None and t.numel() > 0 and t.data_ptr() % VECTOR_ALIGN:
+        raise ValueError("%s: %s must be %d-byte aligned (its address is %d mod %d: a view at a storage offset?); pass an "
+                         "aligned buffer and copy" % (op, name, VECTOR_ALIGN, t.data_ptr() % VECTOR_ALIGN, VECTOR_ALIGN))
+
+
 def set_path(path):
     """Force the kernel path: 'auto' | 'direct' | 'mfma' | 'depthwise'.  Returns the previous setting."""
     names = {"auto": PATH_AUTO, "direct": PATH_DIRECT, "mfma": PATH_MFMA, "depthwise": PATH_DEPTHWISE}

@@ -78,7 +78,8 @@ __global__ __launch_bounds__(64 * WAVES, (WAVES >= 8 || NKS >= 16 || ND == 3) ? 
   tap_coords<ND>(g, tap, tcd);
 
   // ---- grad_out tile loader: item = (o, pixel octet) ----
-  const bool vec_ok = (g.S_o & 7) == 0;
+  // (16-byte loads need 16-byte rows AND a 16-byte aligned tensor: grad_output is an element-aligned argument)
+  const bool vec_ok = (g.S_o & 7) == 0 && (reinterpret_cast<uintptr_t>(gout) & 15) == 0;
   auto load_item = [&](int item, int n0) -> U4 {
     const int o = item >> 2, oct = item & 3;
     const int nn = n0 + oct * 8;

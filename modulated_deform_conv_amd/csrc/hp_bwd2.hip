@@ -277,7 +277,9 @@ __global__ __launch_bounds__(64 * (WAVES + NS), WAVES >= 8 ? 1 : 2) void hp_bwd2
 
   // ---- grad_out tile: item = (o, pixel octet); two items per thread in flight, tail loop.
   // (gb, gp) = image / pixel of the first pixel of the NEXT tile to load (wave-uniform) ----
-  const bool vec_ok = (g.S_o & 7) == 0, tile_ok = (g.S_o & 31) == 0;
+  // (16-byte loads need 16-byte rows AND a 16-byte aligned tensor: grad_output is an element-aligned argument)
+  const bool gout_al = (reinterpret_cast<uintptr_t>(gout) & 15) == 0;
+  const bool vec_ok = (g.S_o & 7) == 0 && gout_al, tile_ok = (g.S_o & 31) == 0;
   int gb = b_first, gp = p_first;
   auto load_item = [&](int item) -> U4 {
     const int o = item >> 2, oct = item & 3;
@@ -286,7 +288,7 @@ __global__ __launch_bounds__(64 * (WAVES + NS), WAVES >= 8 ? 1 : 2) void hp_bwd2
     U4 v = {0, 0, 0, 0};
     // 32 | S_o: a tile never straddles two images -- row offset per thread, tile offset scalar, and
     // images beyond the batch fall out of the buffer's range (no 64-bit address arithmetic per tile)
-    if (tile_ok) return buf_load4u(r_gout, o < g.O ? (o * g.S_o + oct * 8) * 2 : kHpOob, (gb * g.O * g.S_o + gp) * 2);
+    if (tile_ok && gout_al) return buf_load4u(r_gout, o < g.O ? (o * g.S_o + oct * 8) * 2 : kHpOob, (gb * g.O * g.S_o + gp) * 2);
     if (o < g.O && bb < g.B) {
       if (vec_ok) {
         v = *reinterpret_cast<const U4 *>(gout + ((int64_t)bb * g.O + o) * g.S_o + pp);

@@ -133,7 +133,8 @@ __global__ __launch_bounds__(256, 2) void hp_bwd3_kernel(
   // ---- grad_out of the wave's 32 pixels -> B fragments (K = o, N = pixel), kB3ChunkRows rows at a time ----
   U4 gB[NKS];
   {
-    const bool vec_ok = (g.S_o & 7) == 0;
+    // (16-byte loads need 16-byte rows AND a 16-byte aligned tensor: grad_output is an element-aligned argument)
+    const bool vec_ok = (g.S_o & 7) == 0 && (reinterpret_cast<uintptr_t>(gout) & 15) == 0;
     Raw *tl = Gc;   // [kB3ChunkRows][kPP]
 #pragma unroll
     for (int c0 = 0; c0 < NKS * 16; c0 += kB3ChunkRows) {

@@ -61,7 +61,9 @@ __global__ __launch_bounds__(64 * WAVES, MB2 <= 4 ? 3 : 1) void hp_gemm2_kernel(
     // tile_ok (32 | S_o): a tile never straddles two images, so a thread's items have CONSTANT offsets from
     // a per-tile scalar base -- buffer loads with the base in the scalar offset, no per-item address
     // arithmetic (the generic loaders below cost ~100 VALU per item against 8 MFMAs per tile and wave)
-    const bool vec_ok = (g.S_o & 7) == 0, tile_ok = (g.S_o & 31) == 0;
+    // (16-byte loads need 16-byte rows AND a 16-byte aligned tensor: grad_output is an element-aligned argument)
+    const bool gout_al = (reinterpret_cast<uintptr_t>(gout) & 15) == 0;
+    const bool vec_ok = (g.S_o & 7) == 0 && gout_al, tile_ok = (g.S_o & 31) == 0;
     const rsrc_t r_go = make_rsrc(gout, (size_t)g.B * g.O * g.S_o * 2);
     const size_t col_img = (size_t)g.K * g.S_o * Cp;
     const int LPP = Cp / 8;
@@ -70,7 +72,7 @@ __global__ __launch_bounds__(64 * WAVES, MB2 <= 4 ? 3 : 1) void hp_gemm2_kernel(
     int lb = (t_lo * 32) / g.S_o, lp = t_lo * 32 - lb * g.S_o;
     auto load_g = [&](int item, int lb, int lp) -> U4 {
       const int o = item >> 2, oct = item & 3;
-      if (tile_ok)   // the scalar offset is NOT part of the range check: images beyond the batch are parked in the
+      if (tile_ok && gout_al)   // the scalar offset is NOT part of the range check: images beyond the batch are parked in the
                      // lane offset like padded channels (they cannot occur while tile_ok implies lb < B; kept explicit)
         return buf_load4u(r_go, o < g.O && lb < g.B ? (o * g.S_o + oct * 8) * 2 : kHpOob,
                           (min(lb, g.B - 1) * g.O * g.S_o + lp) * 2);

@@ -261,6 +261,20 @@ static int require(const void *p, const char *name) {
   return MDCONV_OK;
 }
 
+// Pointer alignment ("Pointer alignment"; include/mdconv.h states the class of every argument): a tensor pointer is
+// aligned to its class -- `align` = the tensor's element size ("element": every access through it is one element wide, a raw
+// buffer load at an element-aligned offset, or behind a pointer test with an element-wise fallback) or 16 ("16-byte": the
+// kernels move 16-byte vectors through it).  Checked after the NULL checks and before the shape rule and the workspace; a
+// pointer the call ignores (NULL where that is allowed, a skipped gradient, bias without with_bias) is not looked at.
+static int require_aligned(const void *p, const char *name, size_t align) {
+  if (p && ((uintptr_t)p & (align - 1)) != 0) {
+    set_error("%s pointer must be %zu-byte aligned", name, align);
+    return MDCONV_EINVAL;
+  }
+  return MDCONV_OK;
+}
+static size_t dtype_bytes(int dt) { return dt == MDCONV_F64 ? 8 : (dt == MDCONV_F32 ? 4 : 2); }
+
 // element type of the call's tensors (the dtype flags stripped), whether offset / mask are fp32, and whether a backward's
 // grad_weight / grad_bias are (the forward ignores that bit: one descriptor serves both directions)
 static int base_dtype(const mdconv_desc *d) { return d->dtype & ~(MDCONV_SAMPLING_F32 | MDCONV_WGRAD_F32); }
@@ -497,6 +511,14 @@ static int run_forward(const mdconv_desc *d, int nd, int modulated, Tensors t, v
   const int dt = base_dtype(d), s32 = sampling_f32(d);
   t.samp32 = s32;
   g.in_cl = md.input_layout == MDCONV_LAYOUT_CHANNELS_LAST ? 1 : 0;
+  {   // pointer alignment: "element", but 16 bytes for the tensors the kernels move as channels-last vectors
+    const size_t es = dtype_bytes(dt), es_s = s32 ? 4 : es;
+    if ((rc = require_aligned(t.input, "input", g.in_cl ? 16 : es)) || (rc = require_aligned(t.weight, "weight", es)) ||
+        (rc = require_aligned(t.offset, "offset", es_s)) || (rc = require_aligned(t.output, "output", md.out_cl ? 16 : es)))
+      return rc;
+    if (modulated && (rc = require_aligned(t.mask, "mask", es_s))) return rc;
+    if (g.with_bias && (rc = require_aligned(t.bias, "bias", es))) return rc;
+  }
   CallPlan cp;
   plan_call(g, dt, s32, 0, path, false, &cp, Skip(), md.math_bf16, md.out_cl != 0, false);
   if (cp.refused) return refuse(cp, g, dt, path, false);
@@ -566,6 +588,17 @@ static int run_backward(const mdconv_desc *d, int nd, int modulated, Tensors t, 
   t.wgrad32 = wgrad_f32(d, true);
   g.in_cl = md.input_layout == MDCONV_LAYOUT_CHANNELS_LAST ? 1 : 0;
   g.det = md.deterministic;
+  {   // pointer alignment: "element", but 16 bytes for the tensors the kernels move as channels-last vectors
+    const size_t es = dtype_bytes(dt), es_s = s32 ? 4 : es, es_w = t.wgrad32 ? 4 : es;
+    if ((rc = require_aligned(t.input, "input", g.in_cl ? 16 : es)) || (rc = require_aligned(t.weight, "weight", es)) ||
+        (rc = require_aligned(t.offset, "offset", es_s)) || (rc = require_aligned(t.grad_output, "grad_output", es)) ||
+        (rc = require_aligned(t.grad_input, "grad_input", md.gi_cl ? 16 : es)) ||
+        (rc = require_aligned(t.grad_weight, "grad_weight", es_w)) || (rc = require_aligned(t.grad_offset, "grad_offset", es_s)))
+      return rc;
+    if (modulated && ((rc = require_aligned(t.mask, "mask", es_s)) || (rc = require_aligned(t.grad_mask, "grad_mask", es_s))))
+      return rc;
+    if (g.with_bias && !skip.weight && (rc = require_aligned(t.grad_bias, "grad_bias", es_w))) return rc;
+  }
   CallPlan cp;
   plan_call(g, dt, s32, t.wgrad32, path, true, &cp, skip, md.math_bf16, md.out_cl != 0, md.gi_cl != 0);
   if (cp.refused) return refuse(cp, g, dt, path, true);
@@ -1148,6 +1181,9 @@ int mdconv_dcnv3_forward(const mdconv_dcnv3_desc *d, const void *input, const vo
   if ((rc = require(input, "input")) || (rc = require(offset, "offset")) || (rc = require(mask, "mask")) ||
       (rc = require(output, "output")))
     return rc;
+  if ((rc = require_aligned(input, "input", 16)) || (rc = require_aligned(offset, "offset", dtype_bytes(d->dtype))) ||
+      (rc = require_aligned(mask, "mask", dtype_bytes(d->dtype))) || (rc = require_aligned(output, "output", 16)))
+    return rc;
   Dcn3Plan p;
   const char *why;
   if (!dcn3_plan(d, false, &p, &why)) return dcn3_refuse(why);
@@ -1168,6 +1204,12 @@ int mdconv_dcnv3_backward(const mdconv_dcnv3_desc *d, const void *input, const v
       (rc = require(grad_mask, "grad_mask")))
     return rc;
   if (!(d->flags & MDCONV_FLAG_NO_GRAD_INPUT) && (rc = require(grad_input, "grad_input"))) return rc;
+  if ((rc = require_aligned(input, "input", 16)) || (rc = require_aligned(offset, "offset", dtype_bytes(d->dtype))) ||
+      (rc = require_aligned(mask, "mask", dtype_bytes(d->dtype))) || (rc = require_aligned(grad_output, "grad_output", 16)) ||
+      (rc = require_aligned(grad_offset, "grad_offset", dtype_bytes(d->dtype))) ||
+      (rc = require_aligned(grad_mask, "grad_mask", dtype_bytes(d->dtype))))
+    return rc;
+  if (!(d->flags & MDCONV_FLAG_NO_GRAD_INPUT) && (rc = require_aligned(grad_input, "grad_input", 16))) return rc;
   Dcn3Plan p;
   const char *why;
   if (!dcn3_plan(d, true, &p, &why)) return dcn3_refuse(why);
@@ -1213,6 +1255,9 @@ int mdconv_dcnv4_forward(const mdconv_dcnv4_desc *d, const void *input, const vo
   if (rc) return rc;
   if ((rc = require(input, "input")) || (rc = require(offset_mask, "offset_mask")) || (rc = require(output, "output")))
     return rc;
+  if ((rc = require_aligned(input, "input", 16)) || (rc = require_aligned(offset_mask, "offset_mask", dtype_bytes(d->coord_dtype))) ||
+      (rc = require_aligned(output, "output", 16)))
+    return rc;
   Dcn4Plan p;
   const char *why;
   if (!dcn4_plan(d, false, &p, &why)) return dcn4_refuse(why);
@@ -1231,6 +1276,11 @@ int mdconv_dcnv4_backward(const mdconv_dcnv4_desc *d, const void *input, const v
       (rc = require(grad_output, "grad_output")) || (rc = require(grad_offset_mask, "grad_offset_mask")))
     return rc;
   if (!(d->flags & MDCONV_FLAG_NO_GRAD_INPUT) && (rc = require(grad_input, "grad_input"))) return rc;
+  if ((rc = require_aligned(input, "input", 16)) || (rc = require_aligned(offset_mask, "offset_mask", dtype_bytes(d->coord_dtype))) ||
+      (rc = require_aligned(grad_output, "grad_output", 16)) ||
+      (rc = require_aligned(grad_offset_mask, "grad_offset_mask", dtype_bytes(d->coord_dtype))))
+    return rc;
+  if (!(d->flags & MDCONV_FLAG_NO_GRAD_INPUT) && (rc = require_aligned(grad_input, "grad_input", 16))) return rc;
   Dcn4Plan p;
   const char *why;
   if (!dcn4_plan(d, true, &p, &why)) return dcn4_refuse(why);
@@ -1273,6 +1323,11 @@ int mdconv_msda_forward(const mdconv_msda_desc *d, const void *value, const void
   if ((rc = require(value, "value")) || (rc = require(sampling_locations, "sampling_locations")) ||
       (rc = require(attention_weights, "attention_weights")) || (rc = require(output, "output")))
     return rc;
+  if ((rc = require_aligned(value, "value", 16)) ||
+      (rc = require_aligned(sampling_locations, "sampling_locations", dtype_bytes(d->coord_dtype))) ||
+      (rc = require_aligned(attention_weights, "attention_weights", dtype_bytes(d->coord_dtype))) ||
+      (rc = require_aligned(output, "output", 16)))
+    return rc;
   MsdaPlan p;
   const char *why;
   if (!msda_plan(d, false, &p, &why)) return msda_refuse(why);
@@ -1295,6 +1350,14 @@ int mdconv_msda_backward(const mdconv_msda_desc *d, const void *value, const voi
       (rc = require(grad_attention_weights, "grad_attention_weights")))
     return rc;
   if (!(d->flags & MDCONV_FLAG_NO_GRAD_INPUT) && (rc = require(grad_value, "grad_value"))) return rc;
+  if ((rc = require_aligned(value, "value", 16)) ||
+      (rc = require_aligned(sampling_locations, "sampling_locations", dtype_bytes(d->coord_dtype))) ||
+      (rc = require_aligned(attention_weights, "attention_weights", dtype_bytes(d->coord_dtype))) ||
+      (rc = require_aligned(grad_output, "grad_output", 16)) ||
+      (rc = require_aligned(grad_sampling_locations, "grad_sampling_locations", dtype_bytes(d->coord_dtype))) ||
+      (rc = require_aligned(grad_attention_weights, "grad_attention_weights", dtype_bytes(d->coord_dtype))))
+    return rc;
+  if (!(d->flags & MDCONV_FLAG_NO_GRAD_INPUT) && (rc = require_aligned(grad_value, "grad_value", 16))) return rc;
   MsdaPlan p;
   const char *why;
   if (!msda_plan(d, true, &p, &why)) return msda_refuse(why);
@@ -1342,6 +1405,11 @@ int mdconv_msda3d_forward(const mdconv_msda3d_desc *d, const void *value, const 
   if ((rc = require(value, "value")) || (rc = require(sampling_locations, "sampling_locations")) ||
       (rc = require(attention_weights, "attention_weights")) || (rc = require(output, "output")))
     return rc;
+  if ((rc = require_aligned(value, "value", 16)) ||
+      (rc = require_aligned(sampling_locations, "sampling_locations", dtype_bytes(d->coord_dtype))) ||
+      (rc = require_aligned(attention_weights, "attention_weights", dtype_bytes(d->coord_dtype))) ||
+      (rc = require_aligned(output, "output", 16)))
+    return rc;
   Msda3Plan p;
   const char *why;
   if (!msda3_plan(d, false, &p, &why)) return msda3d_refuse(why);
@@ -1364,6 +1432,14 @@ int mdconv_msda3d_backward(const mdconv_msda3d_desc *d, const void *value, const
       (rc = require(grad_attention_weights, "grad_attention_weights")))
     return rc;
   if (!(d->flags & MDCONV_FLAG_NO_GRAD_INPUT) && (rc = require(grad_value, "grad_value"))) return rc;
+  if ((rc = require_aligned(value, "value", 16)) ||
+      (rc = require_aligned(sampling_locations, "sampling_locations", dtype_bytes(d->coord_dtype))) ||
+      (rc = require_aligned(attention_weights, "attention_weights", dtype_bytes(d->coord_dtype))) ||
+      (rc = require_aligned(grad_output, "grad_output", 16)) ||
+      (rc = require_aligned(grad_sampling_locations, "grad_sampling_locations", dtype_bytes(d->coord_dtype))) ||
+      (rc = require_aligned(grad_attention_weights, "grad_attention_weights", dtype_bytes(d->coord_dtype))))
+    return rc;
+  if (!(d->flags & MDCONV_FLAG_NO_GRAD_INPUT) && (rc = require_aligned(grad_value, "grad_value", 16))) return rc;
   Msda3Plan p;
   const char *why;
   if (!msda3_plan(d, true, &p, &why)) return msda3d_refuse(why);
@@ -1416,6 +1492,10 @@ int mdconv_fda_forward(const mdconv_fda_desc *d, const void *value, const void *
   if (rc) return rc;
   if ((rc = require(value, "value")) || (rc = require(sampling_loc_attn, "sampling_loc_attn")) || (rc = require(output, "output")))
     return rc;
+  if ((rc = require_aligned(value, "value", 16)) ||
+      (rc = require_aligned(sampling_loc_attn, "sampling_loc_attn", dtype_bytes(d->coord_dtype))) ||
+      (rc = require_aligned(output, "output", 16)))
+    return rc;
   FdaPlan p;
   const char *why;
   if (!fda_plan(d, false, &p, &why)) return fda_refuse(why);
@@ -1434,6 +1514,12 @@ int mdconv_fda_backward(const mdconv_fda_desc *d, const void *value, const void 
       (rc = require(grad_output, "grad_output")) || (rc = require(grad_sampling_loc_attn, "grad_sampling_loc_attn")))
     return rc;
   if (!(d->flags & MDCONV_FLAG_NO_GRAD_INPUT) && (rc = require(grad_value, "grad_value"))) return rc;
+  if ((rc = require_aligned(value, "value", 16)) ||
+      (rc = require_aligned(sampling_loc_attn, "sampling_loc_attn", dtype_bytes(d->coord_dtype))) ||
+      (rc = require_aligned(grad_output, "grad_output", 16)) ||
+      (rc = require_aligned(grad_sampling_loc_attn, "grad_sampling_loc_attn", dtype_bytes(d->coord_dtype))))
+    return rc;
+  if (!(d->flags & MDCONV_FLAG_NO_GRAD_INPUT) && (rc = require_aligned(grad_value, "grad_value", 16))) return rc;
   FdaPlan p;
   const char *why;
   if (!fda_plan(d, true, &p, &why)) return fda_refuse(why);
@@ -1463,6 +1549,10 @@ int mdconv_droi_forward(const mdconv_droi_desc *d, const void *input, const void
   if (rc) return rc;
   if ((rc = require(input, "input")) || (rc = require(rois, "rois")) || (rc = require(output, "output"))) return rc;
   if (d->with_offset && (rc = require(offset, "offset"))) return rc;
+  if ((rc = require_aligned(input, "input", 16)) || (rc = require_aligned(rois, "rois", 4)) ||
+      (rc = require_aligned(output, "output", 16)))
+    return rc;
+  if (d->with_offset && (rc = require_aligned(offset, "offset", dtype_bytes(d->coord_dtype)))) return rc;
   DroiPlan p;
   const char *why;
   if (!droi_plan(d, false, &p, &why)) return droi_refuse(why);
@@ -1481,6 +1571,13 @@ int mdconv_droi_backward(const mdconv_droi_desc *d, const void *input, const voi
   if ((rc = require(input, "input")) || (rc = require(rois, "rois")) || (rc = require(grad_output, "grad_output"))) return rc;
   if (d->with_offset && ((rc = require(offset, "offset")) || (rc = require(grad_offset, "grad_offset")))) return rc;
   if (!(d->flags & MDCONV_FLAG_NO_GRAD_INPUT) && (rc = require(grad_input, "grad_input"))) return rc;
+  if ((rc = require_aligned(input, "input", 16)) || (rc = require_aligned(rois, "rois", 4)) ||
+      (rc = require_aligned(grad_output, "grad_output", 16)))
+    return rc;
+  if (d->with_offset && ((rc = require_aligned(offset, "offset", dtype_bytes(d->coord_dtype))) ||
+                         (rc = require_aligned(grad_offset, "grad_offset", dtype_bytes(d->coord_dtype)))))
+    return rc;
+  if (!(d->flags & MDCONV_FLAG_NO_GRAD_INPUT) && (rc = require_aligned(grad_input, "grad_input", 16))) return rc;
   DroiPlan p;
   const char *why;
   if (!droi_plan(d, true, &p, &why)) return droi_refuse(why);

@@ -91,6 +91,9 @@ def dcnv3_forward(input, offset, mask, kernel, stride, pad, dilation, group, gro
     d = _desc(input, kernel, stride, pad, dilation, group, group_channels, offset_scale)
     others = {} if output is None else dict(output=output)
     shape = _check(d, input, offset, mask, **others)
+    # pointer classes (include/mdconv.h): input and output are "16-byte", offset and mask "element"
+    _capi.require_aligned_result("dcnv3", "output", output)
+    input = _capi.aligned_input(input)
     if output is None:
         output = torch.empty(shape, dtype=input.dtype, device=input.device)
     _run("mdconv_dcnv3_forward", d, False, [_ptr(input), _ptr(offset), _ptr(mask), _ptr(output)], input)
@@ -111,6 +114,10 @@ def dcnv3_backward(input, offset, mask, grad_output, kernel, stride, pad, dilati
     d = _desc(input, kernel, stride, pad, dilation, group, group_channels, offset_scale,
               accumulate=int(grads is not None if accumulate is None else bool(accumulate)), flags=flags)
     _check(d, input, offset, mask, grad_output=grad_output)
+    # pointer classes (include/mdconv.h): input, grad_output and grad_input are "16-byte", the coordinate tensors "element"
+    if grads is not None and need_grad_input:
+        _capi.require_aligned_result("dcnv3", "grad_input", grads[0])
+    input, grad_output = _capi.aligned_input(input), _capi.aligned_input(grad_output)
     if grads is None:
         grads = (torch.empty_like(input) if need_grad_input else None, torch.empty_like(offset), torch.empty_like(mask))
     gi, goff, gm = grads

@@ -108,6 +108,9 @@ def dcnv4_forward(input, offset_mask, kernel, stride, pad, dilation, group, grou
               flags=_capi.FLAG_SOFTMAX if softmax else 0)
     others = {} if output is None else dict(output=output)
     shape = _check(d, input, offset_mask, **others)
+    # pointer classes (include/mdconv.h): input and output are "16-byte", offset_mask "element"
+    _capi.require_aligned_result("dcnv4", "output", output)
+    input = _capi.aligned_input(input)
     if output is None:
         output = torch.empty(shape, dtype=input.dtype, device=input.device)
     _run("mdconv_dcnv4_forward", d, False, [_ptr(input), _ptr(offset_mask), _ptr(output)], input)
@@ -131,6 +134,10 @@ def dcnv4_backward(input, offset_mask, grad_output, kernel, stride, pad, dilatio
     d = _desc(input, offset_mask, kernel, stride, pad, dilation, group, group_channels, offset_scale, remove_center,
               accumulate=int(grads is not None if accumulate is None else bool(accumulate)), flags=flags)
     _check(d, input, offset_mask, grad_output=grad_output)
+    # pointer classes (include/mdconv.h): input, grad_output and grad_input are "16-byte", offset_mask and its gradient "element"
+    if grads is not None and need_grad_input:
+        _capi.require_aligned_result("dcnv4", "grad_input", grads[0])
+    input, grad_output = _capi.aligned_input(input), _capi.aligned_input(grad_output)
     if grads is None:
         grads = (torch.empty_like(input) if need_grad_input else None, torch.empty_like(offset_mask))
     gi, gom = grads

@@ -98,6 +98,9 @@ def deform_roi_pool_forward(input, rois, offset, output_size, spatial_scale=1.0,
     d = _desc(input, rois, offset, output_size, spatial_scale, sampling_ratio, gamma, max_grid)
     others = {} if output is None else dict(output=output)
     shape = _check(d, input, rois, offset, **others)
+    # pointer classes (include/mdconv.h): input and output are "16-byte", rois and offset "element"
+    _capi.require_aligned_result("droi", "output", output)
+    input = _capi.aligned_input(input)
     if output is None:
         output = torch.empty(shape, dtype=input.dtype, device=input.device)
     _run("mdconv_droi_forward", d, False, [_ptr(input), _ptr(rois), _ptr(offset), _ptr(output)], input)
@@ -118,6 +121,10 @@ def deform_roi_pool_backward(input, rois, offset, grad_output, output_size, spat
     d = _desc(input, rois, offset, output_size, spatial_scale, sampling_ratio, gamma, max_grid,
               accumulate=int(grads is not None if accumulate is None else bool(accumulate)), flags=flags)
     _check(d, input, rois, offset, grad_output=grad_output)
+    # pointer classes (include/mdconv.h): input, grad_output and grad_input are "16-byte", rois, offset and grad_offset "element"
+    if grads is not None and need_grad_input:
+        _capi.require_aligned_result("droi", "grad_input", grads[0])
+    input, grad_output = _capi.aligned_input(input), _capi.aligned_input(grad_output)
     if grads is None:
         grads = (torch.empty_like(input) if need_grad_input else None, None if offset is None else torch.empty_like(offset))
     gi, go = grads

@@ -107,6 +107,9 @@ def flash_deform_attn_forward(value, spatial_shapes, sampling_loc_attn, points, 
     d = _desc(value, sampling_loc_attn, shapes, points)
     others = {} if output is None else dict(output=output)
     shape = _check(d, shapes, value, sampling_loc_attn, **others)
+    # pointer classes (include/mdconv.h): value and output are "16-byte", sampling_loc_attn "element"
+    _capi.require_aligned_result("fda", "output", output)
+    value = _capi.aligned_input(value)
     if output is None:
         output = torch.empty(shape, dtype=value.dtype, device=value.device)
     _run("mdconv_fda_forward", d, False, [_ptr(value), _ptr(sampling_loc_attn), _ptr(output)], value)
@@ -127,6 +130,10 @@ def flash_deform_attn_backward(value, spatial_shapes, sampling_loc_attn, points,
     flags = (_capi.FLAG_DETERMINISTIC if det else 0) | (0 if need_grad_value else _capi.FLAG_NO_GRAD_INPUT)
     d = _desc(value, sampling_loc_attn, shapes, points, accumulate=int(grads is not None and bool(accumulate)), flags=flags)
     _check(d, shapes, value, sampling_loc_attn, grad_output=grad_output)
+    # pointer classes (include/mdconv.h): value, grad_output and grad_value are "16-byte", sampling_loc_attn and its gradient "element"
+    if grads is not None and need_grad_value:
+        _capi.require_aligned_result("fda", "grad_value", grads[0])
+    value, grad_output = _capi.aligned_input(value), _capi.aligned_input(grad_output)
     if grads is None:
         grads = (torch.empty_like(value) if need_grad_value else None, torch.empty_like(sampling_loc_attn))
     gv, gla = grads

@@ -116,6 +116,9 @@ def ms_deform_attn_3d_forward(value, spatial_shapes, sampling_locations, attenti
     d = _desc(value, sampling_locations, shapes)
     others = {} if output is None else dict(output=output)
     shape = _check(d, shapes, value, sampling_locations, attention_weights, **others)
+    # pointer classes (include/mdconv.h): value and output are "16-byte", the locations and weights "element"
+    _capi.require_aligned_result("msda3d", "output", output)
+    value = _capi.aligned_input(value)
     if output is None:
         output = torch.empty(shape, dtype=value.dtype, device=value.device)
     _run("mdconv_msda3d_forward", d, False, [_ptr(value), _ptr(sampling_locations), _ptr(attention_weights), _ptr(output)],
@@ -138,6 +141,10 @@ def ms_deform_attn_3d_backward(value, spatial_shapes, sampling_locations, attent
     d = _desc(value, sampling_locations, shapes,
               accumulate=int(grads is not None if accumulate is None else bool(accumulate)), flags=flags)
     _check(d, shapes, value, sampling_locations, attention_weights, grad_output=grad_output)
+    # pointer classes (include/mdconv.h): value, grad_output and grad_value are "16-byte", the coordinate tensors "element"
+    if grads is not None and need_grad_value:
+        _capi.require_aligned_result("msda3d", "grad_value", grads[0])
+    value, grad_output = _capi.aligned_input(value), _capi.aligned_input(grad_output)
     if grads is None:
         grads = (torch.empty_like(value) if need_grad_value else None, torch.empty_like(sampling_locations),
                  torch.empty_like(attention_weights))

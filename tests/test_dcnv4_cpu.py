@@ -102,6 +102,10 @@ def test_error_order(capi):
     assert _fwd(capi, bad_and_unsupported) == EINVAL and _fwd(capi, bad_and_unsupported, p) == EINVAL
     unsupported = _desc(capi, D=6)
     assert _fwd(capi, unsupported) == ENULL and _fwd(capi, unsupported, p) == EUNSUPPORTED
+    # pointer alignment: after the NULL checks, before the shape rule (include/mdconv.h, "Pointer alignment") -- 2 mod 16 is
+    # below the 16-byte class of the first tensor, and the descriptor is outside the shape rule as well
+    for call in (_fwd, _bwd):
+        assert call(capi, unsupported, ctypes.c_void_p((p.value | 15) - 13)) == EINVAL and "input pointer must be 16-byte aligned" in capi.last_error()
     # a valid backward with good pointers and no workspace stops at the workspace
     assert _bwd(capi, _desc(capi), p) == -3 and "workspace" in capi.last_error().lower()
 

@@ -146,6 +146,11 @@ def test_workspace_refusal_comes_last(capi):
     assert _bwd(capi, d, p, misaligned, need) == EWORKSPACE and "aligned" in capi.last_error()
     # outside the shape rule the same call stops earlier
     assert _bwd(capi, _desc(capi, C=6), p) == EUNSUPPORTED
+    # pointer alignment: after the NULL checks, before the shape rule (include/mdconv.h, "Pointer alignment") -- 2 mod 16 is
+    # below the 16-byte class of the first tensor, and the descriptor is outside the shape rule as well
+    for call in (_fwd, _bwd):
+        assert call(capi, _desc(capi, C=6), ctypes.c_void_p((p.value | 15) - 13)) == EINVAL and "input pointer must be 16-byte aligned" in capi.last_error()
+        assert call(capi, _desc(capi), ctypes.c_void_p((p.value | 15) - 13)) == EINVAL   # ... and before the workspace
 
 
 def _align(n):

@@ -101,6 +101,9 @@ def test_error_order(capi):
         unsupported = _desc(capi, D=6)
         assert call(capi, unsupported) == ENULL and call(capi, unsupported, p) == EUNSUPPORTED
         assert "fda: outside the shape rule" in capi.last_error()
+        # pointer alignment: after the NULL checks, before the shape rule (include/mdconv.h, "Pointer alignment") -- 2 mod 16 is
+        # below the 16-byte class of the first tensor, and the descriptor is outside the shape rule as well
+        assert call(capi, unsupported, ctypes.c_void_p((p.value | 15) - 13)) == EINVAL and "value pointer must be 16-byte aligned" in capi.last_error()
     # a valid backward with good pointers and no workspace stops at the workspace; the forward needs none, and neither
     # does the backward without grad_value, so those are only sized here
     assert _bwd(capi, _desc(capi), p) == EWORKSPACE and "workspace" in capi.last_error().lower()

@@ -105,6 +105,10 @@ def test_order_of_checks(capi):
     assert _fwd(capi, _desc(capi, D=6)) == ENULL and _bwd(capi, _desc(capi, D=6)) == ENULL
     # outside the shape rule with pointers and no workspace: the shape rule comes before the workspace
     assert _bwd(capi, _desc(capi, D=6), p) == EUNSUPPORTED and _refused(capi)
+    # pointer alignment: after the NULL checks, before the shape rule (include/mdconv.h, "Pointer alignment") -- 2 mod 16 is
+    # below the 16-byte class of the first tensor, and the descriptor is outside the shape rule as well
+    for call in (_fwd, _bwd):
+        assert call(capi, _desc(capi, D=6), ctypes.c_void_p((p.value | 15) - 13)) == EINVAL and "value pointer must be 16-byte aligned" in capi.last_error()
     # inside the rule, pointers given, the workspace missing / too small / misaligned: EWORKSPACE, nothing launched
     need = _ws(capi, _desc(capi), 1)
     assert need > 0

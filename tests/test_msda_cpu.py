@@ -94,6 +94,9 @@ def test_shape_rule_refusals_come_before_any_launch(capi):
         for call in (_fwd, _bwd):
             assert call(capi, d, p) == EUNSUPPORTED, word
             assert word in capi.last_error(), capi.last_error()
+            # pointer alignment: after the NULL checks, before the shape rule (include/mdconv.h, "Pointer alignment") -- 2 mod 16 is
+            # below the 16-byte class of the first tensor, and the descriptor is outside the shape rule as well
+            assert call(capi, d, ctypes.c_void_p((p.value | 15) - 13)) == EINVAL and "value pointer must be 16-byte aligned" in capi.last_error()
         assert _ws(capi, d, 1) == 0
     # batch * heads above 65535: the lists of grad_value only -- the forward and the backward without grad_value take it
     big = dict(N=4096, M=17, D=4, Lq=1, P=1, levels=((1, 1),))
