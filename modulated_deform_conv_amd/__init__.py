@@ -30,6 +30,11 @@ behind the reference's own operator surface.
                                                        MSDeformAttn3DFunction, ms_deform_attn_3d,
                                                        ms_deform_attn_3d_forward / _backward, MSDeformAttn3D -- also
                                                        exported here
+    modulated_deform_conv_amd.dagg                     deformable aggregation (Sparse4D / SparseDrive: key points sampled
+                                                       from all cameras and levels in one call, C ABI in
+                                                       include/mdconv_dagg.h): DeformableAggregationFunction,
+                                                       deformable_aggregation, deformable_aggregation_forward / _backward,
+                                                       feature_maps_format -- also exported here
     modulated_deform_conv_amd.distributed              batch-sharded multi-GPU helper (RCCL)
 
 All compute runs in libmdconv_hip.so (hand-written HIP, C ABI in include/mdconv.h); there is no
@@ -48,7 +53,9 @@ _DROI = ("deform_roi_pool_forward", "deform_roi_pool_backward", "DeformRoIPoolFu
          "DeformRoIPoolPack", "ModulatedDeformRoIPoolPack")
 _MSDA3D = ("ms_deform_attn_3d_forward", "ms_deform_attn_3d_backward", "MSDeformAttn3DFunction", "ms_deform_attn_3d",
            "MSDeformAttn3D")
-__all__ = list(_DCNV3 + _MSDA + _DCNV4 + _FDA + _DROI + _MSDA3D)
+_DAGG = ("deformable_aggregation_forward", "deformable_aggregation_backward", "DeformableAggregationFunction",
+         "deformable_aggregation", "feature_maps_format")
+__all__ = list(_DCNV3 + _MSDA + _DCNV4 + _FDA + _DROI + _MSDA3D + _DAGG)
 
 
 def __getattr__(name):
@@ -71,4 +78,7 @@ def __getattr__(name):
     if name in _MSDA3D:
         from . import msda3d
         return getattr(msda3d, name)
+    if name in _DAGG:
+        from . import dagg
+        return getattr(dagg, name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

@@ -44,6 +44,9 @@ EXPORTS = (
     "mdconv_msda3d_value_len", "mdconv_msda3d_workspace_bytes", "mdconv_msda3d_forward", "mdconv_msda3d_backward",
 )
 
+# include/mdconv_dagg.h (deformable aggregation): a header of its own, so a tuple of its own -- EXPORTS is mdconv.h's
+EXPORTS_DAGG = ("mdconv_dagg_feature_len", "mdconv_dagg_workspace_bytes", "mdconv_dagg_forward", "mdconv_dagg_backward")
+
 
 class MdconvDesc(ctypes.Structure):
     """Mirror of ``struct mdconv_desc`` (include/mdconv.h, ABI v2: the call modes travel in the descriptor)."""
@@ -113,6 +116,14 @@ class MdconvDroiDesc(ctypes.Structure):
                 ("height", ctypes.c_int), ("width", ctypes.c_int), ("rois", ctypes.c_int), ("pooled_h", ctypes.c_int),
                 ("pooled_w", ctypes.c_int), ("sampling_ratio", ctypes.c_int), ("max_grid", ctypes.c_int),
                 ("spatial_scale", ctypes.c_float), ("gamma", ctypes.c_float), ("with_offset", ctypes.c_int),
+                ("accumulate", ctypes.c_int), ("flags", ctypes.c_int)]
+
+
+class MdconvDaggDesc(ctypes.Structure):
+    """Mirror of ``struct mdconv_dagg_desc`` (include/mdconv_dagg.h); ``level_sz`` rows are (H, W), of every camera."""
+    _fields_ = [("dtype", ctypes.c_int), ("coord_dtype", ctypes.c_int), ("batch", ctypes.c_int), ("cams", ctypes.c_int),
+                ("levels", ctypes.c_int), ("level_sz", (ctypes.c_int * 2) * MSDA_MAX_LEVELS), ("channels", ctypes.c_int),
+                ("groups", ctypes.c_int), ("anchors", ctypes.c_int), ("points", ctypes.c_int),
                 ("accumulate", ctypes.c_int), ("flags", ctypes.c_int)]
 
 
@@ -201,6 +212,13 @@ def lib():
             L.mdconv_msda3d_value_len.argtypes = [ctypes.c_void_p]
             L.mdconv_msda3d_workspace_bytes.restype = ctypes.c_size_t
             L.mdconv_msda3d_workspace_bytes.argtypes = [ctypes.c_void_p, ctypes.c_int]
+        # (likewise a build from before deformable aggregation: dagg.py raises there)
+        if hasattr(L, "mdconv_dagg_workspace_bytes"):
+            for name in EXPORTS_DAGG:
+                getattr(L, name).restype = ctypes.c_int
+            L.mdconv_dagg_feature_len.argtypes = [ctypes.c_void_p]
+            L.mdconv_dagg_workspace_bytes.restype = ctypes.c_size_t
+            L.mdconv_dagg_workspace_bytes.argtypes = [ctypes.c_void_p, ctypes.c_int]
         if L.mdconv_abi_version() != ABI_VERSION:
             raise ImportError("libmdconv_hip.so ABI version mismatch")
         _lib = L
