@@ -47,6 +47,11 @@ EXPORTS = (
 # include/mdconv_dagg.h (deformable aggregation): a header of its own, so a tuple of its own -- EXPORTS is mdconv.h's
 EXPORTS_DAGG = ("mdconv_dagg_feature_len", "mdconv_dagg_workspace_bytes", "mdconv_dagg_forward", "mdconv_dagg_backward")
 
+# The descriptor-only queries of the sampling operators, operator -> names: every operator has
+# mdconv_<op>_workspace_bytes(desc, backward) -> size_t besides; out_size takes (desc, axis), a *_len (desc); all return int.
+SAMP_QUERIES = {"dcnv3": ("out_size",), "msda": ("value_len",), "dcnv4": ("out_size", "offset_mask_len"),
+                "fda": ("value_len", "loc_attn_len"), "droi": (), "msda3d": ("value_len",), "dagg": ("feature_len",)}
+
 
 class MdconvDesc(ctypes.Structure):
     """Mirror of ``struct mdconv_desc`` (include/mdconv.h, ABI v2: the call modes travel in the descriptor)."""
@@ -177,48 +182,19 @@ def lib():
             L.mdconv_planned_kernels.argtypes = [ctypes.c_void_p, ctypes.c_int]
         missing = (() if has_math_query else ("mdconv_math_bf16_used",)) + (() if has_layout_query else ("mdconv_result_layout_supported",))
         missing += () if has_plan_query else ("mdconv_planned_kernels",)
-        missing += tuple(n for n in EXPORTS if n.startswith(("mdconv_dcnv3_", "mdconv_msda_", "mdconv_dcnv4_", "mdconv_fda_", "mdconv_droi_", "mdconv_msda3d_")) and not hasattr(L, n))
-        for name in EXPORTS[11:]:
+        # (likewise a build from before one of the sampling operators: that operator's wrapper raises there)
+        missing += tuple(n for n in EXPORTS + EXPORTS_DAGG
+                         if n.startswith(tuple("mdconv_%s_" % op for op in SAMP_QUERIES)) and not hasattr(L, n))
+        for name in EXPORTS[11:] + EXPORTS_DAGG:
             if name not in missing:
                 getattr(L, name).restype = ctypes.c_int
-        # (MDCONV_LIB may name a build from before the DCNv3 core operator: dcnv3.py raises there)
-        if hasattr(L, "mdconv_dcnv3_workspace_bytes"):
-            L.mdconv_dcnv3_out_size.argtypes = [ctypes.c_void_p, ctypes.c_int]
-            L.mdconv_dcnv3_workspace_bytes.restype = ctypes.c_size_t
-            L.mdconv_dcnv3_workspace_bytes.argtypes = [ctypes.c_void_p, ctypes.c_int]
-        # (likewise a build from before multi-scale deformable attention: msda.py raises there)
-        if hasattr(L, "mdconv_msda_workspace_bytes"):
-            L.mdconv_msda_value_len.argtypes = [ctypes.c_void_p]
-            L.mdconv_msda_workspace_bytes.restype = ctypes.c_size_t
-            L.mdconv_msda_workspace_bytes.argtypes = [ctypes.c_void_p, ctypes.c_int]
-        # (likewise a build from before the DCNv4 operator: dcnv4.py raises there)
-        if hasattr(L, "mdconv_dcnv4_workspace_bytes"):
-            L.mdconv_dcnv4_out_size.argtypes = [ctypes.c_void_p, ctypes.c_int]
-            L.mdconv_dcnv4_offset_mask_len.argtypes = [ctypes.c_void_p]
-            L.mdconv_dcnv4_workspace_bytes.restype = ctypes.c_size_t
-            L.mdconv_dcnv4_workspace_bytes.argtypes = [ctypes.c_void_p, ctypes.c_int]
-        # (likewise a build from before packed deformable attention: fda.py raises there)
-        if hasattr(L, "mdconv_fda_workspace_bytes"):
-            L.mdconv_fda_value_len.argtypes = [ctypes.c_void_p]
-            L.mdconv_fda_loc_attn_len.argtypes = [ctypes.c_void_p]
-            L.mdconv_fda_workspace_bytes.restype = ctypes.c_size_t
-            L.mdconv_fda_workspace_bytes.argtypes = [ctypes.c_void_p, ctypes.c_int]
-        # (likewise a build from before deformable RoI pooling: droi.py raises there)
-        if hasattr(L, "mdconv_droi_workspace_bytes"):
-            L.mdconv_droi_workspace_bytes.restype = ctypes.c_size_t
-            L.mdconv_droi_workspace_bytes.argtypes = [ctypes.c_void_p, ctypes.c_int]
-        # (likewise a build from before 3-D multi-scale deformable attention: msda3d.py raises there)
-        if hasattr(L, "mdconv_msda3d_workspace_bytes"):
-            L.mdconv_msda3d_value_len.argtypes = [ctypes.c_void_p]
-            L.mdconv_msda3d_workspace_bytes.restype = ctypes.c_size_t
-            L.mdconv_msda3d_workspace_bytes.argtypes = [ctypes.c_void_p, ctypes.c_int]
-        # (likewise a build from before deformable aggregation: dagg.py raises there)
-        if hasattr(L, "mdconv_dagg_workspace_bytes"):
-            for name in EXPORTS_DAGG:
-                getattr(L, name).restype = ctypes.c_int
-            L.mdconv_dagg_feature_len.argtypes = [ctypes.c_void_p]
-            L.mdconv_dagg_workspace_bytes.restype = ctypes.c_size_t
-            L.mdconv_dagg_workspace_bytes.argtypes = [ctypes.c_void_p, ctypes.c_int]
+        for op, queries in SAMP_QUERIES.items():
+            if not hasattr(L, "mdconv_%s_workspace_bytes" % op):
+                continue
+            ws = getattr(L, "mdconv_%s_workspace_bytes" % op)
+            ws.restype, ws.argtypes = ctypes.c_size_t, [ctypes.c_void_p, ctypes.c_int]
+            for q in queries:
+                getattr(L, "mdconv_%s_%s" % (op, q)).argtypes = [ctypes.c_void_p] + ([ctypes.c_int] if q == "out_size" else [])
         if L.mdconv_abi_version() != ABI_VERSION:
             raise ImportError("libmdconv_hip.so ABI version mismatch")
         _lib = L

@@ -135,7 +135,7 @@ int dagg_bwd_coord_launch(const DaggPlan &p, const DaggTensors &t, hipStream_t s
 #define DAGG_BWD(DT, CT)                                                                                            \
   hipLaunchKernelGGL((dagg_bwd_coord_kernel<DT, CT>), dim3(samp_grid(g.ln.lgVL, g.nanchors)), dim3(256), 0, stream, g, \
                      t.feature, t.loc, t.wts, t.grad_output, t.grad_loc, t.grad_wts)
-  DAGG_DISPATCH(p, DAGG_BWD);
+  SAMP_DISPATCH(p, DAGG_BWD);
 #undef DAGG_BWD
   return check_launch("dagg_bwd_coord");
 }

@@ -72,7 +72,7 @@ int dagg_fwd_launch(const DaggPlan &p, const DaggTensors &t, hipStream_t stream)
 #define DAGG_FWD(DT, CT)                                                                                                \
   hipLaunchKernelGGL((dagg_fwd_kernel<DT, CT>), dim3(samp_grid(g.ln.lgVL, g.nanchors)), dim3(256), 0, stream, g, t.feature, \
                      t.loc, t.wts, t.output)
-  DAGG_DISPATCH(p, DAGG_FWD);
+  SAMP_DISPATCH(p, DAGG_FWD);
 #undef DAGG_FWD
   return check_launch("dagg_fwd");
 }

@@ -63,7 +63,7 @@ int dagg_gather_launch(const DaggPlan &p, const DaggTensors &t, const int *rowpt
 #define DAGG_GATHER(DT, CT)                                                                                        \
   hipLaunchKernelGGL((dagg_gather_kernel<DT, CT>), grid, dim3(256), 0, stream, g, stride, t.grad_output, t.wts, rowptr, \
                      (const int4 *)entries, t.grad_feature)
-  DAGG_DISPATCH(p, DAGG_GATHER);
+  SAMP_DISPATCH(p, DAGG_GATHER);
 #undef DAGG_GATHER
   return check_launch("dagg_gather");
 }

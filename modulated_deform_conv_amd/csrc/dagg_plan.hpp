@@ -62,15 +62,6 @@ void dagg_list_launch(const DaggPlan &p, const DaggTensors &t, bool fill, int *c
                       hipStream_t stream);
 int dagg_gather_launch(const DaggPlan &p, const DaggTensors &t, const int *rowptr, const void *entries, hipStream_t stream);
 
-// the five (value type, coordinate type) pairings: `call(DT, CT)` for the plan's
-#define DAGG_DISPATCH(p, call)                                                       \
-  do {                                                                               \
-    if ((p).dtype == MDCONV_F32) call(MDCONV_F32, MDCONV_F32);                       \
-    else if ((p).dtype == MDCONV_F16 && (p).coord_dtype == MDCONV_F16) call(MDCONV_F16, MDCONV_F16); \
-    else if ((p).dtype == MDCONV_F16) call(MDCONV_F16, MDCONV_F32);                  \
-    else if ((p).coord_dtype == MDCONV_BF16) call(MDCONV_BF16, MDCONV_BF16);         \
-    else call(MDCONV_BF16, MDCONV_F32);                                              \
-  } while (0)
 
 #ifdef __HIPCC__
 // ---- the unit: one stored location and its gate, as the lanes of an anchor share it ----

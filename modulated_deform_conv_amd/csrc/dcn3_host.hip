@@ -1,10 +1,13 @@
 // dcn3_host.hip -- plan and execution of the DCNv3 core operator (dcn3_plan.hpp): the sampling core's kernels (samp_core.hpp)
-// instantiated with Dcn3Op, coordinates in the values' type.
+// instantiated with Dcn3Op, coordinates in the values' type; and the operator's C entry points (include/mdconv.h) on the
+// entry-point layer of samp_api.hpp.
 #include "dcn3_plan.hpp"
+#include "samp_api.hpp"
 
 namespace mdconv {
 
-// `call(DT, CT)` for the plan's type: the coordinates have the values'
+// `call(DT, CT)` for the plan's type: the coordinates have the values', so three of the five pairings of SAMP_DISPATCH
+// (which would instantiate the other two)
 #define DCN3_DISPATCH(p, call)                                       \
   do {                                                               \
     if ((p).dtype == MDCONV_F32) call(MDCONV_F32, MDCONV_F32);       \
@@ -13,13 +16,10 @@ namespace mdconv {
   } while (0)
 
 bool dcn3_plan(const mdconv_dcnv3_desc *d, bool backward, Dcn3Plan *p, const char **why) {
-  const char *dummy;
-  if (!why) why = &dummy;
   *why = nullptr;
   const int64_t lim = (int64_t)1 << 31;
-  const int esz = d->dtype == MDCONV_F32 ? 4 : 2;
-  const int64_t Ho = (d->in_sz[0] + 2 * (int64_t)d->pad[0] - ((int64_t)d->dil[0] * (d->k_sz[0] - 1) + 1)) / d->stride[0] + 1;
-  const int64_t Wo = (d->in_sz[1] + 2 * (int64_t)d->pad[1] - ((int64_t)d->dil[1] * (d->k_sz[1] - 1) + 1)) / d->stride[1] + 1;
+  const int esz = (int)dtype_bytes(d->dtype);
+  const int64_t Ho = dcn_out_size(d, 0), Wo = dcn_out_size(d, 1);
   const int64_t K = (int64_t)d->k_sz[0] * d->k_sz[1];
   const int64_t C = (int64_t)d->groups * d->group_channels;
   const int64_t S_i = (int64_t)d->in_sz[0] * d->in_sz[1], S_o = Ho * Wo;
@@ -49,15 +49,8 @@ bool dcn3_plan(const mdconv_dcnv3_desc *d, bool backward, Dcn3Plan *p, const cha
   g.scale = d->offset_scale;
   g.acc = d->accumulate;
   q.dtype = d->dtype;
-  q.backward = backward;
-  q.det = backward && (d->flags & MDCONV_FLAG_DETERMINISTIC);
   q.skip_input = skip_input;
-  q.total = 0;
-  if (backward && !skip_input) {
-    Bump ws;
-    q.lists = scatter_lists_take(ws, g.B * g.G, g.S_i, seg_stride, q.det);
-    q.total = ws.off;
-  }
+  samp_plan_lists(q, backward, d->flags, skip_input, g.B * g.G, g.S_i, seg_stride);
   *p = q;
   return true;
 }
@@ -79,15 +72,71 @@ int dcn3_backward(const Dcn3Plan &p, const Dcn3Tensors &t, void *ws, hipStream_t
 #undef DCN3_BWD
   if ((rc = check_launch("dcn3_bwd_coord"))) return rc;
   if (p.skip_input) return MDCONV_OK;
-  rc = scatter_lists_build(L, ws, p.det, stream, [&](bool fill, int *cnt, const int *rowptr, void *entries) {
+  const SampGather ga = {g.B, g.S_i, g.S_o, g.G, g.D, g.C, g.ln, g.acc};
+  return samp_lists_gather(L, ws, p.det, ga, p.dtype, t.grad_output, t.grad_input, stream,
+                           [&](bool fill, int *cnt, const int *rowptr, void *entries) {
 #define DCN3_LIST(DT, CT) samp_list_launch<Dcn3Op, CT>(g, fill, t.offset, t.mask, cnt, rowptr, entries, L.seg_stride, stream)
     DCN3_DISPATCH(p, DCN3_LIST);
 #undef DCN3_LIST
   });
-  if (rc) return rc;
-  const SampGather ga = {g.B, g.S_i, g.S_o, g.G, g.D, g.C, g.ln, g.acc};
-  return samp_gather_launch(ga, p.dtype, L.seg_stride, t.grad_output, (const int *)((char *)ws + L.off_rowptr),
-                            (char *)ws + L.off_entries, t.grad_input, stream);
 }
 
+// the descriptor's own validation; the shape rule is dcn3_plan's
+static int dcn3_validate(const mdconv_dcnv3_desc *d, bool) {
+  int rc;
+  if ((rc = desc_dtype("dcnv3", d)) || (rc = desc_dcn_geometry("dcnv3", d)) || (rc = desc_modes("dcnv3", d))) return rc;
+  return desc_finite("dcnv3", "offset_scale", d->offset_scale);
+}
+static const SampOp<mdconv_dcnv3_desc, Dcn3Plan> kDcn3 = {"dcnv3", dcn3_validate, dcn3_plan};
+
 }  // namespace mdconv
+
+using namespace mdconv;
+
+extern "C" {
+
+int mdconv_dcnv3_out_size(const mdconv_dcnv3_desc *d, int axis) {
+  if (!d || axis < 0 || axis > 1 || d->stride[axis] <= 0) return -1;
+  return (d->in_sz[axis] + 2 * d->pad[axis] - (d->dil[axis] * (d->k_sz[axis] - 1) + 1)) / d->stride[axis] + 1;
+}
+
+// (the one query that leaves the error text of the call before it in place when it succeeds)
+size_t mdconv_dcnv3_workspace_bytes(const mdconv_dcnv3_desc *d, int backward) { return samp_workspace_bytes(kDcn3, d, backward); }
+
+int mdconv_dcnv3_forward(const mdconv_dcnv3_desc *d, const void *input, const void *offset, const void *mask,
+                         void *output, void *workspace, size_t workspace_bytes, void *stream) {
+  clear_error();
+  return samp_entry(
+      kDcn3, d, false, workspace, workspace_bytes,
+      [&] {
+        const size_t es = dtype_bytes(d->dtype);
+        return check_args({{input, "input", 16}, {offset, "offset", es}, {mask, "mask", es}, {output, "output", 16}});
+      },
+      [&](const Dcn3Plan &p) {
+        Dcn3Tensors t = {};
+        t.input = input; t.offset = offset; t.mask = mask; t.output = output;
+        return dcn3_forward(p, t, (hipStream_t)stream);
+      });
+}
+
+int mdconv_dcnv3_backward(const mdconv_dcnv3_desc *d, const void *input, const void *offset, const void *mask,
+                          const void *grad_output, void *grad_input, void *grad_offset, void *grad_mask,
+                          void *workspace, size_t workspace_bytes, void *stream) {
+  clear_error();
+  return samp_entry(
+      kDcn3, d, true, workspace, workspace_bytes,
+      [&] {
+        const size_t es = dtype_bytes(d->dtype);
+        return check_args({{input, "input", 16}, {offset, "offset", es}, {mask, "mask", es}, {grad_output, "grad_output", 16},
+                           {grad_offset, "grad_offset", es}, {grad_mask, "grad_mask", es},
+                           {grad_input, "grad_input", 16, !(d->flags & MDCONV_FLAG_NO_GRAD_INPUT)}});
+      },
+      [&](const Dcn3Plan &p) {
+        Dcn3Tensors t = {};
+        t.input = input; t.offset = offset; t.mask = mask; t.grad_output = grad_output;
+        t.grad_input = grad_input; t.grad_offset = grad_offset; t.grad_mask = grad_mask;
+        return dcn3_backward(p, t, workspace, (hipStream_t)stream);
+      });
+}
+
+}  // extern "C"

@@ -35,7 +35,7 @@ struct Dcn3Plan {
   size_t total;         // workspace bytes
 };
 
-// false: outside the shape rule; *why names the rule it breaks.  The descriptor has passed validation (mdconv_api.hip).
+// false: outside the shape rule; *why names the rule it breaks.  The descriptor has passed validation (the operator's *_host.hip).
 bool dcn3_plan(const mdconv_dcnv3_desc *d, bool backward, Dcn3Plan *p, const char **why);
 int dcn3_forward(const Dcn3Plan &p, const Dcn3Tensors &t, hipStream_t stream);
 int dcn3_backward(const Dcn3Plan &p, const Dcn3Tensors &t, void *ws, hipStream_t stream);

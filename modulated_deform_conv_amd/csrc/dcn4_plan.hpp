@@ -52,7 +52,7 @@ struct Dcn4Plan {
 // elements per row of offset_mask for G groups of K taps
 inline int64_t dcn4_row_len(int64_t G, int64_t K) { return (G * K * 3 + 7) / 8 * 8; }
 
-// false: outside the shape rule; *why names the rule it breaks.  The descriptor has passed validation (mdconv_api.hip).
+// false: outside the shape rule; *why names the rule it breaks.  The descriptor has passed validation (the operator's *_host.hip).
 bool dcn4_plan(const mdconv_dcnv4_desc *d, bool backward, Dcn4Plan *p, const char **why);
 int dcn4_forward(const Dcn4Plan &p, const Dcn4Tensors &t, hipStream_t stream);
 int dcn4_backward(const Dcn4Plan &p, const Dcn4Tensors &t, void *ws, hipStream_t stream);

@@ -80,7 +80,7 @@ int droi_bwd_offset_launch(const DroiPlan &p, const DroiTensors &t, hipStream_t 
 #define DROI_BWD(DT, CT)                                                                                                 \
   hipLaunchKernelGGL((droi_bwd_offset_kernel<DT, CT>), dim3(samp_grid(g.ln.lgVL, g.nbins)), dim3(256), 0, stream, g, \
                      t.input, (const float *)t.rois, t.offset, t.grad_output, t.grad_offset)
-  DROI_DISPATCH(p, DROI_BWD);
+  SAMP_DISPATCH(p, DROI_BWD);
 #undef DROI_BWD
   return check_launch("droi_bwd_offset");
 }

@@ -62,7 +62,7 @@ int droi_fwd_launch(const DroiPlan &p, const DroiTensors &t, hipStream_t stream)
 #define DROI_FWD(DT, CT)                                                                                                   \
   hipLaunchKernelGGL((droi_fwd_kernel<DT, CT>), dim3(samp_grid(g.ln.lgVL, g.nbins)), dim3(256), 0, stream, g, t.input, \
                      (const float *)t.rois, t.offset, t.output)
-  DROI_DISPATCH(p, DROI_FWD);
+  SAMP_DISPATCH(p, DROI_FWD);
 #undef DROI_FWD
   return check_launch("droi_fwd");
 }

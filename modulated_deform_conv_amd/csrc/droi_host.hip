@@ -1,16 +1,15 @@
 // droi_host.hip -- plan and execution of deformable RoI pooling (droi_plan.hpp): the family's own forward, offset-gradient
-// and list kernels, the list builder and the channels-last gather of the sampling operators.
+// and list kernels, the list builder and the channels-last gather of the sampling operators; and the operator's C entry
+// points (include/mdconv.h) on the entry-point layer of samp_api.hpp.
 #include "droi_plan.hpp"
+#include "samp_api.hpp"
 
 namespace mdconv {
 
 bool droi_plan(const mdconv_droi_desc *d, bool backward, DroiPlan *p, const char **why) {
-  const char *dummy;
-  if (!why) why = &dummy;
   *why = nullptr;
   const int64_t lim = (int64_t)1 << 31;
-  const int esz = d->dtype == MDCONV_F32 ? 4 : 2;
-  const int csz = d->coord_dtype == MDCONV_F32 ? 4 : 2;
+  const int esz = (int)dtype_bytes(d->dtype), csz = (int)dtype_bytes(d->coord_dtype);
   const int64_t gcap = d->sampling_ratio > 0 ? d->sampling_ratio : d->max_grid;   // 1..16
   const int64_t rows_in = (int64_t)d->batch * d->height;                           // times width below
   const int64_t bins = (int64_t)d->rois * d->pooled_h;                             // times pooled_w below
@@ -37,15 +36,8 @@ bool droi_plan(const mdconv_droi_desc *d, bool backward, DroiPlan *p, const char
   g.ln = samp_lanes(g.C, esz);
   q.dtype = d->dtype;
   q.coord_dtype = d->coord_dtype;
-  q.backward = backward;
-  q.det = backward && (d->flags & MDCONV_FLAG_DETERMINISTIC);
   q.skip_input = skip_input;
-  q.total = 0;
-  if (backward && !skip_input) {
-    Bump ws;
-    q.lists = scatter_lists_take(ws, 1, g.B * g.H * g.W, (int64_t)g.nbins * g.gcap * g.gcap * 4, q.det);
-    q.total = ws.off;
-  }
+  samp_plan_lists(q, backward, d->flags, skip_input, 1, g.B * g.H * g.W, (int64_t)g.nbins * g.gcap * g.gcap * 4);
   *p = q;
   return true;
 }
@@ -58,13 +50,88 @@ int droi_backward(const DroiPlan &p, const DroiTensors &t, void *ws, hipStream_t
   int rc;
   if (g.with_offset && (rc = droi_bwd_offset_launch(p, t, stream))) return rc;
   if (p.skip_input) return MDCONV_OK;
-  rc = scatter_lists_build(L, ws, p.det, stream, [&](bool fill, int *cnt, const int *rowptr, void *entries) {
+  const SampGather ga = {1, g.B * g.H * g.W, g.nbins, 1, g.C, g.C, g.ln, g.acc};
+  return samp_lists_gather(L, ws, p.det, ga, p.dtype, t.grad_output, t.grad_input, stream,
+                           [&](bool fill, int *cnt, const int *rowptr, void *entries) {
     droi_list_launch(p, t, fill, cnt, rowptr, entries, stream);
   });
-  if (rc) return rc;
-  const SampGather ga = {1, g.B * g.H * g.W, g.nbins, 1, g.C, g.C, g.ln, g.acc};
-  return samp_gather_launch(ga, p.dtype, L.seg_stride, t.grad_output, (const int *)((char *)ws + L.off_rowptr),
-                            (char *)ws + L.off_entries, t.grad_input, stream);
 }
 
+// the descriptor's own validation; the shape rule is droi_plan's
+static int droi_validate(const mdconv_droi_desc *d, bool backward) {
+  int rc;
+  if ((rc = desc_dtypes("droi", d))) return rc;
+  if (d->batch <= 0 || d->channels <= 0 || d->height <= 0 || d->width <= 0 || d->rois <= 0 || d->pooled_h <= 0 ||
+      d->pooled_w <= 0) {
+    set_error("droi: batch, channels, height, width, rois, pooled_h and pooled_w must be positive (%d, %d, %d, %d, %d, %d, %d)",
+              d->batch, d->channels, d->height, d->width, d->rois, d->pooled_h, d->pooled_w);
+    return MDCONV_EINVAL;
+  }
+  if (d->sampling_ratio < 0 || d->sampling_ratio > 16) {
+    set_error("droi: sampling_ratio must be 0 (adaptive) or 1..16, is %d", d->sampling_ratio);
+    return MDCONV_EINVAL;
+  }
+  if (d->max_grid < 1 || d->max_grid > 16) {
+    set_error("droi: max_grid must be 1..16, is %d", d->max_grid);
+    return MDCONV_EINVAL;
+  }
+  if ((rc = desc_finite("droi", "spatial_scale", d->spatial_scale)) || (rc = desc_finite("droi", "gamma", d->gamma)) ||
+      (rc = desc_modes("droi", d)))
+    return rc;
+  if (backward && !d->with_offset && (d->flags & MDCONV_FLAG_NO_GRAD_INPUT)) {
+    set_error("droi: a backward with with_offset == 0 and MDCONV_FLAG_NO_GRAD_INPUT has nothing to compute");
+    return MDCONV_EINVAL;
+  }
+  return MDCONV_OK;
+}
+static const SampOp<mdconv_droi_desc, DroiPlan> kDroi = {"droi", droi_validate, droi_plan};
+
 }  // namespace mdconv
+
+using namespace mdconv;
+
+extern "C" {
+
+size_t mdconv_droi_workspace_bytes(const mdconv_droi_desc *d, int backward) {
+  clear_error();
+  return samp_workspace_bytes(kDroi, d, backward);
+}
+
+int mdconv_droi_forward(const mdconv_droi_desc *d, const void *input, const void *rois, const void *offset, void *output,
+                        void *workspace, size_t workspace_bytes, void *stream) {
+  clear_error();
+  return samp_entry(
+      kDroi, d, false, workspace, workspace_bytes,
+      [&] {
+        return check_args({{input, "input", 16}, {rois, "rois", 4}, {output, "output", 16},
+                           {offset, "offset", dtype_bytes(d->coord_dtype), d->with_offset != 0}});
+      },
+      [&](const DroiPlan &p) {
+        DroiTensors t = {};
+        t.input = input; t.rois = rois; t.offset = offset; t.output = output;
+        return droi_forward(p, t, (hipStream_t)stream);
+      });
+}
+
+int mdconv_droi_backward(const mdconv_droi_desc *d, const void *input, const void *rois, const void *offset,
+                         const void *grad_output, void *grad_input, void *grad_offset, void *workspace,
+                         size_t workspace_bytes, void *stream) {
+  clear_error();
+  return samp_entry(
+      kDroi, d, true, workspace, workspace_bytes,
+      [&] {
+        const size_t cs = dtype_bytes(d->coord_dtype);
+        const bool off = d->with_offset != 0;
+        return check_args({{input, "input", 16}, {rois, "rois", 4}, {grad_output, "grad_output", 16},
+                           {offset, "offset", cs, off}, {grad_offset, "grad_offset", cs, off},
+                           {grad_input, "grad_input", 16, !(d->flags & MDCONV_FLAG_NO_GRAD_INPUT)}});
+      },
+      [&](const DroiPlan &p) {
+        DroiTensors t = {};
+        t.input = input; t.rois = rois; t.offset = offset; t.grad_output = grad_output;
+        t.grad_input = grad_input; t.grad_offset = grad_offset;
+        return droi_backward(p, t, workspace, (hipStream_t)stream);
+      });
+}
+
+}  // extern "C"

@@ -36,7 +36,7 @@ struct DroiPlan {
   size_t total;             // workspace bytes
 };
 
-// false: outside the shape rule; *why names the rule it breaks.  The descriptor has passed validation (mdconv_api.hip).
+// false: outside the shape rule; *why names the rule it breaks.  The descriptor has passed validation (the operator's *_host.hip).
 bool droi_plan(const mdconv_droi_desc *d, bool backward, DroiPlan *p, const char **why);
 int droi_forward(const DroiPlan &p, const DroiTensors &t, hipStream_t stream);
 int droi_backward(const DroiPlan &p, const DroiTensors &t, void *ws, hipStream_t stream);
@@ -47,15 +47,6 @@ int droi_bwd_offset_launch(const DroiPlan &p, const DroiTensors &t, hipStream_t 
 void droi_list_launch(const DroiPlan &p, const DroiTensors &t, bool fill, int *cnt, const int *rowptr, void *entries,
                       hipStream_t stream);
 
-// the five (value type, coordinate type) pairings: `call(DT, CT)` for the plan's
-#define DROI_DISPATCH(p, call)                                                       \
-  do {                                                                               \
-    if ((p).dtype == MDCONV_F32) call(MDCONV_F32, MDCONV_F32);                       \
-    else if ((p).dtype == MDCONV_F16 && (p).coord_dtype == MDCONV_F16) call(MDCONV_F16, MDCONV_F16); \
-    else if ((p).dtype == MDCONV_F16) call(MDCONV_F16, MDCONV_F32);                  \
-    else if ((p).coord_dtype == MDCONV_BF16) call(MDCONV_BF16, MDCONV_BF16);         \
-    else call(MDCONV_BF16, MDCONV_F32);                                              \
-  } while (0)
 
 #ifdef __HIPCC__
 // ---- the arithmetic the three kernels share, so that they agree bit for bit on every sample ----

@@ -34,7 +34,7 @@ struct FdaPlan {
   size_t total;             // workspace bytes
 };
 
-// false: outside the shape rule; *why names the rule it breaks.  The descriptor has passed validation (mdconv_api.hip).
+// false: outside the shape rule; *why names the rule it breaks.  The descriptor has passed validation (the operator's *_host.hip).
 bool fda_plan(const mdconv_fda_desc *d, bool backward, FdaPlan *p, const char **why);
 int fda_forward(const FdaPlan &p, const FdaTensors &t, hipStream_t stream);
 int fda_backward(const FdaPlan &p, const FdaTensors &t, void *ws, hipStream_t stream);

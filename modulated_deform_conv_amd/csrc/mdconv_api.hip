@@ -1,7 +1,9 @@
-// mdconv_api.hip -- the C ABI (include/mdconv.h): descriptor validation, path selection, and the
+// mdconv_api.hip -- the convolution API of the C ABI (include/mdconv.h): descriptor validation, path selection, and the
 // eight entry points that replace the reference's MDCONV_CUDA exports
 // (mdeformable_conv.cu:460-465 registers two; modulated_deform_conv.py calls all eight:
-//  :28, :57, :112, :142, :194, :225, :281, :313).
+//  :28, :57, :112, :142, :194, :225, :281, :313); and what the whole library has once: the thread-local error text
+// (set_error, mdconv_last_error) and check_launch.  The sampling operators' entry points live beside their planners in the
+// operators' *_host.hip, on the entry-point layer of samp_api.hpp, whose pointer checks the entry points here use too.
 #include <stdarg.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -14,15 +16,10 @@
 #include <utility>
 
 #include "mdconv_common.hpp"
-#include "dcn3_plan.hpp"
-#include "dcn4_plan.hpp"
-#include "msda_plan.hpp"
-#include "msda3_plan.hpp"
-#include "fda_plan.hpp"
-#include "droi_plan.hpp"
 #include "dw_plan.hpp"
 #include "hp_plan.hpp"
 #include "mfma_plan.hpp"
+#include "samp_api.hpp"   // require, require_aligned, check_ws
 
 namespace mdconv {
 
@@ -253,28 +250,6 @@ static void note_direct_fallback(const Geom &g, int dtype, bool backward, int pa
           "C_in/deformable_groups a multiple of 8, at least 16, aligned with them");
 }
 
-static int require(const void *p, const char *name) {
-  if (!p) {
-    set_error("%s pointer is NULL", name);
-    return MDCONV_ENULL;
-  }
-  return MDCONV_OK;
-}
-
-// Pointer alignment ("Pointer alignment"; include/mdconv.h states the class of every argument): a tensor pointer is
-// aligned to its class -- `align` = the tensor's element size ("element": every access through it is one element wide, a raw
-// buffer load at an element-aligned offset, or behind a pointer test with an element-wise fallback) or 16 ("16-byte": the
-// kernels move 16-byte vectors through it).  Checked after the NULL checks and before the shape rule and the workspace; a
-// pointer the call ignores (NULL where that is allowed, a skipped gradient, bias without with_bias) is not looked at.
-static int require_aligned(const void *p, const char *name, size_t align) {
-  if (p && ((uintptr_t)p & (align - 1)) != 0) {
-    set_error("%s pointer must be %zu-byte aligned", name, align);
-    return MDCONV_EINVAL;
-  }
-  return MDCONV_OK;
-}
-static size_t dtype_bytes(int dt) { return dt == MDCONV_F64 ? 8 : (dt == MDCONV_F32 ? 4 : 2); }
-
 // element type of the call's tensors (the dtype flags stripped), whether offset / mask are fp32, and whether a backward's
 // grad_weight / grad_bias are (the forward ignores that bit: one descriptor serves both directions)
 static int base_dtype(const mdconv_desc *d) { return d->dtype & ~(MDCONV_SAMPLING_F32 | MDCONV_WGRAD_F32); }
@@ -473,19 +448,6 @@ static int refuse(const CallPlan &cp, const Geom &g, int dt, int path, bool back
   else
     set_det_refusal(g, dt, path);
   return MDCONV_EUNSUPPORTED;
-}
-
-static int check_ws(void *ws, size_t have, size_t need) {
-  if (need == 0) return MDCONV_OK;
-  if (!ws || have < need) {
-    set_error("workspace too small: need %zu bytes, have %zu", need, have);
-    return MDCONV_EWORKSPACE;
-  }
-  if (((uintptr_t)ws & 15) != 0) {
-    set_error("workspace must be 16-byte aligned");
-    return MDCONV_EWORKSPACE;
-  }
-  return MDCONV_OK;
 }
 
 static int run_forward(const mdconv_desc *d, int nd, int modulated, Tensors t, void *ws,
@@ -715,231 +677,6 @@ static int wait_weight_ready(hipStream_t waiter, bool keyed, hipStream_t produce
 
 using namespace mdconv;
 
-// ---- DCNv3 core operator (dcn3_plan.hpp): the descriptor's own validation; the shape rule is dcn3_plan's ----
-static int dcn3_validate(const mdconv_dcnv3_desc *d) {
-  if (!d) {
-    set_error("descriptor pointer is NULL");
-    return MDCONV_EINVAL;
-  }
-  if (d->dtype != MDCONV_F32 && d->dtype != MDCONV_F16 && d->dtype != MDCONV_BF16) {
-    set_error("dcnv3: dtype %d is not MDCONV_F32, MDCONV_F16 or MDCONV_BF16 (the dtype flags do not apply)", d->dtype);
-    return MDCONV_EINVAL;
-  }
-  if (d->batch <= 0 || d->groups <= 0 || d->group_channels <= 0) {
-    set_error("dcnv3: batch, groups and group_channels must be positive (%d, %d, %d)", d->batch, d->groups, d->group_channels);
-    return MDCONV_EINVAL;
-  }
-  for (int a = 0; a < 2; ++a) {
-    if (d->in_sz[a] <= 0 || d->k_sz[a] <= 0 || d->stride[a] <= 0 || d->dil[a] <= 0 || d->pad[a] < 0) {
-      set_error("dcnv3: bad geometry on axis %d (in_sz=%d, k_sz=%d, stride=%d, pad=%d, dil=%d)", a, d->in_sz[a], d->k_sz[a],
-                d->stride[a], d->pad[a], d->dil[a]);
-      return MDCONV_EINVAL;
-    }
-    const long long span = (long long)d->dil[a] * (d->k_sz[a] - 1) + 1;
-    if ((long long)d->in_sz[a] + 2LL * d->pad[a] < span) {
-      set_error("dcnv3: the output extent on axis %d is below 1 (in_sz=%d, pad=%d, dilated kernel %lld)", a, d->in_sz[a],
-                d->pad[a], span);
-      return MDCONV_EINVAL;
-    }
-  }
-  if (d->accumulate != 0 && d->accumulate != 1) {
-    set_error("dcnv3: accumulate must be 0 or 1, is %d", d->accumulate);
-    return MDCONV_EINVAL;
-  }
-  if (d->flags & ~(MDCONV_FLAG_DETERMINISTIC | MDCONV_FLAG_NO_GRAD_INPUT)) {
-    set_error("dcnv3: unknown bits 0x%x in flags; the flags are MDCONV_FLAG_DETERMINISTIC (1) and MDCONV_FLAG_NO_GRAD_INPUT (4)",
-              (unsigned)(d->flags & ~(MDCONV_FLAG_DETERMINISTIC | MDCONV_FLAG_NO_GRAD_INPUT)));
-    return MDCONV_EINVAL;
-  }
-  if (!(d->offset_scale == d->offset_scale) || d->offset_scale - d->offset_scale != 0.f) {
-    set_error("dcnv3: offset_scale is not finite");
-    return MDCONV_EINVAL;
-  }
-  return MDCONV_OK;
-}
-static int dcn3_refuse(const char *why) {
-  set_error("dcnv3: outside the shape rule of the operator: %s", why);
-  return MDCONV_EUNSUPPORTED;
-}
-
-// ---- DCNv4 operator (dcn4_plan.hpp): the descriptor's own validation; the shape rule is dcn4_plan's ----
-static int dcn4_validate(const mdconv_dcnv4_desc *d) {
-  if (!d) {
-    set_error("descriptor pointer is NULL");
-    return MDCONV_EINVAL;
-  }
-  if (d->dtype != MDCONV_F32 && d->dtype != MDCONV_F16 && d->dtype != MDCONV_BF16) {
-    set_error("dcnv4: dtype %d is not MDCONV_F32, MDCONV_F16 or MDCONV_BF16 (the dtype flags do not apply)", d->dtype);
-    return MDCONV_EINVAL;
-  }
-  if (d->coord_dtype != d->dtype && d->coord_dtype != MDCONV_F32) {
-    set_error("dcnv4: coord_dtype %d is neither dtype (%d) nor MDCONV_F32", d->coord_dtype, d->dtype);
-    return MDCONV_EINVAL;
-  }
-  if (d->batch <= 0 || d->groups <= 0 || d->group_channels <= 0) {
-    set_error("dcnv4: batch, groups and group_channels must be positive (%d, %d, %d)", d->batch, d->groups, d->group_channels);
-    return MDCONV_EINVAL;
-  }
-  for (int a = 0; a < 2; ++a) {
-    if (d->in_sz[a] <= 0 || d->k_sz[a] <= 0 || d->stride[a] <= 0 || d->dil[a] <= 0 || d->pad[a] < 0) {
-      set_error("dcnv4: bad geometry on axis %d (in_sz=%d, k_sz=%d, stride=%d, pad=%d, dil=%d)", a, d->in_sz[a], d->k_sz[a],
-                d->stride[a], d->pad[a], d->dil[a]);
-      return MDCONV_EINVAL;
-    }
-    const long long span = (long long)d->dil[a] * (d->k_sz[a] - 1) + 1;
-    if ((long long)d->in_sz[a] + 2LL * d->pad[a] < span) {
-      set_error("dcnv4: the output extent on axis %d is below 1 (in_sz=%d, pad=%d, dilated kernel %lld)", a, d->in_sz[a],
-                d->pad[a], span);
-      return MDCONV_EINVAL;
-    }
-  }
-  if (d->remove_center != 0 && d->remove_center != 1) {
-    set_error("dcnv4: remove_center must be 0 or 1, is %d", d->remove_center);
-    return MDCONV_EINVAL;
-  }
-  if (d->remove_center && (d->k_sz[0] % 2 == 0 || d->k_sz[1] % 2 == 0 || (d->k_sz[0] == 1 && d->k_sz[1] == 1))) {
-    set_error("dcnv4: remove_center needs an odd kernel with a tap left (%d x %d)", d->k_sz[0], d->k_sz[1]);
-    return MDCONV_EINVAL;
-  }
-  if (d->accumulate != 0 && d->accumulate != 1) {
-    set_error("dcnv4: accumulate must be 0 or 1, is %d", d->accumulate);
-    return MDCONV_EINVAL;
-  }
-  const int dcn4_flags = MDCONV_FLAG_DETERMINISTIC | MDCONV_FLAG_NO_GRAD_INPUT | MDCONV_FLAG_SOFTMAX;
-  if (d->flags & ~dcn4_flags) {
-    set_error("dcnv4: unknown bits 0x%x in flags; the flags are MDCONV_FLAG_DETERMINISTIC (1), MDCONV_FLAG_NO_GRAD_INPUT (4) "
-              "and MDCONV_FLAG_SOFTMAX (256)", (unsigned)(d->flags & ~dcn4_flags));
-    return MDCONV_EINVAL;
-  }
-  if (!(d->offset_scale == d->offset_scale) || d->offset_scale - d->offset_scale != 0.f) {
-    set_error("dcnv4: offset_scale is not finite");
-    return MDCONV_EINVAL;
-  }
-  return MDCONV_OK;
-}
-static int dcn4_refuse(const char *why) {
-  set_error("dcnv4: outside the shape rule of the operator: %s", why);
-  return MDCONV_EUNSUPPORTED;
-}
-
-// ---- multi-scale deformable attention (msda_plan.hpp) and packed deformable attention (fda_plan.hpp), whose descriptors have
-// the same fields: the descriptor's own validation under the operator's name; the shape rules are msda_plan's / fda_plan's ----
-template <class Desc> static int attn_validate(const Desc *d, const char *op) {
-  if (!d) {
-    set_error("descriptor pointer is NULL");
-    return MDCONV_EINVAL;
-  }
-  if (d->dtype != MDCONV_F32 && d->dtype != MDCONV_F16 && d->dtype != MDCONV_BF16) {
-    set_error("%s: dtype %d is not MDCONV_F32, MDCONV_F16 or MDCONV_BF16 (the dtype flags do not apply)", op, d->dtype);
-    return MDCONV_EINVAL;
-  }
-  if (d->coord_dtype != d->dtype && d->coord_dtype != MDCONV_F32) {
-    set_error("%s: coord_dtype %d is neither dtype (%d) nor MDCONV_F32", op, d->coord_dtype, d->dtype);
-    return MDCONV_EINVAL;
-  }
-  if (d->batch <= 0 || d->heads <= 0 || d->head_channels <= 0 || d->queries <= 0 || d->points <= 0) {
-    set_error("%s: batch, heads, head_channels, queries and points must be positive (%d, %d, %d, %d, %d)", op, d->batch, d->heads,
-              d->head_channels, d->queries, d->points);
-    return MDCONV_EINVAL;
-  }
-  if (d->levels < 1 || d->levels > MDCONV_MSDA_MAX_LEVELS) {
-    set_error("%s: levels must be 1..%d, is %d", op, MDCONV_MSDA_MAX_LEVELS, d->levels);
-    return MDCONV_EINVAL;
-  }
-  constexpr int kAxes = (int)(sizeof(d->level_sz[0]) / sizeof(int));   // 2: (H, W); 3: (T, H, W)
-  for (int l = 0; l < d->levels; ++l) {
-    const int *e = d->level_sz[l];
-    bool bad = false;
-    for (int a = 0; a < kAxes; ++a) bad = bad || e[a] <= 0;
-    if (bad) {
-      if (kAxes == 2) set_error("%s: level %d has a non-positive extent (%d x %d)", op, l, e[0], e[1]);
-      else set_error("%s: level %d has a non-positive extent (%d x %d x %d)", op, l, e[0], e[1], e[kAxes - 1]);
-      return MDCONV_EINVAL;
-    }
-  }
-  if (d->accumulate != 0 && d->accumulate != 1) {
-    set_error("%s: accumulate must be 0 or 1, is %d", op, d->accumulate);
-    return MDCONV_EINVAL;
-  }
-  if (d->flags & ~(MDCONV_FLAG_DETERMINISTIC | MDCONV_FLAG_NO_GRAD_INPUT)) {
-    set_error("%s: unknown bits 0x%x in flags; the flags are MDCONV_FLAG_DETERMINISTIC (1) and MDCONV_FLAG_NO_GRAD_INPUT (4)", op,
-              (unsigned)(d->flags & ~(MDCONV_FLAG_DETERMINISTIC | MDCONV_FLAG_NO_GRAD_INPUT)));
-    return MDCONV_EINVAL;
-  }
-  return MDCONV_OK;
-}
-static int msda_validate(const mdconv_msda_desc *d) { return attn_validate(d, "msda"); }
-static int fda_validate(const mdconv_fda_desc *d) { return attn_validate(d, "fda"); }
-static int msda3d_validate(const mdconv_msda3d_desc *d) { return attn_validate(d, "msda3d"); }
-static int msda_refuse(const char *why) {
-  set_error("msda: outside the shape rule of the operator: %s", why);
-  return MDCONV_EUNSUPPORTED;
-}
-static int msda3d_refuse(const char *why) {
-  set_error("msda3d: outside the shape rule of the operator: %s", why);
-  return MDCONV_EUNSUPPORTED;
-}
-static int fda_refuse(const char *why) {
-  set_error("fda: outside the shape rule of the operator: %s", why);
-  return MDCONV_EUNSUPPORTED;
-}
-
-// ---- deformable RoI pooling (droi_plan.hpp): the descriptor's own validation; the shape rule is droi_plan's ----
-static int droi_validate(const mdconv_droi_desc *d, bool backward) {
-  if (!d) {
-    set_error("descriptor pointer is NULL");
-    return MDCONV_EINVAL;
-  }
-  if (d->dtype != MDCONV_F32 && d->dtype != MDCONV_F16 && d->dtype != MDCONV_BF16) {
-    set_error("droi: dtype %d is not MDCONV_F32, MDCONV_F16 or MDCONV_BF16 (the dtype flags do not apply)", d->dtype);
-    return MDCONV_EINVAL;
-  }
-  if (d->coord_dtype != d->dtype && d->coord_dtype != MDCONV_F32) {
-    set_error("droi: coord_dtype %d is neither dtype (%d) nor MDCONV_F32", d->coord_dtype, d->dtype);
-    return MDCONV_EINVAL;
-  }
-  if (d->batch <= 0 || d->channels <= 0 || d->height <= 0 || d->width <= 0 || d->rois <= 0 || d->pooled_h <= 0 ||
-      d->pooled_w <= 0) {
-    set_error("droi: batch, channels, height, width, rois, pooled_h and pooled_w must be positive (%d, %d, %d, %d, %d, %d, %d)",
-              d->batch, d->channels, d->height, d->width, d->rois, d->pooled_h, d->pooled_w);
-    return MDCONV_EINVAL;
-  }
-  if (d->sampling_ratio < 0 || d->sampling_ratio > 16) {
-    set_error("droi: sampling_ratio must be 0 (adaptive) or 1..16, is %d", d->sampling_ratio);
-    return MDCONV_EINVAL;
-  }
-  if (d->max_grid < 1 || d->max_grid > 16) {
-    set_error("droi: max_grid must be 1..16, is %d", d->max_grid);
-    return MDCONV_EINVAL;
-  }
-  if (!(d->spatial_scale == d->spatial_scale) || d->spatial_scale - d->spatial_scale != 0.f) {
-    set_error("droi: spatial_scale is not finite");
-    return MDCONV_EINVAL;
-  }
-  if (!(d->gamma == d->gamma) || d->gamma - d->gamma != 0.f) {
-    set_error("droi: gamma is not finite");
-    return MDCONV_EINVAL;
-  }
-  if (d->accumulate != 0 && d->accumulate != 1) {
-    set_error("droi: accumulate must be 0 or 1, is %d", d->accumulate);
-    return MDCONV_EINVAL;
-  }
-  if (d->flags & ~(MDCONV_FLAG_DETERMINISTIC | MDCONV_FLAG_NO_GRAD_INPUT)) {
-    set_error("droi: unknown bits 0x%x in flags; the flags are MDCONV_FLAG_DETERMINISTIC (1) and MDCONV_FLAG_NO_GRAD_INPUT (4)",
-              (unsigned)(d->flags & ~(MDCONV_FLAG_DETERMINISTIC | MDCONV_FLAG_NO_GRAD_INPUT)));
-    return MDCONV_EINVAL;
-  }
-  if (backward && !d->with_offset && (d->flags & MDCONV_FLAG_NO_GRAD_INPUT)) {
-    set_error("droi: a backward with with_offset == 0 and MDCONV_FLAG_NO_GRAD_INPUT has nothing to compute");
-    return MDCONV_EINVAL;
-  }
-  return MDCONV_OK;
-}
-static int droi_refuse(const char *why) {
-  set_error("droi: outside the shape rule of the operator: %s", why);
-  return MDCONV_EUNSUPPORTED;
-}
-
 extern "C" {
 
 int mdconv_abi_version(void) { return MDCONV_ABI_VERSION; }
@@ -1155,437 +892,6 @@ int mdconv_modulated_deform_conv3d_backward(const mdconv_desc *d, const void *in
   t.grad_output = grad_output; t.grad_input = grad_input; t.grad_weight = grad_weight;
   t.grad_bias = grad_bias; t.grad_offset = grad_offset; t.grad_mask = grad_mask;
   return run_backward(d, 3, 1, t, workspace, workspace_bytes, stream);
-}
-
-int mdconv_dcnv3_out_size(const mdconv_dcnv3_desc *d, int axis) {
-  if (!d || axis < 0 || axis > 1 || d->stride[axis] <= 0) return -1;
-  return (d->in_sz[axis] + 2 * d->pad[axis] - (d->dil[axis] * (d->k_sz[axis] - 1) + 1)) / d->stride[axis] + 1;
-}
-
-size_t mdconv_dcnv3_workspace_bytes(const mdconv_dcnv3_desc *d, int backward) {
-  Dcn3Plan p;
-  const char *why;
-  if (dcn3_validate(d)) return 0;
-  if (!dcn3_plan(d, backward != 0, &p, &why)) {
-    dcn3_refuse(why);
-    return 0;
-  }
-  return p.total;
-}
-
-int mdconv_dcnv3_forward(const mdconv_dcnv3_desc *d, const void *input, const void *offset, const void *mask,
-                         void *output, void *workspace, size_t workspace_bytes, void *stream) {
-  g_err[0] = 0;
-  int rc = dcn3_validate(d);
-  if (rc) return rc;
-  if ((rc = require(input, "input")) || (rc = require(offset, "offset")) || (rc = require(mask, "mask")) ||
-      (rc = require(output, "output")))
-    return rc;
-  if ((rc = require_aligned(input, "input", 16)) || (rc = require_aligned(offset, "offset", dtype_bytes(d->dtype))) ||
-      (rc = require_aligned(mask, "mask", dtype_bytes(d->dtype))) || (rc = require_aligned(output, "output", 16)))
-    return rc;
-  Dcn3Plan p;
-  const char *why;
-  if (!dcn3_plan(d, false, &p, &why)) return dcn3_refuse(why);
-  if ((rc = check_ws(workspace, workspace_bytes, p.total))) return rc;
-  Dcn3Tensors t = {};
-  t.input = input; t.offset = offset; t.mask = mask; t.output = output;
-  return dcn3_forward(p, t, (hipStream_t)stream);
-}
-
-int mdconv_dcnv3_backward(const mdconv_dcnv3_desc *d, const void *input, const void *offset, const void *mask,
-                          const void *grad_output, void *grad_input, void *grad_offset, void *grad_mask,
-                          void *workspace, size_t workspace_bytes, void *stream) {
-  g_err[0] = 0;
-  int rc = dcn3_validate(d);
-  if (rc) return rc;
-  if ((rc = require(input, "input")) || (rc = require(offset, "offset")) || (rc = require(mask, "mask")) ||
-      (rc = require(grad_output, "grad_output")) || (rc = require(grad_offset, "grad_offset")) ||
-      (rc = require(grad_mask, "grad_mask")))
-    return rc;
-  if (!(d->flags & MDCONV_FLAG_NO_GRAD_INPUT) && (rc = require(grad_input, "grad_input"))) return rc;
-  if ((rc = require_aligned(input, "input", 16)) || (rc = require_aligned(offset, "offset", dtype_bytes(d->dtype))) ||
-      (rc = require_aligned(mask, "mask", dtype_bytes(d->dtype))) || (rc = require_aligned(grad_output, "grad_output", 16)) ||
-      (rc = require_aligned(grad_offset, "grad_offset", dtype_bytes(d->dtype))) ||
-      (rc = require_aligned(grad_mask, "grad_mask", dtype_bytes(d->dtype))))
-    return rc;
-  if (!(d->flags & MDCONV_FLAG_NO_GRAD_INPUT) && (rc = require_aligned(grad_input, "grad_input", 16))) return rc;
-  Dcn3Plan p;
-  const char *why;
-  if (!dcn3_plan(d, true, &p, &why)) return dcn3_refuse(why);
-  if ((rc = check_ws(workspace, workspace_bytes, p.total))) return rc;
-  Dcn3Tensors t = {};
-  t.input = input; t.offset = offset; t.mask = mask; t.grad_output = grad_output;
-  t.grad_input = grad_input; t.grad_offset = grad_offset; t.grad_mask = grad_mask;
-  return dcn3_backward(p, t, workspace, (hipStream_t)stream);
-}
-
-int mdconv_dcnv4_out_size(const mdconv_dcnv4_desc *d, int axis) {
-  if (!d || axis < 0 || axis > 1 || d->stride[axis] <= 0) return -1;
-  return (d->in_sz[axis] + 2 * d->pad[axis] - (d->dil[axis] * (d->k_sz[axis] - 1) + 1)) / d->stride[axis] + 1;
-}
-
-int mdconv_dcnv4_offset_mask_len(const mdconv_dcnv4_desc *d) {
-  g_err[0] = 0;
-  if (dcn4_validate(d)) return -1;
-  const long long K = (long long)d->k_sz[0] * d->k_sz[1] - d->remove_center;   // below 2^62
-  if (K >= (1LL << 31) / 3 / d->groups) {   // G * K * 3 + 7 stays below 2^31
-    set_error("dcnv4: a row of offset_mask has 2^31 elements or more");
-    return -1;
-  }
-  return (int)dcn4_row_len(d->groups, K);
-}
-
-size_t mdconv_dcnv4_workspace_bytes(const mdconv_dcnv4_desc *d, int backward) {
-  Dcn4Plan p;
-  const char *why;
-  g_err[0] = 0;
-  if (dcn4_validate(d)) return 0;
-  if (!dcn4_plan(d, backward != 0, &p, &why)) {
-    dcn4_refuse(why);
-    return 0;
-  }
-  return p.total;
-}
-
-int mdconv_dcnv4_forward(const mdconv_dcnv4_desc *d, const void *input, const void *offset_mask, void *output,
-                         void *workspace, size_t workspace_bytes, void *stream) {
-  g_err[0] = 0;
-  int rc = dcn4_validate(d);
-  if (rc) return rc;
-  if ((rc = require(input, "input")) || (rc = require(offset_mask, "offset_mask")) || (rc = require(output, "output")))
-    return rc;
-  if ((rc = require_aligned(input, "input", 16)) || (rc = require_aligned(offset_mask, "offset_mask", dtype_bytes(d->coord_dtype))) ||
-      (rc = require_aligned(output, "output", 16)))
-    return rc;
-  Dcn4Plan p;
-  const char *why;
-  if (!dcn4_plan(d, false, &p, &why)) return dcn4_refuse(why);
-  if ((rc = check_ws(workspace, workspace_bytes, p.total))) return rc;
-  Dcn4Tensors t = {};
-  t.input = input; t.offset_mask = offset_mask; t.output = output;
-  return dcn4_forward(p, t, (hipStream_t)stream);
-}
-
-int mdconv_dcnv4_backward(const mdconv_dcnv4_desc *d, const void *input, const void *offset_mask, const void *grad_output,
-                          void *grad_input, void *grad_offset_mask, void *workspace, size_t workspace_bytes, void *stream) {
-  g_err[0] = 0;
-  int rc = dcn4_validate(d);
-  if (rc) return rc;
-  if ((rc = require(input, "input")) || (rc = require(offset_mask, "offset_mask")) ||
-      (rc = require(grad_output, "grad_output")) || (rc = require(grad_offset_mask, "grad_offset_mask")))
-    return rc;
-  if (!(d->flags & MDCONV_FLAG_NO_GRAD_INPUT) && (rc = require(grad_input, "grad_input"))) return rc;
-  if ((rc = require_aligned(input, "input", 16)) || (rc = require_aligned(offset_mask, "offset_mask", dtype_bytes(d->coord_dtype))) ||
-      (rc = require_aligned(grad_output, "grad_output", 16)) ||
-      (rc = require_aligned(grad_offset_mask, "grad_offset_mask", dtype_bytes(d->coord_dtype))))
-    return rc;
-  if (!(d->flags & MDCONV_FLAG_NO_GRAD_INPUT) && (rc = require_aligned(grad_input, "grad_input", 16))) return rc;
-  Dcn4Plan p;
-  const char *why;
-  if (!dcn4_plan(d, true, &p, &why)) return dcn4_refuse(why);
-  if ((rc = check_ws(workspace, workspace_bytes, p.total))) return rc;
-  Dcn4Tensors t = {};
-  t.input = input; t.offset_mask = offset_mask; t.grad_output = grad_output;
-  t.grad_input = grad_input; t.grad_offset_mask = grad_offset_mask;
-  return dcn4_backward(p, t, workspace, (hipStream_t)stream);
-}
-
-int mdconv_msda_value_len(const mdconv_msda_desc *d) {
-  g_err[0] = 0;
-  if (msda_validate(d)) return -1;
-  long long S = 0;
-  for (int l = 0; l < d->levels; ++l) S += (long long)d->level_sz[l][0] * d->level_sz[l][1];   // (8 products below 2^62)
-  if (S >= (1LL << 31)) {
-    set_error("msda: the levels have 2^31 rows or more");
-    return -1;
-  }
-  return (int)S;
-}
-
-size_t mdconv_msda_workspace_bytes(const mdconv_msda_desc *d, int backward) {
-  MsdaPlan p;
-  const char *why;
-  g_err[0] = 0;
-  if (msda_validate(d)) return 0;
-  if (!msda_plan(d, backward != 0, &p, &why)) {
-    msda_refuse(why);
-    return 0;
-  }
-  return p.total;
-}
-
-int mdconv_msda_forward(const mdconv_msda_desc *d, const void *value, const void *sampling_locations,
-                        const void *attention_weights, void *output, void *workspace, size_t workspace_bytes, void *stream) {
-  g_err[0] = 0;
-  int rc = msda_validate(d);
-  if (rc) return rc;
-  if ((rc = require(value, "value")) || (rc = require(sampling_locations, "sampling_locations")) ||
-      (rc = require(attention_weights, "attention_weights")) || (rc = require(output, "output")))
-    return rc;
-  if ((rc = require_aligned(value, "value", 16)) ||
-      (rc = require_aligned(sampling_locations, "sampling_locations", dtype_bytes(d->coord_dtype))) ||
-      (rc = require_aligned(attention_weights, "attention_weights", dtype_bytes(d->coord_dtype))) ||
-      (rc = require_aligned(output, "output", 16)))
-    return rc;
-  MsdaPlan p;
-  const char *why;
-  if (!msda_plan(d, false, &p, &why)) return msda_refuse(why);
-  if ((rc = check_ws(workspace, workspace_bytes, p.total))) return rc;
-  MsdaTensors t = {};
-  t.value = value; t.loc = sampling_locations; t.attn = attention_weights; t.output = output;
-  return msda_forward(p, t, (hipStream_t)stream);
-}
-
-int mdconv_msda_backward(const mdconv_msda_desc *d, const void *value, const void *sampling_locations,
-                         const void *attention_weights, const void *grad_output, void *grad_value,
-                         void *grad_sampling_locations, void *grad_attention_weights, void *workspace,
-                         size_t workspace_bytes, void *stream) {
-  g_err[0] = 0;
-  int rc = msda_validate(d);
-  if (rc) return rc;
-  if ((rc = require(value, "value")) || (rc = require(sampling_locations, "sampling_locations")) ||
-      (rc = require(attention_weights, "attention_weights")) || (rc = require(grad_output, "grad_output")) ||
-      (rc = require(grad_sampling_locations, "grad_sampling_locations")) ||
-      (rc = require(grad_attention_weights, "grad_attention_weights")))
-    return rc;
-  if (!(d->flags & MDCONV_FLAG_NO_GRAD_INPUT) && (rc = require(grad_value, "grad_value"))) return rc;
-  if ((rc = require_aligned(value, "value", 16)) ||
-      (rc = require_aligned(sampling_locations, "sampling_locations", dtype_bytes(d->coord_dtype))) ||
-      (rc = require_aligned(attention_weights, "attention_weights", dtype_bytes(d->coord_dtype))) ||
-      (rc = require_aligned(grad_output, "grad_output", 16)) ||
-      (rc = require_aligned(grad_sampling_locations, "grad_sampling_locations", dtype_bytes(d->coord_dtype))) ||
-      (rc = require_aligned(grad_attention_weights, "grad_attention_weights", dtype_bytes(d->coord_dtype))))
-    return rc;
-  if (!(d->flags & MDCONV_FLAG_NO_GRAD_INPUT) && (rc = require_aligned(grad_value, "grad_value", 16))) return rc;
-  MsdaPlan p;
-  const char *why;
-  if (!msda_plan(d, true, &p, &why)) return msda_refuse(why);
-  if ((rc = check_ws(workspace, workspace_bytes, p.total))) return rc;
-  MsdaTensors t = {};
-  t.value = value; t.loc = sampling_locations; t.attn = attention_weights; t.grad_output = grad_output;
-  t.grad_value = grad_value; t.grad_loc = grad_sampling_locations; t.grad_attn = grad_attention_weights;
-  return msda_backward(p, t, workspace, (hipStream_t)stream);
-}
-
-int mdconv_msda3d_value_len(const mdconv_msda3d_desc *d) {
-  g_err[0] = 0;
-  if (msda3d_validate(d)) return -1;
-  long long S = 0;
-  bool big = false;
-  for (int l = 0; l < d->levels; ++l) {
-    const long long plane = (long long)d->level_sz[l][1] * d->level_sz[l][2];   // below 2^62
-    if (plane >= (1LL << 31)) big = true;
-    else S += plane * d->level_sz[l][0];   // (8 products below 2^62)
-  }
-  if (big || S >= (1LL << 31)) {
-    set_error("msda3d: the levels have 2^31 rows or more");
-    return -1;
-  }
-  return (int)S;
-}
-
-size_t mdconv_msda3d_workspace_bytes(const mdconv_msda3d_desc *d, int backward) {
-  Msda3Plan p;
-  const char *why;
-  g_err[0] = 0;
-  if (msda3d_validate(d)) return 0;
-  if (!msda3_plan(d, backward != 0, &p, &why)) {
-    msda3d_refuse(why);
-    return 0;
-  }
-  return p.total;
-}
-
-int mdconv_msda3d_forward(const mdconv_msda3d_desc *d, const void *value, const void *sampling_locations,
-                          const void *attention_weights, void *output, void *workspace, size_t workspace_bytes, void *stream) {
-  g_err[0] = 0;
-  int rc = msda3d_validate(d);
-  if (rc) return rc;
-  if ((rc = require(value, "value")) || (rc = require(sampling_locations, "sampling_locations")) ||
-      (rc = require(attention_weights, "attention_weights")) || (rc = require(output, "output")))
-    return rc;
-  if ((rc = require_aligned(value, "value", 16)) ||
-      (rc = require_aligned(sampling_locations, "sampling_locations", dtype_bytes(d->coord_dtype))) ||
-      (rc = require_aligned(attention_weights, "attention_weights", dtype_bytes(d->coord_dtype))) ||
-      (rc = require_aligned(output, "output", 16)))
-    return rc;
-  Msda3Plan p;
-  const char *why;
-  if (!msda3_plan(d, false, &p, &why)) return msda3d_refuse(why);
-  if ((rc = check_ws(workspace, workspace_bytes, p.total))) return rc;
-  Msda3Tensors t = {};
-  t.value = value; t.loc = sampling_locations; t.attn = attention_weights; t.output = output;
-  return msda3_forward(p, t, (hipStream_t)stream);
-}
-
-int mdconv_msda3d_backward(const mdconv_msda3d_desc *d, const void *value, const void *sampling_locations,
-                           const void *attention_weights, const void *grad_output, void *grad_value,
-                           void *grad_sampling_locations, void *grad_attention_weights, void *workspace,
-                           size_t workspace_bytes, void *stream) {
-  g_err[0] = 0;
-  int rc = msda3d_validate(d);
-  if (rc) return rc;
-  if ((rc = require(value, "value")) || (rc = require(sampling_locations, "sampling_locations")) ||
-      (rc = require(attention_weights, "attention_weights")) || (rc = require(grad_output, "grad_output")) ||
-      (rc = require(grad_sampling_locations, "grad_sampling_locations")) ||
-      (rc = require(grad_attention_weights, "grad_attention_weights")))
-    return rc;
-  if (!(d->flags & MDCONV_FLAG_NO_GRAD_INPUT) && (rc = require(grad_value, "grad_value"))) return rc;
-  if ((rc = require_aligned(value, "value", 16)) ||
-      (rc = require_aligned(sampling_locations, "sampling_locations", dtype_bytes(d->coord_dtype))) ||
-      (rc = require_aligned(attention_weights, "attention_weights", dtype_bytes(d->coord_dtype))) ||
-      (rc = require_aligned(grad_output, "grad_output", 16)) ||
-      (rc = require_aligned(grad_sampling_locations, "grad_sampling_locations", dtype_bytes(d->coord_dtype))) ||
-      (rc = require_aligned(grad_attention_weights, "grad_attention_weights", dtype_bytes(d->coord_dtype))))
-    return rc;
-  if (!(d->flags & MDCONV_FLAG_NO_GRAD_INPUT) && (rc = require_aligned(grad_value, "grad_value", 16))) return rc;
-  Msda3Plan p;
-  const char *why;
-  if (!msda3_plan(d, true, &p, &why)) return msda3d_refuse(why);
-  if ((rc = check_ws(workspace, workspace_bytes, p.total))) return rc;
-  Msda3Tensors t = {};
-  t.value = value; t.loc = sampling_locations; t.attn = attention_weights; t.grad_output = grad_output;
-  t.grad_value = grad_value; t.grad_loc = grad_sampling_locations; t.grad_attn = grad_attention_weights;
-  return msda3_backward(p, t, workspace, (hipStream_t)stream);
-}
-
-int mdconv_fda_value_len(const mdconv_fda_desc *d) {
-  g_err[0] = 0;
-  if (fda_validate(d)) return -1;
-  long long S = 0;
-  for (int l = 0; l < d->levels; ++l) S += (long long)d->level_sz[l][0] * d->level_sz[l][1];   // (8 products below 2^62)
-  if (S >= (1LL << 31)) {
-    set_error("fda: the levels have 2^31 rows or more");
-    return -1;
-  }
-  return (int)S;
-}
-
-int mdconv_fda_loc_attn_len(const mdconv_fda_desc *d) {
-  g_err[0] = 0;
-  if (fda_validate(d)) return -1;
-  const long long len = 3LL * d->levels * d->points;
-  if (len >= (1LL << 31)) {
-    set_error("fda: a row of sampling_loc_attn has 2^31 elements or more");
-    return -1;
-  }
-  return (int)len;
-}
-
-size_t mdconv_fda_workspace_bytes(const mdconv_fda_desc *d, int backward) {
-  FdaPlan p;
-  const char *why;
-  g_err[0] = 0;
-  if (fda_validate(d)) return 0;
-  if (!fda_plan(d, backward != 0, &p, &why)) {
-    fda_refuse(why);
-    return 0;
-  }
-  return p.total;
-}
-
-int mdconv_fda_forward(const mdconv_fda_desc *d, const void *value, const void *sampling_loc_attn, void *output,
-                       void *workspace, size_t workspace_bytes, void *stream) {
-  g_err[0] = 0;
-  int rc = fda_validate(d);
-  if (rc) return rc;
-  if ((rc = require(value, "value")) || (rc = require(sampling_loc_attn, "sampling_loc_attn")) || (rc = require(output, "output")))
-    return rc;
-  if ((rc = require_aligned(value, "value", 16)) ||
-      (rc = require_aligned(sampling_loc_attn, "sampling_loc_attn", dtype_bytes(d->coord_dtype))) ||
-      (rc = require_aligned(output, "output", 16)))
-    return rc;
-  FdaPlan p;
-  const char *why;
-  if (!fda_plan(d, false, &p, &why)) return fda_refuse(why);
-  if ((rc = check_ws(workspace, workspace_bytes, p.total))) return rc;
-  FdaTensors t = {};
-  t.value = value; t.loc_attn = sampling_loc_attn; t.output = output;
-  return fda_forward(p, t, (hipStream_t)stream);
-}
-
-int mdconv_fda_backward(const mdconv_fda_desc *d, const void *value, const void *sampling_loc_attn, const void *grad_output,
-                        void *grad_value, void *grad_sampling_loc_attn, void *workspace, size_t workspace_bytes, void *stream) {
-  g_err[0] = 0;
-  int rc = fda_validate(d);
-  if (rc) return rc;
-  if ((rc = require(value, "value")) || (rc = require(sampling_loc_attn, "sampling_loc_attn")) ||
-      (rc = require(grad_output, "grad_output")) || (rc = require(grad_sampling_loc_attn, "grad_sampling_loc_attn")))
-    return rc;
-  if (!(d->flags & MDCONV_FLAG_NO_GRAD_INPUT) && (rc = require(grad_value, "grad_value"))) return rc;
-  if ((rc = require_aligned(value, "value", 16)) ||
-      (rc = require_aligned(sampling_loc_attn, "sampling_loc_attn", dtype_bytes(d->coord_dtype))) ||
-      (rc = require_aligned(grad_output, "grad_output", 16)) ||
-      (rc = require_aligned(grad_sampling_loc_attn, "grad_sampling_loc_attn", dtype_bytes(d->coord_dtype))))
-    return rc;
-  if (!(d->flags & MDCONV_FLAG_NO_GRAD_INPUT) && (rc = require_aligned(grad_value, "grad_value", 16))) return rc;
-  FdaPlan p;
-  const char *why;
-  if (!fda_plan(d, true, &p, &why)) return fda_refuse(why);
-  if ((rc = check_ws(workspace, workspace_bytes, p.total))) return rc;
-  FdaTensors t = {};
-  t.value = value; t.loc_attn = sampling_loc_attn; t.grad_output = grad_output;
-  t.grad_value = grad_value; t.grad_loc_attn = grad_sampling_loc_attn;
-  return fda_backward(p, t, workspace, (hipStream_t)stream);
-}
-
-size_t mdconv_droi_workspace_bytes(const mdconv_droi_desc *d, int backward) {
-  DroiPlan p;
-  const char *why;
-  g_err[0] = 0;
-  if (droi_validate(d, backward != 0)) return 0;
-  if (!droi_plan(d, backward != 0, &p, &why)) {
-    droi_refuse(why);
-    return 0;
-  }
-  return p.total;
-}
-
-int mdconv_droi_forward(const mdconv_droi_desc *d, const void *input, const void *rois, const void *offset, void *output,
-                        void *workspace, size_t workspace_bytes, void *stream) {
-  g_err[0] = 0;
-  int rc = droi_validate(d, false);
-  if (rc) return rc;
-  if ((rc = require(input, "input")) || (rc = require(rois, "rois")) || (rc = require(output, "output"))) return rc;
-  if (d->with_offset && (rc = require(offset, "offset"))) return rc;
-  if ((rc = require_aligned(input, "input", 16)) || (rc = require_aligned(rois, "rois", 4)) ||
-      (rc = require_aligned(output, "output", 16)))
-    return rc;
-  if (d->with_offset && (rc = require_aligned(offset, "offset", dtype_bytes(d->coord_dtype)))) return rc;
-  DroiPlan p;
-  const char *why;
-  if (!droi_plan(d, false, &p, &why)) return droi_refuse(why);
-  if ((rc = check_ws(workspace, workspace_bytes, p.total))) return rc;
-  DroiTensors t = {};
-  t.input = input; t.rois = rois; t.offset = offset; t.output = output;
-  return droi_forward(p, t, (hipStream_t)stream);
-}
-
-int mdconv_droi_backward(const mdconv_droi_desc *d, const void *input, const void *rois, const void *offset,
-                         const void *grad_output, void *grad_input, void *grad_offset, void *workspace,
-                         size_t workspace_bytes, void *stream) {
-  g_err[0] = 0;
-  int rc = droi_validate(d, true);
-  if (rc) return rc;
-  if ((rc = require(input, "input")) || (rc = require(rois, "rois")) || (rc = require(grad_output, "grad_output"))) return rc;
-  if (d->with_offset && ((rc = require(offset, "offset")) || (rc = require(grad_offset, "grad_offset")))) return rc;
-  if (!(d->flags & MDCONV_FLAG_NO_GRAD_INPUT) && (rc = require(grad_input, "grad_input"))) return rc;
-  if ((rc = require_aligned(input, "input", 16)) || (rc = require_aligned(rois, "rois", 4)) ||
-      (rc = require_aligned(grad_output, "grad_output", 16)))
-    return rc;
-  if (d->with_offset && ((rc = require_aligned(offset, "offset", dtype_bytes(d->coord_dtype))) ||
-                         (rc = require_aligned(grad_offset, "grad_offset", dtype_bytes(d->coord_dtype)))))
-    return rc;
-  if (!(d->flags & MDCONV_FLAG_NO_GRAD_INPUT) && (rc = require_aligned(grad_input, "grad_input", 16))) return rc;
-  DroiPlan p;
-  const char *why;
-  if (!droi_plan(d, true, &p, &why)) return droi_refuse(why);
-  if ((rc = check_ws(workspace, workspace_bytes, p.total))) return rc;
-  DroiTensors t = {};
-  t.input = input; t.rois = rois; t.offset = offset; t.grad_output = grad_output;
-  t.grad_input = grad_input; t.grad_offset = grad_offset;
-  return droi_backward(p, t, workspace, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -98,7 +98,7 @@ int msda3_bwd_coord_launch(const Msda3Plan &p, const Msda3Tensors &t, hipStream_
 #define MSDA3_BWD(DT, CT)                                                                                          \
   hipLaunchKernelGGL((msda3_bwd_coord_kernel<DT, CT>), dim3(samp_grid(g.ln.lgVL, g.npairs)), dim3(256), 0, stream, g, \
                      t.value, t.loc, t.attn, t.grad_output, t.grad_loc, t.grad_attn)
-  MSDA3_DISPATCH(p, MSDA3_BWD);
+  SAMP_DISPATCH(p, MSDA3_BWD);
 #undef MSDA3_BWD
   return check_launch("msda3_bwd_coord");
 }

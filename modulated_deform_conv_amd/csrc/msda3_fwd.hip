@@ -59,7 +59,7 @@ int msda3_fwd_launch(const Msda3Plan &p, const Msda3Tensors &t, hipStream_t stre
 #define MSDA3_FWD(DT, CT)                                                                                               \
   hipLaunchKernelGGL((msda3_fwd_kernel<DT, CT>), dim3(samp_grid(g.ln.lgVL, g.npairs)), dim3(256), 0, stream, g, t.value, \
                      t.loc, t.attn, t.output)
-  MSDA3_DISPATCH(p, MSDA3_FWD);
+  SAMP_DISPATCH(p, MSDA3_FWD);
 #undef MSDA3_FWD
   return check_launch("msda3_fwd");
 }

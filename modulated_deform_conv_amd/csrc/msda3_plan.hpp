@@ -42,7 +42,7 @@ struct Msda3Plan {
   size_t total;             // workspace bytes
 };
 
-// false: outside the shape rule; *why names the rule it breaks.  The descriptor has passed validation (mdconv_api.hip).
+// false: outside the shape rule; *why names the rule it breaks.  The descriptor has passed validation (the operator's *_host.hip).
 bool msda3_plan(const mdconv_msda3d_desc *d, bool backward, Msda3Plan *p, const char **why);
 int msda3_forward(const Msda3Plan &p, const Msda3Tensors &t, hipStream_t stream);
 int msda3_backward(const Msda3Plan &p, const Msda3Tensors &t, void *ws, hipStream_t stream);
@@ -53,15 +53,6 @@ int msda3_bwd_coord_launch(const Msda3Plan &p, const Msda3Tensors &t, hipStream_
 void msda3_list_launch(const Msda3Plan &p, const Msda3Tensors &t, bool fill, int *cnt, const int *rowptr, void *entries,
                        hipStream_t stream);
 
-// the five (value type, coordinate type) pairings: `call(DT, CT)` for the plan's
-#define MSDA3_DISPATCH(p, call)                                                      \
-  do {                                                                               \
-    if ((p).dtype == MDCONV_F32) call(MDCONV_F32, MDCONV_F32);                       \
-    else if ((p).dtype == MDCONV_F16 && (p).coord_dtype == MDCONV_F16) call(MDCONV_F16, MDCONV_F16); \
-    else if ((p).dtype == MDCONV_F16) call(MDCONV_F16, MDCONV_F32);                  \
-    else if ((p).coord_dtype == MDCONV_BF16) call(MDCONV_BF16, MDCONV_BF16);         \
-    else call(MDCONV_BF16, MDCONV_F32);                                              \
-  } while (0)
 
 #ifdef __HIPCC__
 // ---- the sampling arithmetic, once for the three kernels, so they agree to the bit on every sample ----

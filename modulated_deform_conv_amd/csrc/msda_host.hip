@@ -1,33 +1,26 @@
 // msda_host.hip -- plan and execution of multi-scale deformable attention (msda_plan.hpp): the sampling core's kernels
-// (samp_core.hpp) instantiated with MsdaOp for the five (value type, coordinate type) pairings.
+// (samp_core.hpp) instantiated with MsdaOp for the five (value type, coordinate type) pairings, and the operator's C entry
+// points (include/mdconv.h) on the entry-point layer of samp_api.hpp.
 #include "msda_plan.hpp"
+#include "samp_api.hpp"
 
 namespace mdconv {
 
 bool msda_plan(const mdconv_msda_desc *d, bool backward, MsdaPlan *p, const char **why) {
-  const char *dummy;
-  if (!why) why = &dummy;
   *why = nullptr;
   const int64_t lim = (int64_t)1 << 31;
-  const int esz = d->dtype == MDCONV_F32 ? 4 : 2;
-  const int csz = d->coord_dtype == MDCONV_F32 ? 4 : 2;
+  const int esz = (int)dtype_bytes(d->dtype), csz = (int)dtype_bytes(d->coord_dtype);
   const int64_t K = (int64_t)d->levels * d->points;
   const int64_t C = (int64_t)d->heads * d->head_channels;
   const int64_t pairs = (int64_t)d->batch * d->queries;   // times heads below, once both factors are bounded
-  int64_t S = 0;
-  bool level_big = false;
-  for (int l = 0; l < d->levels; ++l) {
-    const int64_t rows = (int64_t)d->level_sz[l][0] * d->level_sz[l][1];
-    if (rows >= lim) level_big = true;   // (and stays out of the sum, which then cannot overflow)
-    else S += rows;
-  }
+  const int64_t S = level_rows(d);                        // -1: 2^31 rows or more
   const bool skip_value = backward && (d->flags & MDCONV_FLAG_NO_GRAD_INPUT);
   const int64_t seg_stride = K * d->queries * 4;   // K <= 4096 once checked: no overflow
   // (each product is checked with its factors bounded by the checks before it, so none overflows 64 bits)
   if (esz == 4 && d->head_channels % 4) *why = "head_channels is not a multiple of 4 (fp32 rows of 16 bytes)";
   else if (esz == 2 && d->head_channels % 8) *why = "head_channels is not a multiple of 8 (16-bit rows of 16 bytes)";
   else if (K > 4096) *why = "levels * points exceeds 4096";
-  else if (level_big || C >= lim || S >= lim || pairs >= lim || d->batch * S >= lim || d->batch * S * C >= lim / esz ||
+  else if (S < 0 || C >= lim || pairs >= lim || d->batch * S >= lim || d->batch * S * C >= lim / esz ||
            pairs * C >= lim / esz || pairs * d->heads >= lim || pairs * d->heads * K * 2 * csz >= lim)
     *why = "a tensor of the call has 2^31 bytes or more";
   else if (backward && !skip_value && (int64_t)d->batch * d->heads > 65535)
@@ -41,34 +34,20 @@ bool msda_plan(const mdconv_msda_desc *d, bool backward, MsdaPlan *p, const char
   MsdaGeom &g = q.g;
   g.N = d->batch; g.M = d->heads; g.D = d->head_channels; g.C = (int)C; g.Lq = d->queries; g.L = d->levels; g.P = d->points;
   g.K = (int)K; g.S = (int)S; g.npairs = (int)(pairs * d->heads);
-  int start = 0;
-  for (int l = 0; l < MDCONV_MSDA_MAX_LEVELS; ++l) {
-    const bool used = l < d->levels;
-    g.lvH[l] = used ? d->level_sz[l][0] : 1;
-    g.lvW[l] = used ? d->level_sz[l][1] : 1;
-    g.lvS[l] = used ? start : 0;
-    if (used) start += g.lvH[l] * g.lvW[l];
-  }
+  level_fill(g, d);
   g.ln = samp_lanes(g.D, esz);
   g.acc = d->accumulate;
   q.dtype = d->dtype;
   q.coord_dtype = d->coord_dtype;
-  q.backward = backward;
-  q.det = backward && (d->flags & MDCONV_FLAG_DETERMINISTIC);
   q.skip_value = skip_value;
-  q.total = 0;
-  if (backward && !skip_value) {
-    Bump ws;
-    q.lists = scatter_lists_take(ws, g.N * g.M, g.S, seg_stride, q.det);
-    q.total = ws.off;
-  }
+  samp_plan_lists(q, backward, d->flags, skip_value, g.N * g.M, g.S, seg_stride);
   *p = q;
   return true;
 }
 
 int msda_forward(const MsdaPlan &p, const MsdaTensors &t, hipStream_t stream) {
 #define MSDA_FWD(DT, CT) samp_fwd_launch<MsdaOp, DT, CT>(p.g, t.value, t.loc, t.attn, t.output, stream)
-  MSDA_DISPATCH(p, MSDA_FWD);
+  SAMP_DISPATCH(p, MSDA_FWD);
 #undef MSDA_FWD
   return check_launch("msda_fwd");
 }
@@ -79,19 +58,79 @@ int msda_backward(const MsdaPlan &p, const MsdaTensors &t, void *ws, hipStream_t
   int rc;
 #define MSDA_BWD(DT, CT) \
   samp_bwd_coord_launch<MsdaOp, DT, CT>(g, t.value, t.loc, t.attn, t.grad_output, t.grad_loc, t.grad_attn, stream)
-  MSDA_DISPATCH(p, MSDA_BWD);
+  SAMP_DISPATCH(p, MSDA_BWD);
 #undef MSDA_BWD
   if ((rc = check_launch("msda_bwd_coord"))) return rc;
   if (p.skip_value) return MDCONV_OK;
-  rc = scatter_lists_build(L, ws, p.det, stream, [&](bool fill, int *cnt, const int *rowptr, void *entries) {
+  const SampGather ga = {g.N, g.S, g.Lq, g.M, g.D, g.C, g.ln, g.acc};
+  return samp_lists_gather(L, ws, p.det, ga, p.dtype, t.grad_output, t.grad_value, stream,
+                           [&](bool fill, int *cnt, const int *rowptr, void *entries) {
 #define MSDA_LIST(DT, CT) samp_list_launch<MsdaOp, CT>(g, fill, t.loc, t.attn, cnt, rowptr, entries, L.seg_stride, stream)
-    MSDA_DISPATCH(p, MSDA_LIST);   // (by coordinate type: three instances)
+    SAMP_DISPATCH(p, MSDA_LIST);   // (by coordinate type: three instances)
 #undef MSDA_LIST
   });
-  if (rc) return rc;
-  const SampGather ga = {g.N, g.S, g.Lq, g.M, g.D, g.C, g.ln, g.acc};
-  return samp_gather_launch(ga, p.dtype, L.seg_stride, t.grad_output, (const int *)((char *)ws + L.off_rowptr),
-                            (char *)ws + L.off_entries, t.grad_value, stream);
 }
 
+static int msda_validate(const mdconv_msda_desc *d, bool) { return attn_validate("msda", d); }
+static const SampOp<mdconv_msda_desc, MsdaPlan> kMsda = {"msda", msda_validate, msda_plan};
+
 }  // namespace mdconv
+
+using namespace mdconv;
+
+extern "C" {
+
+int mdconv_msda_value_len(const mdconv_msda_desc *d) {
+  clear_error();
+  if (msda_validate(d, false)) return -1;
+  const int64_t S = level_rows(d);
+  if (S < 0) set_error("msda: the levels have 2^31 rows or more");
+  return (int)S;
+}
+
+size_t mdconv_msda_workspace_bytes(const mdconv_msda_desc *d, int backward) {
+  clear_error();
+  return samp_workspace_bytes(kMsda, d, backward);
+}
+
+int mdconv_msda_forward(const mdconv_msda_desc *d, const void *value, const void *sampling_locations,
+                        const void *attention_weights, void *output, void *workspace, size_t workspace_bytes, void *stream) {
+  clear_error();
+  return samp_entry(
+      kMsda, d, false, workspace, workspace_bytes,
+      [&] {
+        const size_t cs = dtype_bytes(d->coord_dtype);
+        return check_args({{value, "value", 16}, {sampling_locations, "sampling_locations", cs},
+                           {attention_weights, "attention_weights", cs}, {output, "output", 16}});
+      },
+      [&](const MsdaPlan &p) {
+        MsdaTensors t = {};
+        t.value = value; t.loc = sampling_locations; t.attn = attention_weights; t.output = output;
+        return msda_forward(p, t, (hipStream_t)stream);
+      });
+}
+
+int mdconv_msda_backward(const mdconv_msda_desc *d, const void *value, const void *sampling_locations,
+                         const void *attention_weights, const void *grad_output, void *grad_value,
+                         void *grad_sampling_locations, void *grad_attention_weights, void *workspace,
+                         size_t workspace_bytes, void *stream) {
+  clear_error();
+  return samp_entry(
+      kMsda, d, true, workspace, workspace_bytes,
+      [&] {
+        const size_t cs = dtype_bytes(d->coord_dtype);
+        return check_args({{value, "value", 16}, {sampling_locations, "sampling_locations", cs},
+                           {attention_weights, "attention_weights", cs}, {grad_output, "grad_output", 16},
+                           {grad_sampling_locations, "grad_sampling_locations", cs},
+                           {grad_attention_weights, "grad_attention_weights", cs},
+                           {grad_value, "grad_value", 16, !(d->flags & MDCONV_FLAG_NO_GRAD_INPUT)}});
+      },
+      [&](const MsdaPlan &p) {
+        MsdaTensors t = {};
+        t.value = value; t.loc = sampling_locations; t.attn = attention_weights; t.grad_output = grad_output;
+        t.grad_value = grad_value; t.grad_loc = grad_sampling_locations; t.grad_attn = grad_attention_weights;
+        return msda_backward(p, t, workspace, (hipStream_t)stream);
+      });
+}
+
+}  // extern "C"

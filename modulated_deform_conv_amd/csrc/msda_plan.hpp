@@ -36,20 +36,11 @@ struct MsdaPlan {
   size_t total;             // workspace bytes
 };
 
-// false: outside the shape rule; *why names the rule it breaks.  The descriptor has passed validation (mdconv_api.hip).
+// false: outside the shape rule; *why names the rule it breaks.  The descriptor has passed validation (the operator's *_host.hip).
 bool msda_plan(const mdconv_msda_desc *d, bool backward, MsdaPlan *p, const char **why);
 int msda_forward(const MsdaPlan &p, const MsdaTensors &t, hipStream_t stream);
 int msda_backward(const MsdaPlan &p, const MsdaTensors &t, void *ws, hipStream_t stream);
 
-// the five (value type, coordinate type) pairings: `call(DT, CT)` for the plan's
-#define MSDA_DISPATCH(p, call)                                                       \
-  do {                                                                               \
-    if ((p).dtype == MDCONV_F32) call(MDCONV_F32, MDCONV_F32);                       \
-    else if ((p).dtype == MDCONV_F16 && (p).coord_dtype == MDCONV_F16) call(MDCONV_F16, MDCONV_F16); \
-    else if ((p).dtype == MDCONV_F16) call(MDCONV_F16, MDCONV_F32);                  \
-    else if ((p).coord_dtype == MDCONV_BF16) call(MDCONV_BF16, MDCONV_BF16);         \
-    else call(MDCONV_BF16, MDCONV_F32);                                              \
-  } while (0)
 
 #ifdef __HIPCC__
 // The operator policy of the sampling core: coord = sampling_locations, factor = attention_weights, sampled tensor = value.

@@ -67,6 +67,25 @@ struct SampGather {
 };
 int samp_gather_launch(const SampGather &ga, int dtype, int64_t seg_stride, const void *grad_output, const int *rowptr,
                        const void *entries, void *grad_in, hipStream_t stream);
+// The backward tail of the families that gather channels-last: the lists into the workspace (scatter_lists_build with the
+// family's list kernel, `launch_list`), then the gather over them.
+template <class Launch>
+static int samp_lists_gather(const ScatterLists &L, void *ws, bool det, const SampGather &ga, int dtype, const void *grad_output,
+                             void *grad_in, hipStream_t stream, Launch launch_list) {
+  if (int rc = scatter_lists_build(L, ws, det, stream, launch_list)) return rc;
+  return samp_gather_launch(ga, dtype, L.seg_stride, grad_output, (const int *)((char *)ws + L.off_rowptr),
+                            (char *)ws + L.off_entries, grad_in, stream);
+}
+
+// the five (value type, coordinate type) pairings of a sampling operator: `call(DT, CT)` for the plan's
+#define SAMP_DISPATCH(p, call)                                                       \
+  do {                                                                               \
+    if ((p).dtype == MDCONV_F32) call(MDCONV_F32, MDCONV_F32);                       \
+    else if ((p).dtype == MDCONV_F16 && (p).coord_dtype == MDCONV_F16) call(MDCONV_F16, MDCONV_F16); \
+    else if ((p).dtype == MDCONV_F16) call(MDCONV_F16, MDCONV_F32);                  \
+    else if ((p).coord_dtype == MDCONV_BF16) call(MDCONV_BF16, MDCONV_BF16);         \
+    else call(MDCONV_BF16, MDCONV_F32);                                              \
+  } while (0)
 
 #ifdef __HIPCC__
 constexpr int kSampOob = 0x7ffffff0;   // out-of-range buffer offset: loads give 0 (every tensor is below 2^31 bytes)

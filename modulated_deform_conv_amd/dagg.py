@@ -13,18 +13,18 @@ extents), ``sampling_location [B, A, P, cams, 2]`` ((x, y), normalised), ``weigh
 coordinate tensors have its dtype or are fp32.  CPU tensors raise ``NotImplementedError``: there is no CPU or PyTorch
 fallback.  There is no ``nn.Module``: the published module wraps camera projection and anchor encoding, which is model code.
 """
-import ctypes
+import functools
 
 import torch
 from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
-from . import _capi
+from . import _capi, _samp
+from ._samp import DTYPES as _DTYPES, ptr as _ptr
 
 __all__ = ["deformable_aggregation_forward", "deformable_aggregation_backward", "DeformableAggregationFunction",
            "deformable_aggregation", "feature_maps_format"]
 
-_DTYPES = {torch.float32: _capi.F32, torch.float16: _capi.F16, torch.bfloat16: _capi.BF16}
 _SAME_EXTENTS = "every camera must have the same level extents (H_l, W_l)"
 
 
@@ -55,10 +55,7 @@ def _check_starts(shapes, cams, scale_start_index):
         return
     got = scale_start_index.tolist() if isinstance(scale_start_index, torch.Tensor) else list(scale_start_index)
     got = [int(v) for row in got for v in (row if isinstance(row, (list, tuple)) else [row])]
-    starts, s = [], 0
-    for h, w in shapes:
-        starts.append(s)
-        s += h * w
+    starts, s = _samp.level_starts(shapes)
     want = [c * s + st for c in range(cams) for st in starts]
     if got != want and got != starts:
         raise ValueError("dagg: scale_start_index %s is not the cumulative sum %s of spatial_shape over cameras and levels" % (
@@ -108,22 +105,9 @@ def _check(d, shapes, feature, loc, weights, **others):
     return (B, A, C)
 
 
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr() if t is not None else 0)
-
-
-def _run(fn_name, d, backward, args_before_ws, input):
-    L = _capi.lib()
-    if not hasattr(L, "mdconv_dagg_workspace_bytes"):
-        raise RuntimeError("this build of libmdconv_hip.so has no deformable aggregation (mdconv_dagg_*)")
-    with torch.cuda.device(input.device):
-        ws_bytes = L.mdconv_dagg_workspace_bytes(ctypes.byref(d), int(backward))
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=input.device) if ws_bytes else None
-        stream = torch.cuda.current_stream().cuda_stream
-        rc = getattr(L, fn_name)(ctypes.byref(d), *args_before_ws, ctypes.c_void_p(ws.data_ptr() if ws is not None else 0),
-                                 ctypes.c_size_t(ws_bytes), ctypes.c_void_p(stream))
-    if rc != 0:
-        raise RuntimeError("%s failed (%d): %s" % (fn_name, rc, _capi.last_error()))
+# the call itself (the seam the tests replace): workspace query, allocation, current stream, call, RuntimeError
+_run = functools.partial(_samp.run, "mdconv_dagg",
+                         missing_msg="this build of libmdconv_hip.so has no deformable aggregation (mdconv_dagg_*)")
 
 
 def deformable_aggregation_forward(feature, spatial_shape, sampling_location, weights, output=None):
@@ -151,8 +135,7 @@ def deformable_aggregation_backward(feature, spatial_shape, sampling_location, w
     follows ``_capi.deterministic_mode()``.  ``accumulate`` false with ``grads``: the caller's buffers are overwritten
     instead.  Returns the three gradients in that order."""
     shapes = _shapes(spatial_shape)
-    det = _capi.deterministic_mode() if deterministic is None else bool(deterministic)
-    flags = (_capi.FLAG_DETERMINISTIC if det else 0) | (0 if need_grad_feature else _capi.FLAG_NO_GRAD_INPUT)
+    flags = _samp.backward_flags(deterministic, need_grad_feature)
     d = _desc(feature, sampling_location, weights, shapes,
               accumulate=int(grads is not None if accumulate is None else bool(accumulate)), flags=flags)
     _check(d, shapes, feature, sampling_location, weights, grad_output=grad_output)
@@ -166,12 +149,8 @@ def deformable_aggregation_backward(feature, spatial_shape, sampling_location, w
         grads = (torch.empty_like(feature) if need_grad_feature else None, torch.empty_like(sampling_location),
                  torch.empty_like(weights))
     gf, gl, gw = grads
-    for name, g, like in (("grad_feature", gf, feature), ("grad_sampling_location", gl, sampling_location),
-                          ("grad_weights", gw, weights)):
-        if g is None and name == "grad_feature" and not need_grad_feature:
-            continue
-        if g is None or g.shape != like.shape or g.dtype != like.dtype or g.device != like.device or not g.is_contiguous():
-            raise ValueError("dagg: %s must be a dense tensor of the shape, dtype and device of its forward tensor" % name)
+    _samp.check_grads("dagg", (("grad_feature", gf, feature), ("grad_sampling_location", gl, sampling_location), ("grad_weights", gw, weights)),
+                      may_be_none=() if need_grad_feature else ("grad_feature",))
     _run("mdconv_dagg_backward", d, True,
          [_ptr(feature), _ptr(sampling_location), _ptr(weights), _ptr(grad_output), _ptr(gf if need_grad_feature else None),
           _ptr(gl), _ptr(gw)], feature)
@@ -200,7 +179,7 @@ class DeformableAggregationFunction(Function):
         if mc_ms_feat.is_cuda and torch.is_autocast_enabled("cuda"):
             mc_ms_feat = mc_ms_feat.to(torch.get_autocast_dtype("cuda"))
         # one dtype for the two coordinate tensors: fp32 if either is (or if they disagree), else the feature's
-        cdt = mc_ms_feat.dtype if sampling_location.dtype == weights.dtype == mc_ms_feat.dtype else torch.float32
+        cdt = _samp.coord_dtype(mc_ms_feat.dtype, sampling_location.dtype, weights.dtype)
         mc_ms_feat = mc_ms_feat.contiguous()
         sampling_location = sampling_location.to(cdt).contiguous()
         weights = weights.to(cdt).contiguous()
@@ -218,7 +197,7 @@ class DeformableAggregationFunction(Function):
         # selective backward: grad_feature is neither computed nor allocated when the feature needs no gradient
         gf, gl, gw = deformable_aggregation_backward(feature, ctx.shapes, loc, weights, grad_output,
                                                      need_grad_feature=bool(ctx.needs_input_grad[0]), deterministic=None)
-        back = lambda g, dt: g if g is None or g.dtype == dt else g.to(dt)
+        back = _samp.back
         df, dl, dw = ctx.in_dtypes
         return back(gf, df), None, None, back(gl, dl), back(gw, dw)
 
@@ -239,10 +218,7 @@ def feature_maps_format(feature_maps):
     shapes = [(int(m.shape[3]), int(m.shape[4])) for m in feature_maps]
     feature = torch.cat([m.permute(0, 1, 3, 4, 2).reshape(B, cams, h * w, C) for m, (h, w) in zip(feature_maps, shapes)], 2)
     s_cam = int(feature.shape[2])
-    starts, s = [], 0
-    for h, w in shapes:
-        starts.append(s)
-        s += h * w
+    starts, _ = _samp.level_starts(shapes)
     spatial_shape = torch.tensor([shapes] * cams, dtype=torch.int64)
     scale_start_index = torch.tensor([[c * s_cam + st for st in starts] for c in range(cams)], dtype=torch.int64)
     return feature.reshape(B, cams * s_cam, C).contiguous(), spatial_shape, scale_start_index

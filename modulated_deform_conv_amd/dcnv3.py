@@ -12,6 +12,7 @@ The operator has no weight: ``input [B, H, W, G*D]``, ``offset [B, Ho, Wo, G*K*2
 ``NotImplementedError``: there is no CPU or PyTorch fallback.
 """
 import ctypes
+import functools
 
 import torch
 import torch.nn as nn
@@ -21,11 +22,11 @@ from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 from torch.nn.modules.utils import _pair
 
-from . import _capi
+from . import _capi, _samp
+from ._samp import DTYPES as _DTYPES, ptr as _ptr
 
 __all__ = ["DCNv3Function", "dcnv3_core", "DCNv3", "DCNv3Fused"]
 
-_DTYPES = {torch.float32: _capi.F32, torch.float16: _capi.F16, torch.bfloat16: _capi.BF16}
 
 
 def _desc(input, kernel, stride, pad, dilation, group, group_channels, offset_scale, accumulate=1, flags=0):
@@ -68,20 +69,8 @@ def _check(d, input, offset, mask, **others):
     return (d.batch, ho, wo, d.groups * d.group_channels)
 
 
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr() if t is not None else 0)
-
-
-def _run(fn_name, d, backward, args_before_ws, input):
-    L = _capi.lib()
-    with torch.cuda.device(input.device):
-        ws_bytes = L.mdconv_dcnv3_workspace_bytes(ctypes.byref(d), int(backward))
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=input.device) if ws_bytes else None
-        stream = torch.cuda.current_stream().cuda_stream
-        rc = getattr(L, fn_name)(ctypes.byref(d), *args_before_ws, ctypes.c_void_p(ws.data_ptr() if ws is not None else 0),
-                                 ctypes.c_size_t(ws_bytes), ctypes.c_void_p(stream))
-    if rc != 0:
-        raise RuntimeError("%s failed (%d): %s" % (fn_name, rc, _capi.last_error()))
+# the call itself (the seam the tests replace): workspace query, allocation, current stream, call, RuntimeError
+_run = functools.partial(_samp.run, "mdconv_dcnv3")
 
 
 def dcnv3_forward(input, offset, mask, kernel, stride, pad, dilation, group, group_channels, offset_scale, output=None):
@@ -109,8 +98,7 @@ def dcnv3_backward(input, offset, mask, grad_output, kernel, stride, pad, dilati
     Returns (grad_input | None, grad_offset, grad_mask)."""
     if not input.is_cuda:
         raise NotImplementedError
-    det = _capi.deterministic_mode() if deterministic is None else bool(deterministic)
-    flags = (_capi.FLAG_DETERMINISTIC if det else 0) | (0 if need_grad_input else _capi.FLAG_NO_GRAD_INPUT)
+    flags = _samp.backward_flags(deterministic, need_grad_input)
     d = _desc(input, kernel, stride, pad, dilation, group, group_channels, offset_scale,
               accumulate=int(grads is not None if accumulate is None else bool(accumulate)), flags=flags)
     _check(d, input, offset, mask, grad_output=grad_output)
@@ -121,11 +109,8 @@ def dcnv3_backward(input, offset, mask, grad_output, kernel, stride, pad, dilati
     if grads is None:
         grads = (torch.empty_like(input) if need_grad_input else None, torch.empty_like(offset), torch.empty_like(mask))
     gi, goff, gm = grads
-    for name, g, like in (("grad_input", gi, input), ("grad_offset", goff, offset), ("grad_mask", gm, mask)):
-        if g is None and name == "grad_input" and not need_grad_input:
-            continue
-        if g is None or g.shape != like.shape or g.dtype != like.dtype or g.device != like.device or not g.is_contiguous():
-            raise ValueError("dcnv3: %s must be a dense tensor of the shape, dtype and device of its forward tensor" % name)
+    _samp.check_grads("dcnv3", (("grad_input", gi, input), ("grad_offset", goff, offset), ("grad_mask", gm, mask)),
+                      may_be_none=() if need_grad_input else ("grad_input",))
     _run("mdconv_dcnv3_backward", d, True,
          [_ptr(input), _ptr(offset), _ptr(mask), _ptr(grad_output), _ptr(gi if need_grad_input else None), _ptr(goff), _ptr(gm)],
          input)
@@ -167,7 +152,7 @@ class DCNv3Function(Function):
             grad_output = grad_output.to(input.dtype)
         # selective backward: grad_input is neither computed nor allocated when `input` needs no gradient
         grads = dcnv3_backward(input, offset, mask, grad_output, *ctx.geo, need_grad_input=bool(ctx.needs_input_grad[0]))
-        back = lambda g, dt: g if g is None or g.dtype == dt else g.to(dt)
+        back = _samp.back
         return tuple(back(g, dt) for g, dt in zip(grads, ctx.in_dtypes)) + (None,) * 12
 
 

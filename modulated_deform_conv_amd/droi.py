@@ -11,19 +11,19 @@ The entry points take ``input [B, H, W, C]``, ``rois [R, 5]`` (fp32: batch index
 (plane 0 = x, plane 1 = y; or None) and give ``output [R, PH, PW, C]``.  ``input`` is fp32 / fp16 / bf16; ``offset`` has its
 dtype or is fp32.  CPU tensors raise ``NotImplementedError``: there is no CPU or PyTorch fallback.
 """
-import ctypes
+import functools
 
 import torch
 import torch.nn as nn
 from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
-from . import _capi
+from . import _capi, _samp
+from ._samp import DTYPES as _DTYPES, ptr as _ptr
 
 __all__ = ["deform_roi_pool_forward", "deform_roi_pool_backward", "DeformRoIPoolFunction", "deform_roi_pool", "DeformRoIPool",
            "DeformRoIPoolPack", "ModulatedDeformRoIPoolPack"]
 
-_DTYPES = {torch.float32: _capi.F32, torch.float16: _capi.F16, torch.bfloat16: _capi.BF16}
 
 
 def _pair(v):
@@ -71,22 +71,9 @@ def _check(d, input, rois, offset, **others):
     return (R, PH, PW, d.channels)
 
 
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr() if t is not None else 0)
-
-
-def _run(fn_name, d, backward, args_before_ws, input):
-    L = _capi.lib()
-    if not hasattr(L, "mdconv_droi_workspace_bytes"):
-        raise RuntimeError("the loaded libmdconv_hip.so has no deformable RoI pooling (built before it existed)")
-    with torch.cuda.device(input.device):
-        ws_bytes = L.mdconv_droi_workspace_bytes(ctypes.byref(d), int(backward))
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=input.device) if ws_bytes else None
-        stream = torch.cuda.current_stream().cuda_stream
-        rc = getattr(L, fn_name)(ctypes.byref(d), *args_before_ws, ctypes.c_void_p(ws.data_ptr() if ws is not None else 0),
-                                 ctypes.c_size_t(ws_bytes), ctypes.c_void_p(stream))
-    if rc != 0:
-        raise RuntimeError("%s failed (%d): %s" % (fn_name, rc, _capi.last_error()))
+# the call itself (the seam the tests replace): workspace query, allocation, current stream, call, RuntimeError
+_run = functools.partial(_samp.run, "mdconv_droi",
+                         missing_msg="the loaded libmdconv_hip.so has no deformable RoI pooling (built before it existed)")
 
 
 def deform_roi_pool_forward(input, rois, offset, output_size, spatial_scale=1.0, sampling_ratio=0, gamma=0.1, max_grid=8,
@@ -116,8 +103,7 @@ def deform_roi_pool_backward(input, rois, offset, grad_output, output_size, spat
     buffers are overwritten instead.  Returns the two gradients in that order; ``rois`` have none."""
     if not input.is_cuda:
         raise NotImplementedError
-    det = _capi.deterministic_mode() if deterministic is None else bool(deterministic)
-    flags = (_capi.FLAG_DETERMINISTIC if det else 0) | (0 if need_grad_input else _capi.FLAG_NO_GRAD_INPUT)
+    flags = _samp.backward_flags(deterministic, need_grad_input)
     d = _desc(input, rois, offset, output_size, spatial_scale, sampling_ratio, gamma, max_grid,
               accumulate=int(grads is not None if accumulate is None else bool(accumulate)), flags=flags)
     _check(d, input, rois, offset, grad_output=grad_output)
@@ -128,11 +114,8 @@ def deform_roi_pool_backward(input, rois, offset, grad_output, output_size, spat
     if grads is None:
         grads = (torch.empty_like(input) if need_grad_input else None, None if offset is None else torch.empty_like(offset))
     gi, go = grads
-    for name, g, like, needed in (("grad_input", gi, input, need_grad_input), ("grad_offset", go, offset, offset is not None)):
-        if not needed:
-            continue
-        if g is None or g.shape != like.shape or g.dtype != like.dtype or g.device != like.device or not g.is_contiguous():
-            raise ValueError("droi: %s must be a dense tensor of the shape, dtype and device of its forward tensor" % name)
+    _samp.check_grads("droi", [(name, g, like) for name, g, like, needed in (
+        ("grad_input", gi, input, need_grad_input), ("grad_offset", go, offset, offset is not None)) if needed])
     _run("mdconv_droi_backward", d, True,
          [_ptr(input), _ptr(rois), _ptr(offset), _ptr(grad_output), _ptr(gi if need_grad_input else None),
           _ptr(go if offset is not None else None)], input)
@@ -184,7 +167,7 @@ class DeformRoIPoolFunction(Function):
             g = grad_output.to(cl.dtype).permute(0, 2, 3, 1).contiguous()
             # selective backward: grad_input is neither computed nor allocated when `input` needs no gradient
             gi, go = deform_roi_pool_backward(cl, rois, offset, g, *ctx.args, need_grad_input=need_gi)
-        back = lambda t, dt: t if t is None or t.dtype == dt else t.to(dt)
+        back = _samp.back
         di, do = ctx.in_dtypes
         gi = None if gi is None else back(gi, di).permute(0, 3, 1, 2)
         return gi, None, (back(go, do) if need_go else None), None, None, None, None, None

@@ -13,19 +13,19 @@ contract and what is unpinned).
 tap 0 .. L*P-1, normalised, then the L*P logits; tap = l*P + p) -> ``output [N, Lq, M*D]``.  ``value`` is fp32 / fp16 / bf16;
 the packed tensor has its dtype or is fp32.  CPU tensors raise ``NotImplementedError``: there is no CPU or PyTorch fallback.
 """
-import ctypes
+import functools
 
 import torch
 from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
-from . import _capi
-from .msda import MSDeformAttn, _check_starts, _ptr, _shapes
+from . import _capi, _samp
+from ._samp import DTYPES as _DTYPES, ptr as _ptr
+from .msda import MSDeformAttn, _check_starts, _shapes
 
 __all__ = ["flash_deform_attn_forward", "flash_deform_attn_backward", "FlashDeformAttnFunction", "flash_deform_attn",
            "FlashDeformAttn", "pack_loc_attn", "unpack_loc_attn"]
 
-_DTYPES = {torch.float32: _capi.F32, torch.float16: _capi.F16, torch.bfloat16: _capi.BF16}
 
 
 def pack_loc_attn(sampling_locations, attention_logits):
@@ -86,16 +86,8 @@ def _check(d, shapes, value, loc_attn, **others):
     return (N, Lq, M * D)
 
 
-def _run(fn_name, d, backward, args_before_ws, input):
-    L = _capi.lib()
-    with torch.cuda.device(input.device):
-        ws_bytes = L.mdconv_fda_workspace_bytes(ctypes.byref(d), int(backward))
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=input.device) if ws_bytes else None
-        stream = torch.cuda.current_stream().cuda_stream
-        rc = getattr(L, fn_name)(ctypes.byref(d), *args_before_ws, ctypes.c_void_p(ws.data_ptr() if ws is not None else 0),
-                                 ctypes.c_size_t(ws_bytes), ctypes.c_void_p(stream))
-    if rc != 0:
-        raise RuntimeError("%s failed (%d): %s" % (fn_name, rc, _capi.last_error()))
+# the call itself (the seam the tests replace): workspace query, allocation, current stream, call, RuntimeError
+_run = functools.partial(_samp.run, "mdconv_fda")
 
 
 def flash_deform_attn_forward(value, spatial_shapes, sampling_loc_attn, points, output=None):
@@ -126,8 +118,7 @@ def flash_deform_attn_backward(value, spatial_shapes, sampling_loc_attn, points,
     if not value.is_cuda:
         raise NotImplementedError
     shapes = _shapes(spatial_shapes)
-    det = _capi.deterministic_mode() if deterministic is None else bool(deterministic)
-    flags = (_capi.FLAG_DETERMINISTIC if det else 0) | (0 if need_grad_value else _capi.FLAG_NO_GRAD_INPUT)
+    flags = _samp.backward_flags(deterministic, need_grad_value)
     d = _desc(value, sampling_loc_attn, shapes, points, accumulate=int(grads is not None and bool(accumulate)), flags=flags)
     _check(d, shapes, value, sampling_loc_attn, grad_output=grad_output)
     # pointer classes (include/mdconv.h): value, grad_output and grad_value are "16-byte", sampling_loc_attn and its gradient "element"
@@ -137,11 +128,8 @@ def flash_deform_attn_backward(value, spatial_shapes, sampling_loc_attn, points,
     if grads is None:
         grads = (torch.empty_like(value) if need_grad_value else None, torch.empty_like(sampling_loc_attn))
     gv, gla = grads
-    for name, g, like in (("grad_value", gv, value), ("grad_sampling_loc_attn", gla, sampling_loc_attn)):
-        if g is None and name == "grad_value" and not need_grad_value:
-            continue
-        if g is None or g.shape != like.shape or g.dtype != like.dtype or g.device != like.device or not g.is_contiguous():
-            raise ValueError("fda: %s must be a dense tensor of the shape, dtype and device of its forward tensor" % name)
+    _samp.check_grads("fda", (("grad_value", gv, value), ("grad_sampling_loc_attn", gla, sampling_loc_attn)),
+                      may_be_none=() if need_grad_value else ("grad_value",))
     _run("mdconv_fda_backward", d, True,
          [_ptr(value), _ptr(sampling_loc_attn), _ptr(grad_output), _ptr(gv if need_grad_value else None), _ptr(gla)], value)
     return (gv if need_grad_value else None), gla
@@ -168,7 +156,7 @@ class FlashDeformAttnFunction(Function):
         ctx.in_dtypes = (value.dtype, sampling_loc_attn.dtype)
         if torch.is_autocast_enabled("cuda"):
             value = value.to(torch.get_autocast_dtype("cuda"))
-        cdt = value.dtype if sampling_loc_attn.dtype == value.dtype else torch.float32
+        cdt = _samp.coord_dtype(value.dtype, sampling_loc_attn.dtype)
         value = value.contiguous()
         sampling_loc_attn = sampling_loc_attn.to(cdt).contiguous()
         if any(ctx.needs_input_grad):
@@ -185,7 +173,7 @@ class FlashDeformAttnFunction(Function):
         # selective backward: grad_value is neither computed nor allocated when `value` needs no gradient
         gv, gla = flash_deform_attn_backward(value, ctx.shapes, loc_attn, ctx.points, grad_output,
                                              need_grad_value=bool(ctx.needs_input_grad[0]))
-        back = lambda g, dt: g if g is None or g.dtype == dt else g.to(dt)
+        back = _samp.back
         dv, dla = ctx.in_dtypes
         return back(gv, dv), None, None, (back(gla, dla) if ctx.needs_input_grad[3] else None), None, None
 

@@ -12,7 +12,7 @@ contract and what is unpinned).
 (T, H, W).  ``value`` is fp32 / fp16 / bf16; the two coordinate tensors have its dtype or are fp32.  CPU tensors raise
 ``NotImplementedError``: there is no CPU or PyTorch fallback.
 """
-import ctypes
+import functools
 
 import torch
 import torch.nn as nn
@@ -20,12 +20,12 @@ import torch.nn.functional as F
 from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
-from . import _capi
+from . import _capi, _samp
+from ._samp import DTYPES as _DTYPES, ptr as _ptr
 
 __all__ = ["ms_deform_attn_3d_forward", "ms_deform_attn_3d_backward", "MSDeformAttn3DFunction", "ms_deform_attn_3d",
            "MSDeformAttn3D"]
 
-_DTYPES = {torch.float32: _capi.F32, torch.float16: _capi.F16, torch.bfloat16: _capi.BF16}
 
 
 def _shapes(spatial_shapes):
@@ -45,10 +45,7 @@ def _check_starts(shapes, level_start_index):
     if level_start_index is None or (isinstance(level_start_index, torch.Tensor) and level_start_index.is_cuda):
         return
     got = [int(v) for v in (level_start_index.tolist() if isinstance(level_start_index, torch.Tensor) else level_start_index)]
-    want, s = [], 0
-    for t, h, w in shapes:
-        want.append(s)
-        s += t * h * w
+    want, _ = _samp.level_starts(shapes)
     if got != want:
         raise ValueError("msda3d: level_start_index %s is not the cumulative sum %s of spatial_shapes" % (got, want))
 
@@ -92,20 +89,8 @@ def _check(d, shapes, value, loc, attn, **others):
     return (N, Lq, M * D)
 
 
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr() if t is not None else 0)
-
-
-def _run(fn_name, d, backward, args_before_ws, input):
-    L = _capi.lib()
-    with torch.cuda.device(input.device):
-        ws_bytes = L.mdconv_msda3d_workspace_bytes(ctypes.byref(d), int(backward))
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=input.device) if ws_bytes else None
-        stream = torch.cuda.current_stream().cuda_stream
-        rc = getattr(L, fn_name)(ctypes.byref(d), *args_before_ws, ctypes.c_void_p(ws.data_ptr() if ws is not None else 0),
-                                 ctypes.c_size_t(ws_bytes), ctypes.c_void_p(stream))
-    if rc != 0:
-        raise RuntimeError("%s failed (%d): %s" % (fn_name, rc, _capi.last_error()))
+# the call itself (the seam the tests replace): workspace query, allocation, current stream, call, RuntimeError
+_run = functools.partial(_samp.run, "mdconv_msda3d")
 
 
 def ms_deform_attn_3d_forward(value, spatial_shapes, sampling_locations, attention_weights, output=None):
@@ -136,8 +121,7 @@ def ms_deform_attn_3d_backward(value, spatial_shapes, sampling_locations, attent
     if not value.is_cuda:
         raise NotImplementedError
     shapes = _shapes(spatial_shapes)
-    det = _capi.deterministic_mode() if deterministic is None else bool(deterministic)
-    flags = (_capi.FLAG_DETERMINISTIC if det else 0) | (0 if need_grad_value else _capi.FLAG_NO_GRAD_INPUT)
+    flags = _samp.backward_flags(deterministic, need_grad_value)
     d = _desc(value, sampling_locations, shapes,
               accumulate=int(grads is not None if accumulate is None else bool(accumulate)), flags=flags)
     _check(d, shapes, value, sampling_locations, attention_weights, grad_output=grad_output)
@@ -149,12 +133,8 @@ def ms_deform_attn_3d_backward(value, spatial_shapes, sampling_locations, attent
         grads = (torch.empty_like(value) if need_grad_value else None, torch.empty_like(sampling_locations),
                  torch.empty_like(attention_weights))
     gv, gl, ga = grads
-    for name, g, like in (("grad_value", gv, value), ("grad_sampling_locations", gl, sampling_locations),
-                          ("grad_attention_weights", ga, attention_weights)):
-        if g is None and name == "grad_value" and not need_grad_value:
-            continue
-        if g is None or g.shape != like.shape or g.dtype != like.dtype or g.device != like.device or not g.is_contiguous():
-            raise ValueError("msda3d: %s must be a dense tensor of the shape, dtype and device of its forward tensor" % name)
+    _samp.check_grads("msda3d", (("grad_value", gv, value), ("grad_sampling_locations", gl, sampling_locations), ("grad_attention_weights", ga, attention_weights)),
+                      may_be_none=() if need_grad_value else ("grad_value",))
     _run("mdconv_msda3d_backward", d, True,
          [_ptr(value), _ptr(sampling_locations), _ptr(attention_weights), _ptr(grad_output),
           _ptr(gv if need_grad_value else None), _ptr(gl), _ptr(ga)], value)
@@ -181,7 +161,7 @@ class MSDeformAttn3DFunction(Function):
         if torch.is_autocast_enabled("cuda"):
             value = value.to(torch.get_autocast_dtype("cuda"))
         # one dtype for the two coordinate tensors: fp32 if either is (or if they disagree), else value's
-        cdt = value.dtype if sampling_locations.dtype == attention_weights.dtype == value.dtype else torch.float32
+        cdt = _samp.coord_dtype(value.dtype, sampling_locations.dtype, attention_weights.dtype)
         value = value.contiguous()
         sampling_locations = sampling_locations.to(cdt).contiguous()
         attention_weights = attention_weights.to(cdt).contiguous()
@@ -199,7 +179,7 @@ class MSDeformAttn3DFunction(Function):
         # selective backward: grad_value is neither computed nor allocated when `value` needs no gradient
         gv, gl, ga = ms_deform_attn_3d_backward(value, ctx.shapes, loc, attn, grad_output,
                                                 need_grad_value=bool(ctx.needs_input_grad[0]), deterministic=None)
-        back = lambda g, dt: g if g is None or g.dtype == dt else g.to(dt)
+        back = _samp.back
         dv, dl, da = ctx.in_dtypes
         return back(gv, dv), None, None, back(gl, dl), back(ga, da), None
 
