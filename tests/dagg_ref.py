@@ -165,7 +165,20 @@ CASES = {
     "many_taps": dict(B=1, A=2, P=13, cams=6, shapes=[(8, 22), (4, 11), (2, 6), (1, 3)], G=2, Dg=4),
     # every gated-in sample of level 0 lands in one cell: four long lists per camera, empty rows elsewhere
     "crafted": dict(B=2, A=20, P=3, cams=2, shapes=[(4, 4), (2, 2)], G=2, Dg=4),
+    # three groups of 3 vectors (fp32; 16-bit: Dg = 24) in 16 lanes: the masked butterfly inside ONE round, VG no power of two
+    "odd_group": dict(B=1, A=5, P=2, cams=2, shapes=[(3, 4)], G=3, Dg=12),
+    "odd_group_16bit": dict(B=1, A=5, P=2, cams=2, shapes=[(3, 4)], G=3, Dg=24),
+    # eight groups of 24 vectors in three rounds: rounds 0 and 1 hold whole groups and end inside one; round 1 begins with a tail
+    "carry_and_whole_groups": dict(B=1, A=3, P=2, cams=2, shapes=[(3, 4)], G=8, Dg=96),
+    # one group of 128 vectors, wider than a round: the carried sum is consumed exactly at the second round's end
+    "group_fills_two_rounds": dict(B=1, A=4, P=2, cams=2, shapes=[(3, 4)], G=1, Dg=512),
+    # two groups of 64 vectors, VG = VL: the segmented butterfly over a whole round, one group per round
+    "group_per_round": dict(B=1, A=4, P=2, cams=2, shapes=[(3, 4)], G=2, Dg=256),
 }
+# the four cases above: the (seg, rounds) of DaggGeom each one claims in fp32 (tests/test_dagg_cpu.py asserts them and the
+# round boundaries from the lane geometry)
+GROUP_CASES = {"odd_group": (0, 1), "odd_group_16bit": (0, 1), "carry_and_whole_groups": (0, 3), "group_fills_two_rounds": (0, 2),
+               "group_per_round": (1, 2)}
 CRAFTED_XY = ((1.3 + 0.5) / 4, (1.4 + 0.5) / 4)   # pixel (1.3, 1.4) of level 0, (0.4, 0.45) of level 1
 CRAFTED_ROWS = [cam * 20 + r for cam in (0, 1) for r in (5, 6, 9, 10)]
 CRAFTED_EMPTY = [cam * 20 + r for cam in (0, 1) for r in (0, 1, 2, 3, 4, 7, 8, 11, 12, 13, 14, 15)]

@@ -1,7 +1,8 @@
-"""One table of the six channels-last sampling operators -- DCNv3, DCNv4 (plain and ``softmax=``), multi-scale deformable
-attention, packed attention, 3-D attention and deformable RoI pooling -- adapted to a common shape, and the case lists of
-tests/test_gpu_samp_fuzz.py, tests/test_gpu_samp_scale.py and tests/test_gpu_samp_nonfinite.py.  Importable without a GPU:
-tests/test_samp_cases_cpu.py checks, from the reference geometry alone, that every case is what it claims.
+"""One table of the seven channels-last sampling operators -- DCNv3, DCNv4 (plain and ``softmax=``), multi-scale deformable
+attention, packed attention, 3-D attention, deformable RoI pooling and deformable aggregation -- adapted to a common shape,
+and the case lists of tests/test_gpu_samp_fuzz.py, tests/test_gpu_samp_scale.py and tests/test_gpu_samp_nonfinite.py.
+Importable without a GPU: tests/test_samp_cases_cpu.py checks, from the reference geometry alone, that every case is what it
+claims.
 
 An operator entry (``OPS[name]``) holds: ``draw(spec, dtype, coord_dtype, seed)`` -> ``(t, geo)`` -- the CPU tensors of a call,
 ``grad_output`` last, and the call's static arguments --, ``native(t, geo, ...)`` (the forward and backward entry points,
@@ -15,6 +16,7 @@ import random
 
 import torch
 
+from tests import dagg_ref as RG
 from tests import dcnv3_ref as R3
 from tests import dcnv4_ref as R4
 from tests import dcnv4_softmax_ref as R4S
@@ -34,6 +36,7 @@ K_SORT_ROWS = 64      # kRowsPerChunk (csr_sort.hip)
 K_KEY_BLOCK = 2048    # kKeyBlock (csr_sort.hip)
 MAX_SEGMENTS = 65535  # the grid.y limit of the scan, the operators' shape rule
 LIMIT = 1 << 31       # "every tensor is below 2^31 bytes"
+FUZZ_V = (1, 2, 3, 4, 5, 8, 16)   # vectors per head of a random shape: V = 1, odd V, V = 5 in eight lanes, VL = 16
 
 
 def esize(dtype):
@@ -88,6 +91,7 @@ def _call_kw(grads, deterministic, accumulate):
 class Dcnv3:
     name, kinds, pairings, plain_factor, naxes = "dcnv3", "vvcc", SAME_TYPE, True, 2
     names = ("output", "grad_input", "grad_offset", "grad_mask")
+    fuzz_V = FUZZ_V   # the V a random shape of the operator may have (test_fuzz_draw)
     far = -1e4   # px
 
     @staticmethod
@@ -161,6 +165,7 @@ class Dcnv3:
 class Dcnv4:
     name, kinds, pairings, plain_factor, naxes, softmax = "dcnv4", "vvc", PAIRINGS, True, 2, False
     names = ("output", "grad_input", "grad_offset_mask")
+    fuzz_V = FUZZ_V
 
     @staticmethod
     def draw(spec, dtype, coord_dtype, seed):
@@ -230,6 +235,7 @@ class Dcnv4Softmax(Dcnv4):
 class Msda:
     name, kinds, pairings, plain_factor, naxes = "msda", "vvcc", PAIRINGS, True, 2
     names = ("output", "grad_value", "grad_sampling_locations", "grad_attention_weights")
+    fuzz_V = FUZZ_V
     R = RA
 
     @classmethod
@@ -390,6 +396,7 @@ class Fda(Msda):
 class Droi:
     name, kinds, pairings, plain_factor, naxes = "droi", "vvc", PAIRINGS, True, 2
     names = ("output", "grad_input", "grad_offset")
+    fuzz_V = FUZZ_V
     gate = None   # the reference module has no gate_of: RoIAlign's gate is closed, -1 <= loc <= size, inside droi_explicit
 
     @staticmethod
@@ -467,7 +474,92 @@ class Droi:
         return -1e4   # times gamma * (RoI extent >= 1.5 px): hundreds of pixels outside
 
 
-OPS = {op.name: op for op in (Dcnv3, Dcnv4, Dcnv4Softmax, Msda, Fda, Msda3d, Droi)}
+DAGG_G = (1, 2, 3, 4, 8)                 # groups of a random shape
+DAGG_VG = (1, 2, 3, 4, 5, 6, 8, 33)      # vectors per group: VG = 33 with G >= 2 takes two rounds and carries a group
+
+
+class Dagg:
+    """Deformable aggregation: the anchor's whole row is the head (D = C), a unit (point, camera) the tap (K = U), and one
+    segment per image of S = cams * S_cam rows; ``seg`` and ``rounds`` tell which reduction of dagg_bwd_coord_kernel runs."""
+    name, kinds, pairings, plain_factor, naxes = "dagg", "vvcc", PAIRINGS, True, 2
+    names = ("output", "grad_feature", "grad_sampling_location", "grad_weights")
+    fuzz_V = tuple(sorted({g * vg for g in DAGG_G for vg in DAGG_VG}))
+
+    @staticmethod
+    def draw(spec, dtype, coord_dtype, seed):
+        spec = dict(spec)
+        shapes = tuple(tuple(s) for s in spec.pop("shapes"))
+        return RG.make_inputs(shapes=list(shapes), dtype=dtype, coord_dtype=coord_dtype, seed=seed, **spec), shapes
+
+    @staticmethod
+    def native(t, geo, grads=None, deterministic=False, accumulate=True):
+        from modulated_deform_conv_amd import dagg
+        feature, loc, weights, go = t
+        out = dagg.deformable_aggregation_forward(feature, geo, loc, weights)
+        g = dagg.deformable_aggregation_backward(feature, geo, loc, weights, go, **_call_kw(grads, deterministic, accumulate))
+        torch.cuda.synchronize()
+        return (out,) + tuple(g)
+
+    @staticmethod
+    def ref(t, geo):
+        return RG.dagg_ref_grads(t[0], geo, t[1], t[2], t[3])
+
+    @staticmethod
+    def direct(t, geo):
+        return RG.dagg_ref_grads(t[0], geo, t[1], t[2], t[3], fn=RG.dagg_direct)
+
+    @staticmethod
+    def grad_like(t):
+        return t[:3]
+
+    @staticmethod
+    def gate(t, geo):
+        return RG.gate_of(t[1])   # [B, A, P, cams]
+
+    @staticmethod
+    def min_lattice_distance(t, geo):
+        return RG.min_lattice_distance(t[1], list(geo))
+
+    @staticmethod
+    def structure(t, geo):
+        feature, loc, weights = t[:3]
+        B, S, C = feature.shape
+        A, P, cams = loc.shape[1:4]
+        L, G = weights.shape[4:]
+        starts, s_cam = RG.level_starts(list(geo))
+        assert S == cams * s_cam and L == len(geo)
+        pos = RG.pixel_positions(loc, list(geo))   # [B, A, P, cams, L, 2], (x, y)
+        # the operator's own gate, 0 < x < 1 and 0 < y < 1 on the stored location: a unit outside it reads no level
+        gate = RG.gate_of(loc)[..., None].expand(pos.shape[:-1])
+        x, y = (torch.where(gate, pos[..., a], torch.full_like(pos[..., a], -2.0)) for a in (0, 1))
+        seg = torch.arange(B).view(B, 1, 1, 1, 1).expand(x.shape)
+        start = torch.arange(cams).view(1, 1, 1, cams, 1) * s_cam + torch.tensor(starts).view(1, 1, 1, 1, L)
+        hs, ws = (torch.tensor([float(s[a]) for s in geo], dtype=torch.float64).view(1, 1, 1, 1, L).expand(x.shape) for a in (0, 1))
+        counts = _corner_counts(seg, B, S, start, [(y, hs), (x, ws)])
+        s = _summary(counts, B, S, B * A, feature, C, P * cams)
+        VG = C // G * esize(feature.dtype) // 16
+        # DaggGeom.seg (dagg_host.hip): a group is an aligned power-of-two run of lanes inside one round
+        s.update(VG=VG, seg=int(VG & (VG - 1) == 0 and VG <= s["VL"]), L=L)
+        return s
+
+    @staticmethod
+    def unpack(t, geo):
+        return t[1], t[2]
+
+    @staticmethod
+    def repack(t, geo, coords):
+        return (t[0], coords.contiguous(), t[2], t[3])
+
+    @staticmethod
+    def unpack_grads(got, t, geo):
+        return got[2], got[3]
+
+    @staticmethod
+    def far_value(t, geo):
+        return -3.0
+
+
+OPS = {op.name: op for op in (Dcnv3, Dcnv4, Dcnv4Softmax, Msda, Fda, Msda3d, Droi, Dagg)}
 
 
 def tols(op, t):
@@ -508,7 +600,7 @@ def compare(op, tag, got, want, tol):
 # ---- part 2: seeded random shapes ------------------------------------------------------------------------------------
 FUZZ_SEEDS = 24
 FUZZ_ATTEMPTS = 8
-_V = (1, 2, 3, 4, 5, 8, 16)   # vectors per head: V = 1, odd V, V = 5 in eight lanes, VL = 16
+_V = FUZZ_V
 
 
 def _head_channels(r, dtype):
@@ -559,7 +651,16 @@ def _draw_droi(r, dtype, coord_dtype):
                 gamma=r.choice((0.05, 0.1, 0.3)), max_grid=r.choice((2, 4, 8)), with_offset=r.random() < 0.7)
 
 
-_DRAW = {"dcnv3": lambda r, d, c: _draw_dcn(r, d, c, False), "dcnv4": lambda r, d, c: _draw_dcn(r, d, c, True),
+def _draw_dagg(r, dtype, coord_dtype):
+    """U = P * cams against VL, G and VG independently (V = G * VG: no power of two, a group across a round's end, V = 66
+    and more in two or more rounds), one to eight levels shared by up to six cameras."""
+    ext = _max_extent(dtype, coord_dtype)
+    L = r.randint(1, 8)
+    return dict(B=r.randint(1, 3), A=r.randint(1, 40), P=r.randint(1, 5), cams=r.randint(1, 6), shapes=_draw_levels(r, ext, L, 2),
+                G=r.choice(DAGG_G), Dg=r.choice(DAGG_VG) * (4 if dtype == F32 else 8))
+
+
+_DRAW = {"dcnv3": lambda r, d, c: _draw_dcn(r, d, c, False), "dcnv4": lambda r, d, c: _draw_dcn(r, d, c, True), "dagg": _draw_dagg,
          "dcnv4_softmax": lambda r, d, c: _draw_dcn(r, d, c, True), "msda": lambda r, d, c: _draw_attn(r, d, c, 2),
          "fda": lambda r, d, c: _draw_attn(r, d, c, 2), "msda3d": lambda r, d, c: _draw_attn(r, d, c, 3), "droi": _draw_droi}
 
@@ -646,7 +747,16 @@ def _dyadic_droi(t, geo):
     return (inp, rois, (off.double() * 64).round().div(64).to(off.dtype), go)
 
 
-CRAFT = {"attn": _crafted_attn, "dcnv3": _crafted_dcnv3, "dyadic_dcnv3": _dyadic_dcnv3, "dyadic_droi": _dyadic_droi}
+def _crafted_dagg(t, geo):
+    """Every location at pixel (1.3, 1.4) of the 4 x 4 level, (0.4, 0.45) of the 2 x 2 one: every unit passes the gate, and
+    four rows of each level take one entry per unit."""
+    feature, loc, weights, go = t
+    loc = torch.tensor(RG.CRAFTED_XY, dtype=torch.float64).to(loc.dtype).expand(loc.shape).contiguous()
+    return (feature, loc, weights, go)
+
+
+CRAFT = {"attn": _crafted_attn, "dcnv3": _crafted_dcnv3, "dyadic_dcnv3": _dyadic_dcnv3, "dyadic_droi": _dyadic_droi,
+         "dagg": _crafted_dagg}
 # the 3 x 683 image with free fp32 offsets: what the input rule above is measured on
 WIDE_FREE = dict(op="dcnv3", spec=dict(B=2, G=2, D=4, H=3, W=683, kernel=3, pad=1), seed=17)
 # per-element bound of WIDE_FREE against the fp64 reference: the reference's own movement under fp32 positions, 2.15e-4
@@ -685,6 +795,14 @@ SCAN_CASES = {
                       claim=dict(rows=2049, chunks=2, tail=True)),
     "droi_4794": dict(op="droi", spec=dict(B=2, C=8, H=47, W=51, R=41, PH=3, PW=3, sampling_ratio=0, max_grid=4),
                       pairings=((F32, None), (F16, F32)), claim=dict(rows=4794, chunks=3, tail=True)),
+    # deformable aggregation: one segment per IMAGE of cams * S_cam rows, its own list kernel and gather.  2049 rows: the last
+    # chunk holds the one-pixel level's row, which every gated-in unit samples.  4680 = 3 cameras x 1560 rows: the camera
+    # boundaries at rows 1560 and 3120 fall inside scan chunks
+    "dagg_2048": dict(op="dagg", spec=dict(B=2, A=67, P=2, cams=2, shapes=((32, 32),), G=1, Dg=4), claim=dict(rows=2048, chunks=1)),
+    "dagg_2049": dict(op="dagg", spec=dict(B=2, A=135, P=2, cams=1, shapes=((32, 64), (1, 1)), G=1, Dg=4),
+                      claim=dict(rows=2049, chunks=2, straddle=True, tail=True)),
+    "dagg_4680": dict(op="dagg", spec=dict(B=2, A=101, P=2, cams=3, shapes=((37, 41), (6, 7), (1, 1)), G=3, Dg=8),
+                      pairings=((F32, None), (F16, F32)), claim=dict(rows=4680, chunks=3, straddle=True, tail=True)),
 }
 
 LIST_CASES = {
@@ -698,6 +816,13 @@ LIST_CASES = {
     # K * output pixels = 3 * 28 * 25
     "dcnv3_list_2100": dict(op="dcnv3", spec=dict(B=1, G=1, D=4, H=28, W=25, kernel=(3, 1), pad=(1, 0)), craft="dcnv3",
                             claim=dict(longest=2100)),
+    # an entry per sample, shared by all groups (the gather multiplies by weights[id * G + grp]): A * P units at one location
+    "dagg_list_2048": dict(op="dagg", spec=dict(B=1, A=2048, P=1, cams=1, shapes=((4, 4), (2, 2)), G=1, Dg=4), craft="dagg",
+                           claim=dict(longest=2048)),
+    "dagg_list_2049": dict(op="dagg", spec=dict(B=1, A=2049, P=1, cams=1, shapes=((4, 4), (2, 2)), G=1, Dg=4), craft="dagg",
+                           claim=dict(longest=2049)),
+    "dagg_list_2100": dict(op="dagg", spec=dict(B=1, A=700, P=3, cams=1, shapes=((4, 4), (2, 2)), G=1, Dg=4), craft="dagg",
+                           claim=dict(longest=2100)),
 }
 
 SEGMENT_CASES = {
@@ -709,6 +834,8 @@ SEGMENT_CASES = {
     "dcnv4_65535": dict(op="dcnv4", spec=dict(B=21845, G=3, D=4, H=2, W=2, kernel=1), claim=dict(segments=65535)),
     "dcnv4_softmax_65535": dict(op="dcnv4_softmax", spec=dict(B=13107, G=5, D=4, H=2, W=2, kernel=(1, 3), pad=(0, 1)),
                                 claim=dict(segments=65535)),
+    # one segment per image: batch = 65535, the limit dagg_plan states for the lists
+    "dagg_65535": dict(op="dagg", spec=dict(B=65535, A=1, P=1, cams=1, shapes=((1, 2),), G=1, Dg=4), claim=dict(segments=65535)),
 }
 
 FIXED_CASES = dict(SCAN_CASES, **LIST_CASES, **SEGMENT_CASES)
@@ -760,11 +887,14 @@ TOP_CASES = {
     "dcnv4": dict(B=2047, G=8, D=32, H=32, W=32, kernel=1, stride=2),
     "dcnv4_softmax": dict(B=2047, G=8, D=32, H=32, W=32, kernel=(1, 3), stride=2, pad=(0, 1)),
     "droi": dict(B=2047, C=256, H=32, W=32, R=6, PH=2, PW=2, sampling_ratio=2),
+    "dagg": dict(B=2047, A=5, P=2, cams=2, shapes=((16, 32),), G=8, Dg=32),
 }
 
 
 def top_bytes(op_name):
     s = TOP_CASES[op_name]
+    if op_name == "dagg":
+        return s["B"] * s["cams"] * sum(h * w for h, w in s["shapes"]) * s["G"] * s["Dg"] * 4
     if "shapes" in s:
         rows = sum(functools.reduce(lambda a, b: a * b, sh) for sh in s["shapes"])
         return s["N"] * rows * s["M"] * s["D"] * 4
@@ -784,6 +914,7 @@ NONFINITE_CASES = {
     "fda": dict(N=2, M=3, D=8, shapes=((6, 5), (3, 4), (2, 2)), Lq=9, P=2),
     "msda3d": dict(N=2, M=2, D=8, shapes=((3, 5, 4), (2, 2, 3)), Lq=9, P=2),
     "droi": dict(B=2, C=8, H=8, W=7, R=5, PH=3, PW=2, sampling_ratio=2, gamma=0.2),
+    "dagg": dict(B=2, A=9, P=2, cams=3, shapes=((6, 5), (3, 4), (2, 2)), G=3, Dg=8),
 }
 NONFINITE_PAIRINGS = ((F32, None), (F16, None))
 NAN, INF = float("nan"), float("inf")
@@ -827,7 +958,7 @@ def overwrite(op_name, dtype, coord_dtype, axes, value):
 @functools.lru_cache(maxsize=None)
 def replaced_case(op_name, dtype, coord_dtype, axes):
     """The same inputs with every such coordinate replaced by a finite one far outside the gate (normalised -3 for the
-    attention operators, -1e4 px for the DCN operators, an offset of -1e4 RoI fractions for the RoI pooling), and the fp64
+    attention operators and the aggregation, -1e4 px for the DCN operators, an offset of -1e4 RoI fractions for the RoI pooling), and the fp64
     reference of those inputs."""
     op = OPS[op_name]
     t, geo = nonfinite_case(op_name, dtype, coord_dtype)

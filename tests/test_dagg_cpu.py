@@ -88,6 +88,45 @@ def test_the_two_references_agree(name):
     assert float(ref[2][~gate].abs().max()) == 0.0 and float(ref[3][~gate].abs().max()) == 0.0
 
 
+def _rounds_of(name, dtype):
+    """(VG, VL, V, seg, per round: (first vector, one past the last)) of a case, as dagg_plan lays the anchor's row out."""
+    from tests import samp_cases as SC
+    kw = R.CASES[name]
+    ln = SC.lanes(kw["G"] * kw["Dg"], dtype)
+    VG = kw["Dg"] * SC.esize(dtype) // 16
+    seg = int(VG & (VG - 1) == 0 and VG <= ln["VL"])
+    return VG, ln["VL"], ln["V"], seg, [(rd * ln["VL"], min(ln["V"], (rd + 1) * ln["VL"])) for rd in range(ln["rounds"])]
+
+
+def test_the_group_reduction_cases_are_what_they_claim():
+    """The four group-reduction cases reach the branch of dagg_bwd_coord_kernel their comments name, from the lane geometry
+    (``samp_cases.lanes``) and VG: ``seg``, the rounds, and where a round's end falls against the groups."""
+    whole = lambda VG, lo, hi: [g for g in range(lo // VG, (hi - 1) // VG + 1) if g * VG >= lo and (g + 1) * VG <= hi]
+    for name, (seg, rounds) in R.GROUP_CASES.items():
+        dtypes = (torch.float16, torch.bfloat16) if name.endswith("16bit") else (torch.float32,)
+        for dtype in dtypes:
+            got = _rounds_of(name, dtype)
+            assert (got[3], len(got[4])) == (seg, rounds), (name, dtype, got)
+    # odd_group: three groups of three vectors in the first 9 of 16 lanes, one round
+    for name, dtype in (("odd_group", torch.float32), ("odd_group_16bit", torch.float16), ("odd_group_16bit", torch.bfloat16)):
+        assert _rounds_of(name, dtype)[:3] == (3, 16, 9)
+    # carry_and_whole_groups: rounds 0 and 1 end inside a group and hold whole groups; rounds 1 and 2 begin with a tail
+    VG, VL, V, _, rds = _rounds_of("carry_and_whole_groups", torch.float32)
+    assert (VG, VL, V) == (24, 64, 192)
+    for rd, (lo, hi) in enumerate(rds):
+        assert whole(VG, lo, hi), rd
+        assert (hi % VG != 0) == (rd < 2) and (lo % VG != 0) == (rd > 0), rd
+    assert any(lo % VG and hi % VG for lo, hi in rds)   # the tail of one group, whole groups and the head of the next
+    # group_fills_two_rounds: wider than a round; the group, carried over round 0, ends exactly on round 1's end
+    VG, VL, V, _, rds = _rounds_of("group_fills_two_rounds", torch.float32)
+    assert VG == V == 128 > VL == 64 and rds[1][1] == VG and not whole(VG, *rds[0])
+    # group_per_round: a group is a whole round (VG = VL), the widest segmented butterfly
+    VG, VL, V, _, rds = _rounds_of("group_per_round", torch.float32)
+    assert VG == VL == 64 and V == 128 and [whole(VG, lo, hi) for lo, hi in rds] == [[0], [1]]
+    # and the cases from before keep the masked butterfly at VG = 65 only
+    assert _rounds_of("two_rounds", torch.float32)[:4] == (65, 64, 65, 0)
+
+
 def test_the_references_at_the_gate():
     """Exactly 0.0 and 1.0 are out, one step inside both ends is in (pixel -0.5: half the weight falls outside the map), NaN,
     Inf and huge locations equal -3.0, and a NaN weight of a gated-out triple reaches nothing."""

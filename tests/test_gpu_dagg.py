@@ -77,6 +77,8 @@ def _exact_zero(tag, t, where=None):
     ("straddle", F32, None), ("straddle", BF16, F32), ("wide_anchor", F32, None), ("wide_anchor", F16, None),
     ("two_rounds", F32, None), ("two_rounds_16bit", F16, None), ("groups_across_rounds", F32, None), ("eight_levels", F32, None), ("many_taps", F32, None),
     ("cams_levels", BF16, F32), ("crafted", F32, None),
+    ("odd_group", F32, None), ("odd_group_16bit", F16, None), ("odd_group_16bit", BF16, F32),
+    ("carry_and_whole_groups", F32, None), ("group_fills_two_rounds", F32, None), ("group_per_round", F32, None),
 ])
 def test_against_reference(name, dtype, coord_dtype):
     t, shapes, want = _case(name, dtype, coord_dtype)

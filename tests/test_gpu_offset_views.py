@@ -456,6 +456,8 @@ def _forward_with_output(op_name, views, geo, out):
         return m.ms_deform_attn_3d_forward(views[0], geo, views[1], views[2], output=out)
     if op_name == "fda":
         return m.flash_deform_attn_forward(views[0], geo[0], views[1], geo[1], output=out)
+    if op_name == "dagg":
+        return m.deformable_aggregation_forward(views[0], geo, views[1], views[2], output=out)
     return m.deform_roi_pool_forward(views[0], views[1], views[2], **geo, output=out)
 
 
@@ -499,6 +501,8 @@ def _functional(op_name, v, geo):
         return m.ms_deform_attn_3d(v[0], geo, v[1], v[2])
     if op_name == "fda":
         return m.flash_deform_attn(v[0], geo[0], v[1], geo[1])
+    if op_name == "dagg":
+        return m.deformable_aggregation(v[0], geo, v[1], v[2])
     # logical NCHW in and out: permute views of the channels-last tensors, no copy
     return m.deform_roi_pool(v[0].permute(0, 3, 1, 2), v[1], v[2], **geo).permute(0, 2, 3, 1)
 

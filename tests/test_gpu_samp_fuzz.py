@@ -1,4 +1,4 @@
-"""Seeded random shapes for the six channels-last sampling operators (DCNv4 with and without ``softmax=``: seven entries of
+"""Seeded random shapes for the seven channels-last sampling operators (DCNv4 with and without ``softmax=``: eight entries of
 tests/samp_cases.py), 24 seeds each, the dtype pairings rotating over the seeds: output and every gradient against the fp64
 reference evaluated from the inputs as the kernel sees them, at the project's tolerances (1e-4 fp32, ``TOL`` of
 tests/test_gpu_hp.py for 16-bit; value-typed results by the value dtype, coordinate and factor gradients by the coordinate
@@ -63,8 +63,9 @@ def test_random_shape(op_name, seed):
 
 def test_fuzz_reaches_the_lane_geometry():
     """From the draws that ran: the seeds of each operator reach three distinct VL, a K below VL and a K that is no multiple
-    of VL (the RoI pooling has no tap batches: three VL, both grid rules).  Needs the seeds of this module in the same
-    session."""
+    of VL (the RoI pooling has no tap batches: three VL, both grid rules); the aggregation's also both group reductions of
+    its coordinate backward (``seg``), a row of more than one round and five levels or more.  Needs the seeds of this module
+    in the same session."""
     if any(len(_DRAWN.get(op_name, {})) < SC.FUZZ_SEEDS for op_name in SC.OPS):
         pytest.skip("needs the %d random cases per operator of this module in the same session" % SC.FUZZ_SEEDS)
     for op_name, drawn in sorted(_DRAWN.items()):
@@ -75,3 +76,6 @@ def test_fuzz_reaches_the_lane_geometry():
             continue
         assert any(s["K"] < s["VL"] for s in st), op_name
         assert any(s["K"] % s["VL"] for s in st), op_name
+        if op_name == "dagg":
+            assert {s["seg"] for s in st} == {0, 1}
+            assert any(s["rounds"] > 1 for s in st) and any(s["L"] >= 5 for s in st)

@@ -1,4 +1,4 @@
-"""NaN, infinite and overflowing coordinates on the six channels-last sampling operators.  The contract (include/mdconv.h): a
+"""NaN, infinite and overflowing coordinates on the seven channels-last sampling operators.  The contract (include/mdconv.h): a
 sample contributes iff it passes the gate on every axis, so a NaN or infinite coordinate -- or a finite one that overflows once
 scaled by the extent or by ``offset_scale`` -- contributes nothing and has gradient exactly zero.  A fresh layer whose offset
 branch diverges produces exactly such inputs.

@@ -3,7 +3,8 @@ MiB below 2^31 bytes (the cases are tests/samp_cases.py's; tests/test_samp_cases
 
   * segments of 2048, 2049 and more than 4096 rows -- one, two and three chunks of ``csr_scan_chunk`` (kScanChunk = 2048), the
     ``pre`` loop and its second iteration --, more than one segment (a 64-row sort chunk straddles two), many workgroups with a
-    partly filled last one; one depthwise case, whose family builds its lists with the same ``scatter_lists_build``;
+    partly filled last one; one depthwise case, whose family builds its lists with the same ``scatter_lists_build``; the
+    aggregation's segment is an image of cams * S_cam rows, with camera boundaries inside a chunk (its own list kernel and gather);
   * lists of exactly 2048, 2049 and 2100 entries: the second pass over the key blocks of ``sort_row_block`` (kKeyBlock = 2048),
     its last partial block and the padding keys;
   * 65535 segments, the scan's ``grid.y`` at the limit the shape rules allow;

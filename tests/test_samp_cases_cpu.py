@@ -30,9 +30,11 @@ def _meta(t):
 
 def _workspace_bytes(capi, op_name, t, geo):
     """Bytes of the full backward's workspace by the library's own plan: 0 for a call outside the shape rule."""
-    from modulated_deform_conv_amd import dcnv3, dcnv4, droi, fda, msda, msda3d
+    from modulated_deform_conv_amd import dagg, dcnv3, dcnv4, droi, fda, msda, msda3d
     L = capi.lib()
-    if op_name == "dcnv3":
+    if op_name == "dagg":
+        d, fn = dagg._desc(t[0], t[1], t[2], geo), L.mdconv_dagg_workspace_bytes
+    elif op_name == "dcnv3":
         d, fn = dcnv3._desc(t[0], *geo), L.mdconv_dcnv3_workspace_bytes
     elif op_name.startswith("dcnv4"):
         d, fn = dcnv4._desc(t[0], t[1], *geo), L.mdconv_dcnv4_workspace_bytes
@@ -88,7 +90,7 @@ def test_fuzz_draw(capi, op_name, seed):
     assert _extents(op_name, spec) <= (24 if (coord_dtype or dtype) == F32 else 8)
     _conditions(op, t, geo)
     s = op.structure(t, geo)
-    assert s["V"] in (1, 2, 3, 4, 5, 8, 16) and s["K"] >= 1 and s["entries"] > 0
+    assert s["V"] in op.fuzz_V and s["K"] >= 1 and s["entries"] > 0
     assert s["bytes"] < SC.LIMIT and s["segments"] <= SC.MAX_SEGMENTS
     assert _workspace_bytes(capi, op_name, t, geo) > 0, capi.last_error()
     _references_agree("%s seed %d" % (op_name, seed), op, t, geo)
@@ -97,7 +99,8 @@ def test_fuzz_draw(capi, op_name, seed):
 def test_fuzz_redraws_and_coverage(capi):
     """How many redraws each operator took (printed), and what the 24 seeds of each operator reach: three distinct VL, a K
     below VL and a K that is no multiple of VL (the RoI pooling walks a bin's samples lane by lane, without tap batches: its
-    seeds reach three VL, both grid rules, and calls with and without offset)."""
+    seeds reach three VL, both grid rules, and calls with and without offset).  The aggregation's seeds also reach both
+    group reductions of its coordinate backward (``seg``), a row of more than one round, and five levels or more."""
     for op_name in sorted(SC.OPS):
         op = SC.OPS[op_name]
         draws = [SC.fuzz_case(op_name, seed) for seed in range(SC.FUZZ_SEEDS)]
@@ -111,6 +114,9 @@ def test_fuzz_redraws_and_coverage(capi):
         else:
             assert any(s["K"] < s["VL"] for s in st), op_name
             assert any(s["K"] % s["VL"] for s in st), op_name
+        if op_name == "dagg":
+            assert {s["seg"] for s in st} == {0, 1}
+            assert any(s["rounds"] > 1 for s in st) and any(s["L"] >= 5 for s in st)
 
 
 @pytest.mark.parametrize("name, dtype, coord_dtype", SC.fixed_params(SC.FIXED_CASES), ids=SC.fixed_ids(SC.FIXED_CASES))
@@ -167,13 +173,29 @@ def test_wide_image_rule_is_the_fp32_positions():
 
 def test_the_tables_cover_what_the_issue_names():
     scan = {SC.FIXED_CASES[n]["op"] for n in SC.SCAN_CASES}
-    assert {"dcnv3", "msda", "msda3d", "droi"} <= scan
-    for op_name in ("dcnv3", "msda", "msda3d", "droi"):
+    assert {"dcnv3", "msda", "msda3d", "droi", "dagg"} <= scan
+    for op_name in ("dcnv3", "msda", "msda3d", "droi", "dagg"):
         rows = sorted(c["claim"]["rows"] for c in SC.SCAN_CASES.values() if c["op"] == op_name)
         assert rows[0] == 2048 and rows[1] == 2049 and rows[2] > 4096, (op_name, rows)
     assert sorted(c["claim"]["longest"] for c in SC.LIST_CASES.values() if c["op"] == "msda") == [2048, 2049, 2100]
-    assert {c["op"] for c in SC.SEGMENT_CASES.values()} == {"dcnv3", "dcnv4", "dcnv4_softmax", "msda", "fda", "msda3d"}
+    assert sorted(c["claim"]["longest"] for c in SC.LIST_CASES.values() if c["op"] == "dagg") == [2048, 2049, 2100]
+    assert {c["op"] for c in SC.SEGMENT_CASES.values()} == {"dcnv3", "dcnv4", "dcnv4_softmax", "msda", "fda", "msda3d", "dagg"}
     assert set(SC.TOP_CASES) == set(SC.OPS) == set(SC.NONFINITE_CASES)
+
+
+def test_dagg_batch_limit(capi):
+    """One image more than ``dagg_65535``: the full backward has no plan, for the reason dagg_plan states for the lists of
+    grad_feature; the backward without grad_feature, which builds no lists, and the forward are inside the shape rule."""
+    from modulated_deform_conv_amd import dagg
+    t, geo = SC.fixed_case("dagg_65535")
+    assert t[0].shape[0] == SC.MAX_SEGMENTS
+    more = tuple(torch.empty((SC.MAX_SEGMENTS + 1,) + v.shape[1:], dtype=v.dtype, device="meta") for v in t)
+    fn = capi.lib().mdconv_dagg_workspace_bytes
+    assert int(fn(ctypes.byref(dagg._desc(more[0], more[1], more[2], geo)), 1)) == 0
+    assert "shape rule" in capi.last_error() and "batch exceeds 65535" in capi.last_error()
+    skip = dagg._desc(more[0], more[1], more[2], geo, flags=capi.FLAG_NO_GRAD_INPUT)
+    assert int(fn(ctypes.byref(skip), 1)) == 0 and "shape rule" not in capi.last_error()   # accepted: a call without workspace
+    assert int(fn(ctypes.byref(dagg._desc(more[0], more[1], more[2], geo)), 0)) == 0 and "shape rule" not in capi.last_error()
 
 
 @pytest.mark.parametrize("op_name", sorted(SC.TOP_CASES))
