@@ -35,6 +35,11 @@ behind the reference's own operator surface.
                                                        include/mdconv_dagg.h): DeformableAggregationFunction,
                                                        deformable_aggregation, deformable_aggregation_forward / _backward,
                                                        feature_maps_format -- also exported here
+    modulated_deform_conv_amd.msdap                    multi-scale deformable attention with a point count per level
+                                                       (RT-DETRv2's num_points_list; D-FINE / DEIM: (3, 6, 3); C ABI in
+                                                       include/mdconv_msdap.h): MSDeformAttnPointsFunction,
+                                                       ms_deform_attn_points, ms_deform_attn_points_forward / _backward,
+                                                       MSDeformableAttention -- also exported here
     modulated_deform_conv_amd.distributed              batch-sharded multi-GPU helper (RCCL)
 
 All compute runs in libmdconv_hip.so (hand-written HIP, C ABI in include/mdconv.h); there is no
@@ -55,7 +60,9 @@ _MSDA3D = ("ms_deform_attn_3d_forward", "ms_deform_attn_3d_backward", "MSDeformA
            "MSDeformAttn3D")
 _DAGG = ("deformable_aggregation_forward", "deformable_aggregation_backward", "DeformableAggregationFunction",
          "deformable_aggregation", "feature_maps_format")
-__all__ = list(_DCNV3 + _MSDA + _DCNV4 + _FDA + _DROI + _MSDA3D + _DAGG)
+_MSDAP = ("ms_deform_attn_points_forward", "ms_deform_attn_points_backward", "MSDeformAttnPointsFunction",
+          "ms_deform_attn_points", "MSDeformableAttention")
+__all__ = list(_DCNV3 + _MSDA + _DCNV4 + _FDA + _DROI + _MSDA3D + _DAGG + _MSDAP)
 
 
 def __getattr__(name):
@@ -81,4 +88,7 @@ def __getattr__(name):
     if name in _DAGG:
         from . import dagg
         return getattr(dagg, name)
+    if name in _MSDAP:
+        from . import msdap
+        return getattr(msdap, name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))
