@@ -40,6 +40,13 @@ behind the reference's own operator surface.
                                                        include/mdconv_msdap.h): MSDeformAttnPointsFunction,
                                                        ms_deform_attn_points, ms_deform_attn_points_forward / _backward,
                                                        MSDeformableAttention -- also exported here
+    modulated_deform_conv_amd.fdap                     packed deformable attention with a point count per level (one packed
+                                                       tensor of locations and logits, the softmax over all K taps inside
+                                                       the operator; C ABI in include/mdconv_fdap.h):
+                                                       FlashDeformAttnPointsFunction, flash_deform_attn_points,
+                                                       flash_deform_attn_points_forward / _backward,
+                                                       MSDeformableAttentionFused, pack_loc_attn_points /
+                                                       unpack_loc_attn_points -- also exported here
     modulated_deform_conv_amd.distributed              batch-sharded multi-GPU helper (RCCL)
 
 All compute runs in libmdconv_hip.so (hand-written HIP, C ABI in include/mdconv.h); there is no
@@ -62,7 +69,9 @@ _DAGG = ("deformable_aggregation_forward", "deformable_aggregation_backward", "D
          "deformable_aggregation", "feature_maps_format")
 _MSDAP = ("ms_deform_attn_points_forward", "ms_deform_attn_points_backward", "MSDeformAttnPointsFunction",
           "ms_deform_attn_points", "MSDeformableAttention")
-__all__ = list(_DCNV3 + _MSDA + _DCNV4 + _FDA + _DROI + _MSDA3D + _DAGG + _MSDAP)
+_FDAP = ("flash_deform_attn_points_forward", "flash_deform_attn_points_backward", "FlashDeformAttnPointsFunction",
+         "flash_deform_attn_points", "MSDeformableAttentionFused", "pack_loc_attn_points", "unpack_loc_attn_points")
+__all__ = list(_DCNV3 + _MSDA + _DCNV4 + _FDA + _DROI + _MSDA3D + _DAGG + _MSDAP + _FDAP)
 
 
 def __getattr__(name):
@@ -91,4 +100,7 @@ def __getattr__(name):
     if name in _MSDAP:
         from . import msdap
         return getattr(msdap, name)
+    if name in _FDAP:
+        from . import fdap
+        return getattr(fdap, name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

@@ -49,12 +49,15 @@ EXPORTS_DAGG = ("mdconv_dagg_feature_len", "mdconv_dagg_workspace_bytes", "mdcon
 # include/mdconv_msdap.h (deformable attention with a point count per level): likewise
 EXPORTS_MSDAP = ("mdconv_msdap_value_len", "mdconv_msdap_points_len", "mdconv_msdap_workspace_bytes", "mdconv_msdap_forward",
                  "mdconv_msdap_backward")
+# include/mdconv_fdap.h (packed deformable attention with a point count per level): likewise
+EXPORTS_FDAP = ("mdconv_fdap_value_len", "mdconv_fdap_loc_attn_len", "mdconv_fdap_workspace_bytes", "mdconv_fdap_forward",
+                "mdconv_fdap_backward")
 
 # The descriptor-only queries of the sampling operators, operator -> names: every operator has
 # mdconv_<op>_workspace_bytes(desc, backward) -> size_t besides; out_size takes (desc, axis), a *_len (desc); all return int.
 SAMP_QUERIES = {"dcnv3": ("out_size",), "msda": ("value_len",), "dcnv4": ("out_size", "offset_mask_len"),
                 "fda": ("value_len", "loc_attn_len"), "droi": (), "msda3d": ("value_len",), "dagg": ("feature_len",),
-                "msdap": ("value_len", "points_len")}
+                "msdap": ("value_len", "points_len"), "fdap": ("value_len", "loc_attn_len")}
 
 
 class MdconvDesc(ctypes.Structure):
@@ -142,6 +145,11 @@ class MdconvMsdapDesc(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int * MSDA_MAX_LEVELS) if n == "points" else (n, t) for n, t in MdconvMsdaDesc._fields_]
 
 
+class MdconvFdapDesc(ctypes.Structure):
+    """Mirror of ``struct mdconv_fdap_desc`` (include/mdconv_fdap.h): the fields of ``MdconvMsdapDesc``."""
+    _fields_ = list(MdconvMsdapDesc._fields_)
+
+
 _lib = None
 
 
@@ -193,9 +201,9 @@ def lib():
         missing = (() if has_math_query else ("mdconv_math_bf16_used",)) + (() if has_layout_query else ("mdconv_result_layout_supported",))
         missing += () if has_plan_query else ("mdconv_planned_kernels",)
         # (likewise a build from before one of the sampling operators: that operator's wrapper raises there)
-        missing += tuple(n for n in EXPORTS + EXPORTS_DAGG + EXPORTS_MSDAP
+        missing += tuple(n for n in EXPORTS + EXPORTS_DAGG + EXPORTS_MSDAP + EXPORTS_FDAP
                          if n.startswith(tuple("mdconv_%s_" % op for op in SAMP_QUERIES)) and not hasattr(L, n))
-        for name in EXPORTS[11:] + EXPORTS_DAGG + EXPORTS_MSDAP:
+        for name in EXPORTS[11:] + EXPORTS_DAGG + EXPORTS_MSDAP + EXPORTS_FDAP:
             if name not in missing:
                 getattr(L, name).restype = ctypes.c_int
         for op, queries in SAMP_QUERIES.items():

@@ -248,18 +248,31 @@ class MSDeformableAttention(nn.Module):
         ``value [N, S, C]``; ``value_spatial_shapes``: L rows (H, W), host data or a tensor (a CUDA tensor costs a
         synchronisation per call); ``value_mask [N, S]``: True / 1 where the value is KEPT (the published block multiplies)."""
         N, Lq, _ = query.shape
-        S = value.shape[1]
+        shapes, value = self._values(value, value_spatial_shapes, value_mask)
+        K = sum(self.num_points_list)
+        # (softmax and the locations run in fp32 under autocast: the core then takes fp32 coordinates)
+        weights = F.softmax(self.attention_weights(query).float().view(N, Lq, self.num_heads, K), -1)
+        locations = self._locations(query, reference_points, shapes)
+        out = self._core(value, shapes, self.num_points_list, locations, weights)
+        return self.output_proj(out)
+
+    def _values(self, value, value_spatial_shapes, value_mask):
+        """The level extents as host data and the projected, masked ``value [N, S, M, D]`` of a forward."""
+        N, S = value.shape[:2]
         shapes = _shapes(value_spatial_shapes)
         if len(shapes) != self.num_levels or sum(h * w for h, w in shapes) != S:
             raise ValueError("value_spatial_shapes %s does not describe %d levels of %d rows" % (shapes, self.num_levels, S))
-        M, L, K = self.num_heads, self.num_levels, sum(self.num_points_list)
         value = self.value_proj(value)
         if value_mask is not None:
             value = value * value_mask.to(value.dtype).unsqueeze(-1)
-        value = value.view(N, S, M, self.head_dim)
+        return shapes, value.view(N, S, self.num_heads, self.head_dim)
+
+    def _locations(self, query, reference_points, shapes):
+        """``sampling_locations [N, Lq, M, K, 2]`` of a forward, fp32: the reference points (or boxes) plus the scaled output
+        of the ``sampling_offsets`` linear.  (A method of its own for ``MSDeformableAttentionFused``.)"""
+        N, Lq, _ = query.shape
+        M, L, K = self.num_heads, self.num_levels, sum(self.num_points_list)
         offsets = self.sampling_offsets(query).float().view(N, Lq, M, K, 2)
-        # (softmax and the locations run in fp32 under autocast: the core then takes fp32 coordinates)
-        weights = F.softmax(self.attention_weights(query).float().view(N, Lq, M, K), -1)
         ref = reference_points.float()
         if ref.dim() != 4 or ref.shape[:2] != (N, Lq):
             raise ValueError("reference_points must be [N, Lq, 1 or L, 2 or 4], got %s" % (tuple(reference_points.shape),))
@@ -274,14 +287,11 @@ class MSDeformableAttention(nn.Module):
                                  "num_points is %s: pass boxes (x, y, w, h)" % (self.num_points_list,))
             wh = torch.tensor([[w, h] for h, w in shapes], dtype=torch.float32, device=query.device)   # (x, y) order
             wh = wh.repeat_interleave(self.num_points_list[0], dim=0)
-            locations = ref[:, :, None, :, :] + offsets / wh[None, None, None, :, :]
-        elif ref.shape[-1] == 4:
+            return ref[:, :, None, :, :] + offsets / wh[None, None, None, :, :]
+        if ref.shape[-1] == 4:
             scale = self.num_points_scale.float()[None, None, None, :, None]
-            locations = ref[:, :, None, :, :2] + offsets * scale * ref[:, :, None, :, 2:] * self.offset_scale
-        else:
-            raise ValueError("the last dimension of reference_points must be 2 or 4, but is %d" % ref.shape[-1])
-        out = self._core(value, shapes, self.num_points_list, locations, weights)
-        return self.output_proj(out)
+            return ref[:, :, None, :, :2] + offsets * scale * ref[:, :, None, :, 2:] * self.offset_scale
+        raise ValueError("the last dimension of reference_points must be 2 or 4, but is %d" % ref.shape[-1])
 
     def extra_repr(self):
         return "embed_dim=%d, num_heads=%d, num_levels=%d, num_points=%s, offset_scale=%s" % (
