@@ -47,6 +47,12 @@ behind the reference's own operator surface.
                                                        flash_deform_attn_points_forward / _backward,
                                                        MSDeformableAttentionFused, pack_loc_attn_points /
                                                        unpack_loc_attn_points -- also exported here
+    modulated_deform_conv_amd.afda                     anchored packed deformable attention (the packed row of RAW offsets
+                                                       and logits of one linear layer plus the reference points or boxes;
+                                                       the reference arithmetic and the softmax inside the operator; C ABI
+                                                       in include/mdconv_afda.h): AnchoredDeformAttnFunction,
+                                                       anchored_deform_attn, anchored_deform_attn_forward / _backward,
+                                                       MSDeformableAttentionAnchored -- also exported here
     modulated_deform_conv_amd.distributed              batch-sharded multi-GPU helper (RCCL)
 
 All compute runs in libmdconv_hip.so (hand-written HIP, C ABI in include/mdconv.h); there is no
@@ -71,7 +77,9 @@ _MSDAP = ("ms_deform_attn_points_forward", "ms_deform_attn_points_backward", "MS
           "ms_deform_attn_points", "MSDeformableAttention")
 _FDAP = ("flash_deform_attn_points_forward", "flash_deform_attn_points_backward", "FlashDeformAttnPointsFunction",
          "flash_deform_attn_points", "MSDeformableAttentionFused", "pack_loc_attn_points", "unpack_loc_attn_points")
-__all__ = list(_DCNV3 + _MSDA + _DCNV4 + _FDA + _DROI + _MSDA3D + _DAGG + _MSDAP + _FDAP)
+_AFDA = ("anchored_deform_attn_forward", "anchored_deform_attn_backward", "AnchoredDeformAttnFunction", "anchored_deform_attn",
+         "MSDeformableAttentionAnchored")
+__all__ = list(_DCNV3 + _MSDA + _DCNV4 + _FDA + _DROI + _MSDA3D + _DAGG + _MSDAP + _FDAP + _AFDA)
 
 
 def __getattr__(name):
@@ -103,4 +111,7 @@ def __getattr__(name):
     if name in _FDAP:
         from . import fdap
         return getattr(fdap, name)
+    if name in _AFDA:
+        from . import afda
+        return getattr(afda, name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

@@ -27,7 +27,7 @@ def _hipcc():
 
 
 def _deps():
-    return glob.glob(os.path.join(CSRC, "*.hpp")) + [os.path.join(HERE, "..", "include", h) for h in ("mdconv.h", "mdconv_dagg.h", "mdconv_msdap.h", "mdconv_fdap.h")]
+    return glob.glob(os.path.join(CSRC, "*.hpp")) + [os.path.join(HERE, "..", "include", h) for h in ("mdconv.h", "mdconv_dagg.h", "mdconv_msdap.h", "mdconv_fdap.h", "mdconv_afda.h")]
 
 
 def _stale(target, sources):

@@ -52,12 +52,16 @@ EXPORTS_MSDAP = ("mdconv_msdap_value_len", "mdconv_msdap_points_len", "mdconv_ms
 # include/mdconv_fdap.h (packed deformable attention with a point count per level): likewise
 EXPORTS_FDAP = ("mdconv_fdap_value_len", "mdconv_fdap_loc_attn_len", "mdconv_fdap_workspace_bytes", "mdconv_fdap_forward",
                 "mdconv_fdap_backward")
+# include/mdconv_afda.h (anchored packed deformable attention: reference points and raw offsets): likewise
+EXPORTS_AFDA = ("mdconv_afda_value_len", "mdconv_afda_offs_attn_len", "mdconv_afda_workspace_bytes", "mdconv_afda_forward",
+                "mdconv_afda_backward")
 
 # The descriptor-only queries of the sampling operators, operator -> names: every operator has
 # mdconv_<op>_workspace_bytes(desc, backward) -> size_t besides; out_size takes (desc, axis), a *_len (desc); all return int.
 SAMP_QUERIES = {"dcnv3": ("out_size",), "msda": ("value_len",), "dcnv4": ("out_size", "offset_mask_len"),
                 "fda": ("value_len", "loc_attn_len"), "droi": (), "msda3d": ("value_len",), "dagg": ("feature_len",),
-                "msdap": ("value_len", "points_len"), "fdap": ("value_len", "loc_attn_len")}
+                "msdap": ("value_len", "points_len"), "fdap": ("value_len", "loc_attn_len"),
+                "afda": ("value_len", "offs_attn_len")}
 
 
 class MdconvDesc(ctypes.Structure):
@@ -150,6 +154,13 @@ class MdconvFdapDesc(ctypes.Structure):
     _fields_ = list(MdconvMsdapDesc._fields_)
 
 
+class MdconvAfdaDesc(ctypes.Structure):
+    """Mirror of ``struct mdconv_afda_desc`` (include/mdconv_afda.h): the fields of ``MdconvFdapDesc`` and the four of the
+    reference tensor."""
+    _fields_ = list(MdconvFdapDesc._fields_) + [("ref_levels", ctypes.c_int), ("ref_comps", ctypes.c_int),
+                                                ("offset_scale", ctypes.c_float), ("grad_reference", ctypes.c_int)]
+
+
 _lib = None
 
 
@@ -201,9 +212,9 @@ def lib():
         missing = (() if has_math_query else ("mdconv_math_bf16_used",)) + (() if has_layout_query else ("mdconv_result_layout_supported",))
         missing += () if has_plan_query else ("mdconv_planned_kernels",)
         # (likewise a build from before one of the sampling operators: that operator's wrapper raises there)
-        missing += tuple(n for n in EXPORTS + EXPORTS_DAGG + EXPORTS_MSDAP + EXPORTS_FDAP
+        missing += tuple(n for n in EXPORTS + EXPORTS_DAGG + EXPORTS_MSDAP + EXPORTS_FDAP + EXPORTS_AFDA
                          if n.startswith(tuple("mdconv_%s_" % op for op in SAMP_QUERIES)) and not hasattr(L, n))
-        for name in EXPORTS[11:] + EXPORTS_DAGG + EXPORTS_MSDAP + EXPORTS_FDAP:
+        for name in EXPORTS[11:] + EXPORTS_DAGG + EXPORTS_MSDAP + EXPORTS_FDAP + EXPORTS_AFDA:
             if name not in missing:
                 getattr(L, name).restype = ctypes.c_int
         for op, queries in SAMP_QUERIES.items():

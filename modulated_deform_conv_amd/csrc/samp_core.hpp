@@ -30,6 +30,8 @@
 //                                  gsum the coordinate backward holds for it, and s_pair = sum over the pair's taps of a * gsum
 //   Op::list_factor(g, id, raw)    the factor of sample id from its stored element
 // and every other policy inherits the identities of SampPlainFactor.
+// A policy with one more gradient summed from its taps' location gradients (AfdaOp) also has kTapGrads and tap_grads; see
+// SampTapGrads below.
 #pragma once
 #include "host_util.hpp"
 #include "mfma_tile.hpp"   // raw buffer loads
@@ -219,6 +221,14 @@ struct SampPlainFactor {
   template <class G> static __device__ __forceinline__ float list_factor(const G &, int, float raw) { return raw; }
 };
 
+// A policy with one more gradient, summed from the pixel-space location gradients of its taps (AfdaOp: the reference points
+// its positions start from), declares `static constexpr bool kTapGrads = true` and has
+//   Op::tap_grads<CT>(g, cx, ln, t0, my_tap, my_on, gx, gy, coord)   after the tap batch that begins at t0 of the coordinate
+//                                  backward: gx, gy are the lane's sums of its tap my_tap times the tap's factor, before fx, fy
+// For every other policy the hook does not exist: the kernel's call is discarded at compile time.
+template <class Op, class = void> struct SampTapGrads { static constexpr bool value = false; };
+template <class Op> struct SampTapGrads<Op, decltype((void)Op::kTapGrads)> { static constexpr bool value = Op::kTapGrads; };
+
 // ---- forward ----
 // Taps outside: the VL lanes of a pair build the sampling state of VL consecutive taps at once -- lane j the state of tap
 // t0 + j, from one coordinate pair and one factor -- and then walk those taps together, each state broadcast from the lane that
@@ -354,6 +364,7 @@ __global__ __launch_bounds__(256) void samp_bwd_coord_kernel(typename Op::Geom g
     float fx, fy;   // of my_tap
     Op::template build_tap<CT>(g, cx, ln.pair, my_tap, my_on, coord, factor, mine, fx, fy);
     float r_m = 0.f, r_x = 0.f, r_y = 0.f;   // the sums of my_tap
+    float h_x = 0.f, h_y = 0.f;              // (kTapGrads) its pixel-space location gradients
     const int nt = min(g.ln.VL, g.K - t0);
     for (int jj = 0; jj < nt; ++jj) {
       const SampTap t = g.ln.VL > 1 ? samp_tap_from(mine, ln.first + jj) : mine;
@@ -393,6 +404,10 @@ __global__ __launch_bounds__(256) void samp_bwd_coord_kernel(typename Op::Geom g
         r_m = Op::factor_grad(t.m, s_m, s_pair);
         r_x = s_x * (t.m * fx);
         r_y = s_y * (t.m * fy);
+        if constexpr (SampTapGrads<Op>::value) {
+          h_x = s_x * t.m;
+          h_y = s_y * t.m;
+        }
       }
     }
     if (my_on) {
@@ -400,6 +415,7 @@ __global__ __launch_bounds__(256) void samp_bwd_coord_kernel(typename Op::Geom g
       samp_st<CT>(grad_coord, Op::coord_index(g, cx, ln.pair, my_tap, 0), r_x, g.acc != 0);
       samp_st<CT>(grad_coord, Op::coord_index(g, cx, ln.pair, my_tap, 1), r_y, g.acc != 0);
     }
+    if constexpr (SampTapGrads<Op>::value) Op::template tap_grads<CT>(g, cx, ln, t0, my_tap, my_on, h_x, h_y, coord);
   }
   Op::template finish_pair<CT>(g, cx, ln, grad_coord);
 }
