@@ -244,6 +244,16 @@ int mdconv_last_path(void);
  * native fp16 / bf16 MFMA kernels, or the depthwise kernels (no matrix instructions, no atomics on results). */
 enum { MDCONV_KERNELS_DIRECT = 1, MDCONV_KERNELS_F32 = 2, MDCONV_KERNELS_HP = 3, MDCONV_KERNELS_DEPTHWISE = 4 };
 int mdconv_last_kernels(void);
+/* Geometry variant of the fp32 MFMA kernels the last call of this thread launched (the forward GEMM of a forward, GEMM-1 of a
+ * backward): CANON3X3 = the instances with the geometry of a standard DCNv2 layer compiled in (2-D, 3x3, stride 1, pad 1,
+ * dilation 1, one conv group, one deformable group, modulated), RUNTIME = the instances of any shape -- also for every call
+ * that ran no fp32 MFMA kernel.  The results of the two are bit-identical; MDCONV_GEOM_FIXED=0 in the environment (read once)
+ * keeps every call on RUNTIME. */
+enum { MDCONV_GEOMETRY_RUNTIME = 0, MDCONV_GEOMETRY_CANON3X3 = 1 };
+int mdconv_last_geometry(void);
+/* 1 when the geometry of `d` is the canonical one (the match rule alone, decided without a device: a matching call runs the
+ * CANON3X3 instances where it reaches the wide forward tile / the straight-line GEMM-1), else 0 -- also for an invalid `d`. */
+int mdconv_geometry_is_canonical(const mdconv_desc *d);
 /* The MDCONV_KERNELS_* family the forward (backward = 0) / backward (backward = 1) of `d` would run on -- the routing of the
  * call itself (`path`, `input_layout`, the flags), decided without a device -- or 0 for an invalid descriptor and for a call
  * that would be refused (MDCONV_EUNSUPPORTED).  The two directions of one layer can differ. */

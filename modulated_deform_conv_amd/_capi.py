@@ -42,6 +42,7 @@ EXPORTS = (
     "mdconv_fda_value_len", "mdconv_fda_loc_attn_len", "mdconv_fda_workspace_bytes", "mdconv_fda_forward", "mdconv_fda_backward",
     "mdconv_droi_workspace_bytes", "mdconv_droi_forward", "mdconv_droi_backward",
     "mdconv_msda3d_value_len", "mdconv_msda3d_workspace_bytes", "mdconv_msda3d_forward", "mdconv_msda3d_backward",
+    "mdconv_last_geometry", "mdconv_geometry_is_canonical",
 )
 
 # include/mdconv_dagg.h (deformable aggregation): a header of its own, so a tuple of its own -- EXPORTS is mdconv.h's
@@ -211,6 +212,8 @@ def lib():
             L.mdconv_planned_kernels.argtypes = [ctypes.c_void_p, ctypes.c_int]
         missing = (() if has_math_query else ("mdconv_math_bf16_used",)) + (() if has_layout_query else ("mdconv_result_layout_supported",))
         missing += () if has_plan_query else ("mdconv_planned_kernels",)
+        # (likewise a build from before the canonical-geometry instances: last_geometry() says 'runtime' there)
+        missing += tuple(n for n in ("mdconv_last_geometry", "mdconv_geometry_is_canonical") if not hasattr(L, n))
         # (likewise a build from before one of the sampling operators: that operator's wrapper raises there)
         missing += tuple(n for n in EXPORTS + EXPORTS_DAGG + EXPORTS_MSDAP + EXPORTS_FDAP + EXPORTS_AFDA
                          if n.startswith(tuple("mdconv_%s_" % op for op in SAMP_QUERIES)) and not hasattr(L, n))
@@ -273,6 +276,14 @@ def last_kernels():
 
 
 KERNELS = {0: "none", 1: "direct", 2: "f32", 3: "hp", 4: "depthwise"}   # MDCONV_KERNELS_*
+
+
+def last_geometry():
+    """Geometry variant of the fp32 MFMA kernels the last call launched (its forward GEMM / GEMM-1): 'canon3x3' (the
+    instances with a standard 3x3 DCNv2 layer's geometry compiled in) | 'runtime' (any shape; also when the call ran no
+    fp32 MFMA kernel).  ``MDCONV_GEOM_FIXED=0`` in the environment keeps every call on 'runtime'."""
+    L = lib()
+    return "canon3x3" if hasattr(L, "mdconv_last_geometry") and L.mdconv_last_geometry() == 1 else "runtime"
 
 
 def planned_kernels(desc, backward):

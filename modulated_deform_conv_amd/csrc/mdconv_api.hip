@@ -26,6 +26,7 @@ namespace mdconv {
 static thread_local char g_err[512] = "";
 static thread_local int g_last_path = 0;
 static thread_local int g_last_kernels = 0;
+static thread_local int g_last_geometry = 0;   // MDCONV_GEOMETRY_* of the fp32 matrix kernels the last call launched
 // ABI v1 call modes (descriptors without MDCONV_DESC_V2); v2 descriptors carry their own
 static thread_local int g_accumulate = 1;
 static thread_local int g_input_layout = 0;   // MDCONV_LAYOUT_*
@@ -450,9 +451,12 @@ static int refuse(const CallPlan &cp, const Geom &g, int dt, int path, bool back
   return MDCONV_EUNSUPPORTED;
 }
 
+void note_geometry_variant(int v) { g_last_geometry = v; }
+
 static int run_forward(const mdconv_desc *d, int nd, int modulated, Tensors t, void *ws,
                        size_t ws_bytes, void *stream) {
   g_err[0] = 0;
+  g_last_geometry = 0;
   Geom g;
   int rc = fill_geom(d, &g);
   if (rc) return rc;
@@ -519,6 +523,7 @@ static int run_forward(const mdconv_desc *d, int nd, int modulated, Tensors t, v
 static int run_backward(const mdconv_desc *d, int nd, int modulated, Tensors t, void *ws,
                         size_t ws_bytes, void *stream) {
   g_err[0] = 0;
+  g_last_geometry = 0;
   Geom g;
   int rc = fill_geom(d, &g);
   if (rc) return rc;
@@ -805,6 +810,11 @@ int mdconv_set_path(int path) {
 }
 int mdconv_last_path(void) { return g_last_path; }
 int mdconv_last_kernels(void) { return g_last_kernels; }
+int mdconv_last_geometry(void) { return g_last_geometry; }
+int mdconv_geometry_is_canonical(const mdconv_desc *d) {
+  Geom g;
+  return fill_geom(d, &g) == MDCONV_OK && geom_is_canon3x3(g) ? 1 : 0;
+}
 
 int mdconv_deform_conv2d_forward(const mdconv_desc *d, const void *input, const void *weight,
                                  const void *bias, const void *offset, void *output,

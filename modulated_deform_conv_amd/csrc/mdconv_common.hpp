@@ -53,6 +53,55 @@ __host__ __device__ __forceinline__ int caller_channel(const Geom &g, int c) {
 }
 __host__ __device__ __forceinline__ int caller_channels(const Geom &g) { return g.cm_pad ? g.C_caller : g.C; }
 
+// ---- geometry policies of the fp32 matrix kernels (mfma_fwd.hip, mfma_bwd_data.hip) ----
+// A kernel instance reads the call's geometry through GP::view(kernel argument), and so does everything it hands the
+// view to (out_coords, tap_coords, make_tap, make_pairs*, below).
+//   GeomRuntime   the argument itself: every field is read at run time.  The instances of any shape.
+//   GeomCanon3x3  the argument with the fields that are the same in every DCNv2 layer of a real network replaced by
+//                 literals: 2-D, 3x3 taps, stride 1, pad 1, dilation 1, one conv group, one deformable group, modulated,
+//                 with the gating flavour of the modulated 2-D file (fill_geom).  The tap decomposition, the stride / pad /
+//                 dilation products, the gates and the group logic then fold at compile time; sizes stay run-time values.
+//                 Only operands become literals: every float expression is the one the run-time instance evaluates
+//                 (integer parts fold as integers before the conversion, as they do there), so results are bit-identical.
+// geom_is_canon3x3() is the host's match rule; a call that does not match must not reach a GeomCanon3x3 instance.
+struct GeomRuntime {
+  static constexpr bool kFixed = false;
+  __device__ __forceinline__ static const Geom &view(const Geom &g) { return g; }
+};
+struct GeomCanon3x3 {
+  static constexpr bool kFixed = true;
+  __device__ __forceinline__ static Geom view(const Geom &g) {
+    Geom v = g;
+    v.nd = 2;
+    v.G = 1;
+    v.DG = 1;
+    v.K = 9;
+    v.Cg = v.Cdg = g.C;
+    v.Og = g.O;
+#pragma unroll
+    for (int a = 0; a < 2; ++a) {
+      v.ksz[a] = 3;
+      v.stride[a] = 1;
+      v.pad[a] = 1;
+      v.dil[a] = 1;
+      v.out_sz[a] = g.in_sz[a];   // (in + 2 pad - dil (k - 1) - 1) / stride + 1
+    }
+    v.S_o = g.S_i;
+    v.modulated = 1;
+    v.load_eps = 0;
+    v.atom_eps = 1;
+    v.range_gate = 1;
+    return v;
+  }
+};
+inline bool geom_is_canon3x3(const Geom &g) {
+  if (g.nd != 2 || !g.modulated || g.G != 1 || g.DG != 1 || g.K != 9) return false;
+  for (int a = 0; a < 2; ++a)
+    if (g.ksz[a] != 3 || g.stride[a] != 1 || g.pad[a] != 1 || g.dil[a] != 1 || g.out_sz[a] != g.in_sz[a]) return false;
+  return g.S_o == g.S_i && g.Cg == g.C && g.Cdg == g.C && g.Og == g.O && g.load_eps == 0 && g.atom_eps == 1 &&
+         g.range_gate == 1;
+}
+
 template <typename T> struct Acc { using type = float; };
 template <> struct Acc<double> { using type = double; };
 

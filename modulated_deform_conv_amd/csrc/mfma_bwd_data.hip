@@ -36,6 +36,7 @@
 #include <mutex>
 #include <stdio.h>
 #include <stdlib.h>
+#include <type_traits>
 
 namespace mdconv {
 
@@ -137,9 +138,13 @@ __global__ __launch_bounds__(256) void bwd_prep_kernel(Geom g, int ochunks, int 
 // fetches 4 consecutive channels of ONE corner of its pixel with a 16-byte load -- half the load
 // instructions of the paired NCHW loads and, in 3-D, a third of the cache lines.
 
-template <int ND, bool MOD, int WAVES_C, int QPQ, bool CL>
+// GP: geometry policy (mdconv_common.hpp).  GeomCanon3x3 -- the straight-line 2-D instances of a standard DCNv2 layer -- folds
+// the tap decomposition, the stride / pad / dilation products, the gates, the conv-group ranges (`krange`) and the
+// per-block deformable-group logic (`per_block`, `bpd`, `dg`) at compile time.
+
+template <int ND, bool MOD, int WAVES_C, int QPQ, bool CL, typename GP = GeomRuntime>
 __global__ __launch_bounds__(256, 2) void mfma_bwd_data_kernel(
-    Geom g, BwdDims bd, const float *__restrict__ input, const float *__restrict__ gout,
+    Geom g_arg, BwdDims bd, const float *__restrict__ input, const float *__restrict__ gout,
     const float *__restrict__ wq, const float *__restrict__ offset, const float *__restrict__ mask,
     float *__restrict__ gcol, float *__restrict__ grad_offset, float *__restrict__ grad_mask,
     float *__restrict__ ga, float *__restrict__ bias_part, int *__restrict__ cnt,
@@ -152,6 +157,8 @@ __global__ __launch_bounds__(256, 2) void mfma_bwd_data_kernel(
   constexpr int NBATCH = MB * 16 / RB;
   constexpr int HS = NBATCH / 2, CPS = NC / HS;   // CL drain: batches per half tile, corners per batch
   constexpr int kOob = 0x7ffffff0;         // out-of-range buffer offset: loads give 0, stores drop
+  static_assert(!GP::kFixed || (ND == 2 && MOD && QPQ > 0), "the canonical geometry is 2-D, modulated, one conv group");
+  const auto &g = GP::view(g_arg);
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int T_o = bd.ochunks;              // multiple of 4
   const int gpitch = T_o * 16 + 4;         // floats per pixel row of the grad_out tile
@@ -1010,7 +1017,7 @@ int mfma_bwd_data_f32(const Geom &g, const BwdDims &bd, const Tensors &t, const 
                       const float *xt, hipStream_t stream) {
   // cnt: per-(image, deformable group, input pixel) counters (zeroed by csr_zero_f32), counted
   // by GEMM-1 (CSR pass 1)
-#define LAUNCH_BD_(ND, MOD, WC, QPQ, CL)                                                            \
+#define LAUNCH_BD_(ND, MOD, WC, QPQ, CL, GP)                                                          \
   do {                                                                                          \
     const int bnp = 32 * (4 / WC);                                                              \
     const int ntiles = (g.N + bnp - 1) / bnp;                                                   \
@@ -1022,7 +1029,7 @@ int mfma_bwd_data_f32(const Geom &g, const BwdDims &bd, const Tensors &t, const 
     static std::once_flag attr_once;                                                            \
     static hipError_t attr_err = hipSuccess;                                                    \
     std::call_once(attr_once, [] {                                                              \
-      attr_err = hipFuncSetAttribute((const void *)mfma_bwd_data_kernel<ND, MOD, WC, QPQ, CL>,  \
+      attr_err = hipFuncSetAttribute((const void *)mfma_bwd_data_kernel<ND, MOD, WC, QPQ, CL, GP>,  \
                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)kBwdDataLdsCap); \
     });                                                                                         \
     if (attr_err != hipSuccess) { set_error("hipFuncSetAttribute: %s", hipGetErrorString(attr_err)); return MDCONV_ELAUNCH; } \
@@ -1037,7 +1044,7 @@ int mfma_bwd_data_f32(const Geom &g, const BwdDims &bd, const Tensors &t, const 
       if (it == occ_by_lds.end()) {                                                             \
         int nq = 0;                                                                             \
         (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(                                     \
-            &nq, (const void *)mfma_bwd_data_kernel<ND, MOD, WC, QPQ, CL>, 256, lds);           \
+            &nq, (const void *)mfma_bwd_data_kernel<ND, MOD, WC, QPQ, CL, GP>, 256, lds);           \
         (void)hipGetLastError();                                                                \
         it = occ_by_lds.emplace(lds, nq > 0 ? nq : (lds * 2 <= 160 * 1024 ? 2 : 1)).first;      \
       }                                                                                         \
@@ -1049,8 +1056,12 @@ int mfma_bwd_data_f32(const Geom &g, const BwdDims &bd, const Tensors &t, const 
     static const bool debug_plan = getenv("MDCONV_DEBUG_PLAN") != nullptr;                      \
     if (debug_plan)                                                                             \
       fprintf(stderr, "[mdconv] GEMM-1 plan: %d tiles, %zu B LDS, %d resident per CU\n", ntiles, lds, occ_q); \
+    if (debug_plan)                                                                             \
+      fprintf(stderr, "[mdconv] GEMM-1 instance <%d,%d,%d,%d,%d>, geometry: %s\n", ND, (int)MOD, WC, QPQ, (int)CL, \
+              GP::kFixed ? "canonical 3x3 (compile-time)" : "run-time");                       \
+    note_geometry_variant(GP::kFixed ? 1 : 0);                                                  \
     const int n_tail = (int)std::min<int64_t>((int64_t)(ntiles - n_full * tpw) * g.K, slots);   \
-    hipLaunchKernelGGL((mfma_bwd_data_kernel<ND, MOD, WC, QPQ, CL>), dim3(n_full + n_tail), \
+    hipLaunchKernelGGL((mfma_bwd_data_kernel<ND, MOD, WC, QPQ, CL, GP>), dim3(n_full + n_tail), \
                        dim3(256), lds, stream,                                                  \
                        g, bd, (const float *)t.input, (const float *)t.grad_output, wq,         \
                        (const float *)t.offset, (const float *)t.mask, gcol,                    \
@@ -1060,8 +1071,20 @@ int mfma_bwd_data_f32(const Geom &g, const BwdDims &bd, const Tensors &t, const 
 /* channels-last drain only where it pays (3-D) */                                                \
 #define LAUNCH_BD(ND, MOD, WC, QPQ)                                                             \
   do {                                                                                          \
-    if (xt != nullptr && bd.cl_drain) LAUNCH_BD_(ND, MOD, WC, QPQ, true);                       \
-    else LAUNCH_BD_(ND, MOD, WC, QPQ, false);                                                   \
+    if (xt != nullptr && bd.cl_drain) LAUNCH_BD_(ND, MOD, WC, QPQ, true, GeomRuntime);          \
+    else LAUNCH_BD_(ND, MOD, WC, QPQ, false, GeomRuntime);                                      \
+  } while (0)
+/* the straight-line 2-D modulated instances: canonical-geometry twins where the call's geometry matches */ \
+#define LAUNCH_BD_Q(ND, MOD, WC, QPQ)                                                           \
+  do {                                                                                          \
+    /* (no twin for the other instances: GPc is then the run-time policy itself and the branch is dead) */ \
+    using GPc = std::conditional<(ND == 2 && MOD && (QPQ) > 0), GeomCanon3x3, GeomRuntime>::type; \
+    if (GPc::kFixed && geom_canon3x3_selected(g)) {                                             \
+      if (xt != nullptr && bd.cl_drain) LAUNCH_BD_(ND, MOD, WC, QPQ, true, GPc);                \
+      else LAUNCH_BD_(ND, MOD, WC, QPQ, false, GPc);                                            \
+    } else {                                                                                    \
+      LAUNCH_BD(ND, MOD, WC, QPQ);                                                              \
+    }                                                                                           \
   } while (0)
 #define LAUNCH_BD2(ND, MOD)                                                                     \
   do {                                                                                          \
@@ -1069,8 +1092,8 @@ int mfma_bwd_data_f32(const Geom &g, const BwdDims &bd, const Tensors &t, const 
     /* straight-line K loop: 2-D only (the 3-D instances spill ~100 registers) */               \
     const int qpq = (ND == 2 && g.G == 1 && nquads % nbatch == 0 && nquads / nbatch <= 2) ? nquads / nbatch : 0; \
     if (bd.waves_c == 4) {                                                                      \
-      if (ND == 2 && qpq == 1) LAUNCH_BD(ND, MOD, 4, (ND == 2 ? 1 : 0));                        \
-      else if (ND == 2 && qpq == 2) LAUNCH_BD(ND, MOD, 4, (ND == 2 ? 2 : 0));                   \
+      if (ND == 2 && qpq == 1) LAUNCH_BD_Q(ND, MOD, 4, (ND == 2 ? 1 : 0));                      \
+      else if (ND == 2 && qpq == 2) LAUNCH_BD_Q(ND, MOD, 4, (ND == 2 ? 2 : 0));                 \
       else LAUNCH_BD(ND, MOD, 4, 0);                                                            \
     } else if (bd.waves_c == 2) LAUNCH_BD(ND, MOD, 2, 0);                                       \
     else LAUNCH_BD(ND, MOD, 1, 0);                                                              \
@@ -1078,6 +1101,7 @@ int mfma_bwd_data_f32(const Geom &g, const BwdDims &bd, const Tensors &t, const 
   if (g.nd == 2) { if (g.modulated) LAUNCH_BD2(2, true); else LAUNCH_BD2(2, false); }
   else { if (g.modulated) LAUNCH_BD2(3, true); else LAUNCH_BD2(3, false); }
 #undef LAUNCH_BD2
+#undef LAUNCH_BD_Q
 #undef LAUNCH_BD
 #undef LAUNCH_BD_
   return check_launch("mfma_bwd_data");

@@ -42,8 +42,9 @@ namespace mdconv {
 namespace {
 
 
-template <int ND, bool MOD, int BM, int BN, int WM, int WN, bool PADK>
-__global__ __launch_bounds__(256) void mfma_fwd_kernel(Geom g, PackDims pd,
+// GP: geometry policy (mdconv_common.hpp) -- GeomCanon3x3 for the layer every DCNv2 network uses, GeomRuntime for any other
+template <int ND, bool MOD, int BM, int BN, int WM, int WN, bool PADK, typename GP = GeomRuntime>
+__global__ __launch_bounds__(256) void mfma_fwd_kernel(Geom g_arg, PackDims pd,
                                                        const float *__restrict__ input,
                                                        const float *__restrict__ wp,
                                                        const float *__restrict__ bias,
@@ -61,6 +62,9 @@ __global__ __launch_bounds__(256) void mfma_fwd_kernel(Geom g, PackDims pd,
   constexpr int CPT = BK / KSUBS;             // channels per thread per chunk
   static_assert((BM / WM) * (BN / WN) == 4, "4 waves per workgroup");
   static_assert(BK == 16 && CPT >= 1 && BN <= 256 && MB * 2 * 1024 <= 4096, "tile shape");
+
+  static_assert(!GP::kFixed || (ND == 2 && MOD), "the canonical geometry is 2-D and modulated");
+  const auto &g = GP::view(g_arg);
 
   __shared__ __attribute__((aligned(16))) float Bs[2 * BK * BN];  // [2][BK][BN]
 
@@ -133,12 +137,17 @@ __global__ __launch_bounds__(256) void mfma_fwd_kernel(Geom g, PackDims pd,
 
   // Gathers run TWO chunks ahead of the MFMAs (one chunk was not enough to cover the L2/MALL
   // latency: the loads added 0.18 ms to an otherwise 0.97 ms kernel).  voff / wgt describe the
-  // (tap, dg) of the chunk being requested; each of the two in-flight register sets remembers
-  // the weights it was requested with.
+  // (tap, dg) of the chunk being requested, wcm the (tap, dg) of the chunk being committed.  The
+  // state changes once per (tap, dg), not per chunk, so nothing is copied per chunk: `take_state`
+  // moves the requested state over after the last commit of the old one, before the next request
+  // -- the requests of the chunk committed next are out by then, and exactly one chunk of the old
+  // state is committed between the request of a chunk and its own commit.  (Until the canonical
+  // instances each in-flight register set carried a copy of the weights and masks it was requested
+  // with: 2^ND v_mov per chunk.)
   int voff[NP];       // byte offsets of the corner PAIRS of the chunk being requested
   float wgt[NC];      // their weights * mask: [2*pi] first element, [2*pi+1] second
   float2 rg0[CPT][NP], rg1[CPT][NP];
-  float wc0[NC], wc1[NC];
+  float wcm[NC];
   int cur_tap = -1, cur_dg = -1;
   // Elements of the pairs the reference never reads (a corner outside the image, mdeformable_conv.cu:9-34): their
   // weight is 0, but 0 * Inf = NaN, so a non-finite value in the neighbouring pixel must not be multiplied at all.
@@ -146,13 +155,14 @@ __global__ __launch_bounds__(256) void mfma_fwd_kernel(Geom g, PackDims pd,
   // sample sits across the first or the last column -- keeps its load, and the waves that hold such a lane take a
   // select per loaded element in `commit` (lane masks in SGPRs, one v_cndmask each; wave-uniform branch).
   typedef unsigned long long lanemask_t;
-  lanemask_t bad[NC], bad0[NC], bad1[NC];   // of the chunk being requested / of the two in-flight sets
+  lanemask_t bad[NC], badc[NC];   // of the chunk being requested / being committed
 #pragma unroll
-  for (int ci = 0; ci < NC; ++ci) bad[ci] = bad0[ci] = bad1[ci] = 0ull;
+  for (int ci = 0; ci < NC; ++ci) bad[ci] = badc[ci] = 0ull;
 
+  auto dg_of = [&](int c0) { return g.DG == 1 ? 0 : min(grp * g.Cg + c0, g.C - 1) / g.Cdg; };
   // request the gathers of chunk (tap, c0) (and rebuild the sampling state when (tap, dg) changes)
-  auto issue = [&](float2 (&rg)[CPT][NP], float (&wc)[NC], lanemask_t (&bd)[NC], int tap, int c0) {
-    const int dg = g.DG == 1 ? 0 : min(grp * g.Cg + c0, g.C - 1) / g.Cdg;
+  auto issue = [&](float2 (&rg)[CPT][NP], int tap, int c0) {
+    const int dg = dg_of(c0);
     if (tap != cur_tap || dg != cur_dg) {
       float delta[ND];
       const int64_t ob = ((int64_t)(b_g * g.DG + dg) * (ND * g.K) + ND * tap) * g.S_o + pix_g;
@@ -186,11 +196,15 @@ __global__ __launch_bounds__(256) void mfma_fwd_kernel(Geom g, PackDims pd,
       for (int pi = 0; pi < NP; ++pi) {
         rg[i][pi] = buf_load2(r_in, voff[pi], soff + i * g.S_i * 4);
       }
+  };
+  auto take_state = [&]() {
 #pragma unroll
-    for (int ci = 0; ci < NC; ++ci) { wc[ci] = wgt[ci]; bd[ci] = bad[ci]; }
+    for (int ci = 0; ci < NC; ++ci) { wcm[ci] = wgt[ci]; badc[ci] = bad[ci]; }
   };
   // interpolate the gathered corners and publish the B slab of the chunk starting at channel c0
-  auto commit = [&](const float2 (&rgl)[CPT][NP], const float (&wc)[NC], const lanemask_t (&bd)[NC], int c0, float *Bb) {
+  auto commit = [&](const float2 (&rgl)[CPT][NP], int c0, float *Bb) {
+    const float (&wc)[NC] = wcm;
+    const lanemask_t (&bd)[NC] = badc;
     lanemask_t any_bad = 0ull;
 #pragma unroll
     for (int ci = 0; ci < NC; ++ci) any_bad |= bd[ci];
@@ -261,29 +275,36 @@ __global__ __launch_bounds__(256) void mfma_fwd_kernel(Geom g, PackDims pd,
   const int a_last = (T - 1) * slab_bytes;
   int a_soff = tap_lo * cchunks * slab_bytes;   // byte offset of the current chunk in the packed weights
   load_a(ra0, a_soff);
-  issue(rg0, wc0, bad0, tap_lo, 0);
-  issue(rg1, wc1, bad1, tap_lo, BK);
+  issue(rg0, tap_lo, 0);
+  take_state();
+  issue(rg1, tap_lo, BK);
   for (int tap = tap_lo; tap < tap_hi; ++tap) {
     for (int c0 = 0; c0 < pd.Cgp; c0 += 2 * BK) {
       // position of the chunk pair two chunks ahead (past the end: harmless re-request)
-      const bool wrap = c0 + 2 * BK >= pd.Cgp;
+      // (the position is made opaque: seeing that `wrap` is the inner loop's last trip, hipcc peels that trip, and its copy
+      // of the loop body carries the accumulators in VGPRs through the state rebuild -- 116 + 32 registers, occupancy 3)
+      int c_ahead = c0 + 2 * BK;
+      asm volatile("" : "+s"(c_ahead));
+      const bool wrap = c_ahead >= pd.Cgp;
       const int ntap = wrap ? min(tap + 1, g.K - 1) : tap;
       const int nc0 = wrap ? 0 : c0 + 2 * BK;
       // ---- even chunk: LDS buffer 0, fragments ra0, gathers rg0 ----
-      commit(rg0, wc0, bad0, c0, Bs);
+      commit(rg0, c0, Bs);
+      if (g.DG != 1 && dg_of(c0 + BK) != dg_of(c0)) take_state();   // (a tap changes after an odd chunk only)
       __syncthreads();
       // A first: vmcnt retires in order, so fragments requested AFTER the gathers would make the
       // MFMAs that need them wait for those gathers as well
       load_a(ra1, a_soff + slab_bytes);
-      issue(rg0, wc0, bad0, ntap, nc0);
+      issue(rg0, ntap, nc0);
       __builtin_amdgcn_sched_barrier(0);   // keep every request above the MFMA phase
       mma(ra0, Bs);
       // ---- odd chunk: LDS buffer 1, fragments ra1, gathers rg1 ----
-      commit(rg1, wc1, bad1, c0 + BK, Bs + BK * BN);
+      commit(rg1, c0 + BK, Bs + BK * BN);
+      if (wrap || (g.DG != 1 && dg_of(nc0) != dg_of(c0 + BK))) take_state();
       __syncthreads();
       a_soff += 2 * slab_bytes;
       load_a(ra0, min(a_soff, a_last));
-      issue(rg1, wc1, bad1, ntap, nc0 + BK);
+      issue(rg1, ntap, nc0 + BK);
       __builtin_amdgcn_sched_barrier(0);
       mma(ra1, Bs + BK * BN);
     }
@@ -409,14 +430,21 @@ int fwd_tail_reduce_launch(int BM, int BN, const Geom &g, const float *part, con
   return check_launch("fwd_tail_reduce");
 }
 
+// MDCONV_GEOM_FIXED = 0 | 1 (read once, default 1): 0 keeps every call on the run-time-geometry instances of the forward
+// and GEMM-1 (bit-comparison tests, A/B timing).
+bool geom_canon3x3_selected(const Geom &g) {
+  static const int on = getenv("MDCONV_GEOM_FIXED") ? atoi(getenv("MDCONV_GEOM_FIXED")) : 1;
+  return on != 0 && geom_is_canon3x3(g);
+}
+
 namespace {
-template <int ND, bool MOD, int BM, int BN, int WM, int WN, bool PADK>
+template <int ND, bool MOD, int BM, int BN, int WM, int WN, bool PADK, typename GP>
 int fwd_tile_slots() {
   static int slots = 0;
   if (!slots) {
     int n = 0;
     (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(
-        &n, reinterpret_cast<const void *>(&mfma_fwd_kernel<ND, MOD, BM, BN, WM, WN, PADK>), 256, 0);
+        &n, reinterpret_cast<const void *>(&mfma_fwd_kernel<ND, MOD, BM, BN, WM, WN, PADK, GP>), 256, 0);
     (void)hipGetLastError();
     // clamped to kTailMaxPerCu: the tail scratch (fwd_tail_bytes) holds one partial tile per slot, and the tail never
     // has more workgroups than slots (advisor, round 4: an instance that got leaner would otherwise overrun it)
@@ -425,20 +453,22 @@ int fwd_tile_slots() {
   return slots;
 }
 
-template <int ND, bool MOD, int BM, int BN, int WM, int WN, bool PADK>
+template <int ND, bool MOD, int BM, int BN, int WM, int WN, bool PADK, typename GP = GeomRuntime>
 int launch_fwd_tile_k(const Geom &g, const PackDims &pd, const Tensors &t, const float *wp, float *part,
                       hipStream_t stream) {
   const int ntm = (g.Og + BM - 1) / BM;
   const int ntn = (g.N + BN - 1) / BN;
   int full_tiles, ways, n_hi;
-  fwd_tail_plan(g, ntm * ntn, part ? fwd_tile_slots<ND, MOD, BM, BN, WM, WN, PADK>() : 0, &full_tiles, &ways, &n_hi);
+  fwd_tail_plan(g, ntm * ntn, part ? fwd_tile_slots<ND, MOD, BM, BN, WM, WN, PADK, GP>() : 0, &full_tiles, &ways, &n_hi);
   const int tail_tiles = ntm * ntn - full_tiles;
   static const bool debug_plan = getenv("MDCONV_DEBUG_PLAN") != nullptr;
+  if (debug_plan) fprintf(stderr, "[mdconv] forward geometry: %s\n", GP::kFixed ? "canonical 3x3 (compile-time)" : "run-time");
+  note_geometry_variant(GP::kFixed ? 1 : 0);
   if (debug_plan)
     fprintf(stderr, "[mdconv] forward plan: %d x %d tile, %d tiles, slots %d, full %d, tail %d x %d tap ranges (%d of them x %d)\n", BM, BN,
-            ntm * ntn, part ? fwd_tile_slots<ND, MOD, BM, BN, WM, WN, PADK>() : 0, full_tiles, tail_tiles, ways, n_hi, ways + 1);
+            ntm * ntn, part ? fwd_tile_slots<ND, MOD, BM, BN, WM, WN, PADK, GP>() : 0, full_tiles, tail_tiles, ways, n_hi, ways + 1);
   dim3 grid(full_tiles + tail_tiles * ways + n_hi, g.G);
-  hipLaunchKernelGGL((mfma_fwd_kernel<ND, MOD, BM, BN, WM, WN, PADK>), grid, dim3(256), 0, stream,
+  hipLaunchKernelGGL((mfma_fwd_kernel<ND, MOD, BM, BN, WM, WN, PADK, GP>), grid, dim3(256), 0, stream,
                      g, pd, (const float *)t.input, wp, (const float *)t.bias,
                      (const float *)t.offset, (const float *)t.mask, (float *)t.output, ntm, ntn,
                      full_tiles, ways, n_hi, part);
@@ -451,6 +481,13 @@ int launch_fwd_tile_k(const Geom &g, const PackDims &pd, const Tensors &t, const
 template <int ND, bool MOD, int BM, int BN, int WM, int WN>
 int launch_fwd_tile(const Geom &g, const PackDims &pd, const Tensors &t, const float *wp, float *part,
                     hipStream_t stream) {
+  // the canonical-geometry instances: only of the hot tile (BM = 256, wide layers), where the call's geometry matches
+  if constexpr (ND == 2 && MOD && BM == 256) {
+    if (geom_canon3x3_selected(g)) {
+      if (g.Cg % (2 * kBK)) return launch_fwd_tile_k<ND, MOD, BM, BN, WM, WN, true, GeomCanon3x3>(g, pd, t, wp, part, stream);
+      return launch_fwd_tile_k<ND, MOD, BM, BN, WM, WN, false, GeomCanon3x3>(g, pd, t, wp, part, stream);
+    }
+  }
   if (g.Cg % (2 * kBK)) return launch_fwd_tile_k<ND, MOD, BM, BN, WM, WN, true>(g, pd, t, wp, part, stream);
   return launch_fwd_tile_k<ND, MOD, BM, BN, WM, WN, false>(g, pd, t, wp, part, stream);
 }

@@ -18,6 +18,9 @@ int record_weight_ready(hipStream_t stream);
 hipStream_t fork_side_stream(hipStream_t stream);
 int join_side_stream(hipStream_t stream);
 
+// geometry variant of the fp32 matrix kernels a call launched (mdconv_last_geometry): 0 = run-time, 1 = canonical 3x3
+void note_geometry_variant(int v);
+
 // clears `bytes` (a multiple of 2) of device memory with a kernel (graph-capture friendly)
 int zero_bytes(void *p, size_t bytes, hipStream_t stream);
 

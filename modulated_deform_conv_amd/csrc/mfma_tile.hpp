@@ -129,6 +129,9 @@ int fwd_tail_reduce_launch(int BM, int BN, const Geom &g, const float *part, con
                            int tail_tiles, int full_tiles, int ways, int n_hi, hipStream_t stream);
 int mfma_forward_f32(const Geom &g, const PackDims &pd, const Tensors &t, const float *wp, float *part,
                      hipStream_t stream);
+// the call's geometry is the canonical one (geom_is_canon3x3) and MDCONV_GEOM_FIXED does not force the run-time instances:
+// the BM = 256 forward and the straight-line 2-D GEMM-1 then run their GeomCanon3x3 instances (mfma_fwd.hip)
+bool geom_canon3x3_selected(const Geom &g);
 // channels-last gathers (mfma_fwd_cl.hip): xt = scratch for the NHWC copy of the input
 bool fwd_channels_last(const Geom &g);
 size_t fwd_cl_bytes(const Geom &g);
